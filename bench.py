@@ -18,6 +18,12 @@ from ALL ranks' reads (one exchange step over RCCL), then replicated; correction
 
 `python bench.py --gpus N` started by hand spawns its N ranks itself (one fresh child process per GPU,
 before anything touches the GPU); under `python -m torch.distributed.run` it is one of the ranks.
+
+A plain run sets up, warms up, times --steps steps and prints the result line (with the per-kernel timers, phases and
+self-checks of those same steps).  `--full` adds what takes runs of its own: the CPU baseline with its read-by-read
+parity check against the oracle (exit 3 on a mismatch), the host-buffer batches (`host_8192`) and the FASTA file to
+FASTA file leg (`e2e`), as switched by --no-cpu-baseline / --no-e2e.  `--dump-outputs DIR` writes what the last timed
+step computed as .npy files (float32 / float64, under 64 MB in all; see dump_outputs) for comparing two builds.
 """
 from __future__ import annotations
 
@@ -60,8 +66,14 @@ def parse():
     ap.add_argument("--strategy", default="auto", choices=["auto", "dense", "sorted"])
     ap.add_argument("--exchange", default="abi", choices=["abi", "torch"],
                     help="N > 1 set exchange: brx_exchange_* (librccl called from libbrx) or br_amd/dist.py over torch.distributed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the FASTA-file-in -> FASTA-file-out figure")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline (with its parity check against the oracle), the host-buffer batches and "
+                         "the FASTA-file-in -> FASTA-file-out figure; off: only the timed steps and what they measure")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64, < 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the host-buffer and FASTA-file-in -> "
+                                                          "FASTA-file-out figures")
     ap.add_argument("--progress", action="store_true", help="timestamps of the stages on stderr (big configurations)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N > 1 ranks all on cuda:0 with the gloo backend: checks the multi-rank code path where only one "
@@ -73,6 +85,8 @@ def parse():
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="PMC-derived HBM bytes per launch of an EARLIER run of this workload (profiles/collect_pmc.sh)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     # (a rehearsal puts every rank on ONE card: configs[1]'s 1 Gbp per rank fits it, configs[3]'s 6.25 Gbp per rank does not)
     args.config = args.config or (1 if (args.gpus == 1 or args.rehearse_on_one_gpu) else 3)
     cfg = CONFIGS[args.config]
@@ -251,6 +265,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     _lib.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gs, d_out, d_out_off, n_reads, read_len, stream)
 
     def reduce_scalar(v, op, dtype=torch.float64):
         if world == 1:
@@ -341,7 +357,7 @@ def main():
                                  "%.3f ms per step" % (", ".join(n_ for n_ in LANE_AUX if n_ in prof), aux_ms / max(args.steps, 1))}
 
     cpu = e2e = host = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # free the bench's own HBM/host buffers are not needed any more; the legs below bring their own
         # the file-to-file leg first: behind the CPU baseline (16 threads for ~20 s, an 8 GiB table allocated and freed) its
         # host stages measured 3-8x slower on the same box (build 1.0 s instead of 0.16 s per Gbp)
@@ -374,7 +390,7 @@ def main():
             "value": round(value, 4), "unit": "Gbases/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64 k-mers / 1-bit set",
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full,
             "config": {"workload": "BASELINE configs[%d]: synthetic %.2f Gbp/GPU ONT-error %d bp reads, k=%d, set build "
                                    "(-a %d) + %s (-C %d) fwd+rev" % (args.config, total / 1e9, read_len, k, a, mdesc, args.confirm),
                        "reads_per_gpu": n_reads, "bases_per_gpu": total, "genome_len": genome_len,
@@ -520,6 +536,41 @@ def cpu_baseline(args, cfg, gs, k, n_reads, d_out=None, d_out_off=None):
     except MemoryError:
         res["set_build"] = {"value": None, "sample": "host table of k=%d did not fit" % kb}
     return res
+
+
+DUMP_SEED = 0x5EED_B3C4
+DUMP_SAMPLE_BASES = 8 << 20   # corrected bases of the sampled reads, as float32: 32 MiB at most
+DUMP_LENGTH_READS = 2 << 20   # corrected lengths of the first 2 Mi reads, as float64: 16 MiB at most
+
+
+def dump_outputs(out_dir, gs, d_out, d_out_off, n_reads, read_len, stream):
+    """What a caller of the timed path receives from its last step, as .npy files that a run of another build with the
+    same arguments (hence the same synthetic input) can be compared with file for file:
+      corrected_lengths.npy       float64  length of every corrected read (of the first 2 Mi reads in a bigger batch)
+      corrected_sample_reads.npy  float64  indices of a fixed, seeded sample of reads, chosen from n_reads and read_len
+                                           alone so that every build samples the same reads
+      corrected_sample_bases.npy  float32  those reads' corrected bases (ASCII codes), concatenated in index order and
+                                           cut at 8 Mi bases
+      solid_set.npy               float64  the solid set: members, then the two order-independent 64-bit folds of
+                                           brx_set_fingerprint as 32-bit halves, high half first
+    At most 48 MiB and a few kB in all; rank 0's reads only at N > 1 (every rank holds the same set)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    off = d_out_off[:n_reads + 1].cpu().numpy()
+    lengths = np.diff(off[:min(n_reads, DUMP_LENGTH_READS) + 1]).astype(np.float64)
+    n_s = max(1, min(n_reads, DUMP_SAMPLE_BASES // max(read_len, 1)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_reads, size=n_s, replace=False))
+    sample = torch.cat([d_out[int(off[i]):int(off[i + 1])] for i in idx])[:DUMP_SAMPLE_BASES]
+    members, f1, f2 = gs.fingerprint(stream)
+    halves = lambda v: [float((v >> 32) & 0xFFFFFFFF), float(v & 0xFFFFFFFF)]
+    arrays = {"corrected_lengths": lengths,
+              "corrected_sample_reads": idx.astype(np.float64),
+              "corrected_sample_bases": sample.cpu().numpy().astype(np.float32),
+              "solid_set": np.array([float(members)] + halves(f1) + halves(f2), dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def build_roofline(prof, total, steps, build_ms):

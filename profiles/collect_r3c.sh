@@ -4,7 +4,7 @@
 O=$PWD/gpurun_out/r3c
 mkdir -p $O
 R=$PWD
-timeout -k 10 600 python bench.py --steps 10 --warmup 2 > $O/bench.log 2>$O/bench.err; tail -1 $O/bench.log > $O/bench_n1.json
+timeout -k 10 600 python bench.py --full --steps 10 --warmup 2 > $O/bench.log 2>$O/bench.err; tail -1 $O/bench.log > $O/bench_n1.json
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-e2e > $O/stats.log 2>&1
 cd $R

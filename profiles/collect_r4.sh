@@ -5,7 +5,7 @@
 O=$PWD/gpurun_out/${TAG:-r4z}
 mkdir -p $O
 R=$PWD
-echo "== bench (default)"; timeout -k 10 600 python bench.py --steps 10 --warmup 2 > $O/bench.log 2>$O/bench.err; echo "rc=$?"; tail -1 $O/bench.log > $O/bench_n1.json
+echo "== bench (default)"; timeout -k 10 600 python bench.py --full --steps 10 --warmup 2 > $O/bench.log 2>$O/bench.err; echo "rc=$?"; tail -1 $O/bench.log > $O/bench_n1.json
 cd /tmp && export TMPDIR=/tmp
 echo "== kernel stats"; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-e2e > $O/stats.log 2>&1; echo "rc=$?"
 cd $R
