@@ -3040,6 +3040,10 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
             if (unw) // an invariant of the lane form is broken (the output is still right: those reads went to the group kernel)
                 fprintf(stderr, "[brx correct] WARNING: %llu unit record(s) were never written by the lane pass\n", (unsigned long long)unw);
         }
+#ifdef BRX_AP_COUNT
+        fprintf(stderr, "[brx correct] replay chunks with fixes: %llu vector, %llu byte way, %llu partial\n", (unsigned long long)ch->h_ctrl[CTL_AP_VEC],
+                (unsigned long long)ch->h_ctrl[CTL_AP_BYTEWAY], (unsigned long long)ch->h_ctrl[CTL_AP_PARTIAL]);
+#endif
         stats[0] += ch->h_ctrl[CTL_ROUNDS];
         stats[1] += ch->h_ctrl[CTL_PROBES];
         stats[2] += ch->h_ctrl[CTL_TRIGGERS];

@@ -19,7 +19,10 @@ enum { CTL_WORK = 0, CTL_OVERFLOW = 1, CTL_ROUNDS = 2, CTL_PROBES = 3, CTL_TRIGG
        CTL_LANE_UNWRITTEN = 15,
        // ... and the triggers it left to the verify pass (this pass / summed)
        CTL_REV_TRIGS = 16, CTL_REV_TRIGS_SUM = 17,
-       CTL_N = 20 };
+       // builds with -DBRX_AP_COUNT only: 16-byte chunks with fixes that the replay kernels put together from vector
+       // loads, whole chunks that went the byte way, chunks shorter than 16 bytes (the ends of a batch of fixes)
+       CTL_AP_VEC = 18, CTL_AP_BYTEWAY = 19, CTL_AP_PARTIAL = 20,
+       CTL_N = 21 };
 
 // A trigger of a reverse pass that the lean scan could not settle itself (alt_nucs named exactly one alternative): the scan
 // goes on as if the method returned None, and the group kernel checks that it does (SRC == 2 of correct_kernel).

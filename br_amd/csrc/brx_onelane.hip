@@ -58,7 +58,8 @@ constexpr uint32_t U_UNWRITTEN = 0xffffffffu; // res[6] as lane_pass leaves it b
 constexpr int MAX_DEPTH = 3;               // edit lists: own stretch + two stretches scanned after a miss
 constexpr uint32_t MAX_LANE_READ = 1u << 28; // positions are kept in 28 bits of an edit
 // (a 10 kb read has ~250 fixes in ~19 units: batches of 256 fixes / 128 pieces take most reads in one go and leave the
-// replay kernel's LDS at 9.5 KB a block -- 512 / 256 measured 2.37 against 2.22 ms per pass, profiles/r4m_greedy_ab.txt)
+// replay kernel's LDS at 7 KB a block -- 512 / 256 measured 2.37 against 2.22 ms per pass, profiles/r4m_greedy_ab.txt,
+// and 1.46 against 1.30 with the chunks put together in registers, profiles/r5_replay_variants.txt)
 #ifndef BRX_AP_EDITS
 #define BRX_AP_EDITS 256
 #endif
@@ -67,8 +68,11 @@ constexpr uint32_t MAX_LANE_READ = 1u << 28; // positions are kept in 28 bits of
 #endif
 constexpr uint32_t AP_EDITS = BRX_AP_EDITS;   // fixes replayed per batch
 constexpr uint32_t AP_PIECES = BRX_AP_PIECES; // pieces (unit, depth) gathered per batch
+// (one wave per read: the barriers of the replay cost nothing, the lane that walks the chain holds up 63 others instead of
+// 127, and a CU holds twice as many reads -- 1.30 against 1.36 ms per pass with 128 threads, 2.36 with 256,
+// profiles/r5_replay_variants.txt)
 #ifndef BRX_AP_BS
-#define BRX_AP_BS 128
+#define BRX_AP_BS 64
 #endif
 constexpr uint32_t AP_BS = BRX_AP_BS; // threads of One's replay kernel per read
 constexpr uint32_t APW_EDITS = 512; // ... by the walking correctors' replay kernel
@@ -149,6 +153,17 @@ __device__ __forceinline__ uint4 ld16_logical(const uint8_t *in, uint32_t n, uin
     }
     __builtin_memcpy(&q, in + (n - 16u - j), 16);
     return make_uint4(__builtin_bswap32(q.w), __builtin_bswap32(q.z), __builtin_bswap32(q.y), __builtin_bswap32(q.x));
+}
+// the same in two steps, for loads that are issued together and turned round afterwards
+__device__ __forceinline__ uint4 ld16_raw(const uint8_t *in, uint32_t n, uint32_t j, bool flip)
+{
+    uint4 q;
+    __builtin_memcpy(&q, in + (flip ? n - 16u - j : j), 16);
+    return q;
+}
+__device__ __forceinline__ uint4 ld16_turn(const uint4 &q, bool flip)
+{
+    return flip ? make_uint4(__builtin_bswap32(q.w), __builtin_bswap32(q.z), __builtin_bswap32(q.y), __builtin_bswap32(q.x)) : q;
 }
 // first dword of read r in P: 16 bases per dword and five dwords of padding per read (the window prefetches ahead)
 __device__ __forceinline__ uint64_t pack_start(uint64_t in_at, uint32_t r) { return (in_at >> 4) + 5ull * r; }
@@ -908,6 +923,82 @@ __device__ __forceinline__ void copy_bytes(uint8_t *dst, const uint8_t *in, uint
         dst[j] = ld_logical(in, n_read, from + j, flip);
 }
 
+// ---- a 16-byte output chunk of the replay that holds fixes, put together in registers ---------------------------------
+// The chunk [x0, x0 + 16) of a batch's output is cut by its fixes into at most 16 stretches of copied bytes.  Output byte
+// x of stretch m is input byte e_in[m] + (x - e_os[m]): a 16-byte load at e_in[m] + (x0 - e_os[m]) brings the stretch's
+// bytes to the places they take in the chunk, whatever the fixes in front of it consumed -- the address does the
+// shifting.  So a chunk is one such load per stretch it touches (AP_CH of them issued together, then the next AP_CH if
+// the chunk has more), each laid over the chunk from the stretch's first byte on, the fixes' own bases behind them, and one
+// aligned 16-byte store; the short chunks at the ends of a batch are put together the same way and stored byte by byte
+// from the registers.  Only a chunk with a stretch whose load would leave the read (its last bytes, its first ones behind
+// bases put in, a read of fewer than 16) goes the byte way.
+// (three stretches at a time: two sends the 6 % of the chunks with two fixes round again, four costs registers and work
+// for stretches that are hardly ever there -- 1.30 / 1.31 / 1.76 ms per pass, profiles/r5_replay_variants.txt)
+#ifndef BRX_AP_CH
+#define BRX_AP_CH 3
+#endif
+constexpr uint32_t AP_CH = BRX_AP_CH; // stretches (fixes + 1) of a chunk loaded at a time
+
+struct Chunk16 {
+    uint32_t w[4];
+};
+// bytes 0 .. c-1 of a dword (c <= 0: none, c >= 4: all), without a branch or a compare
+__device__ __forceinline__ uint32_t bytes_below(int c)
+{
+    const uint32_t h = 4u * (uint32_t)(c < 0 ? 0 : (c > 4 ? 4 : c)); // (two shifts by half the bits: a shift by 32 is none)
+    return ~((0xffffffffu << h) << h);
+}
+// q's bytes [lo, 16) into the chunk (0 <= lo <= 16)
+__device__ __forceinline__ void chunk_take_from(Chunk16 &o, const uint4 &q, int lo)
+{
+    const uint32_t v[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+        const uint32_t m = bytes_below(lo - 4 * d);
+        o.w[d] = (o.w[d] & m) | (v[d] & ~m);
+    }
+}
+// byte b from place i of the chunk on (whatever follows a fix's base takes its bytes from the place behind it)
+__device__ __forceinline__ void chunk_fill_from(Chunk16 &o, uint32_t i, uint8_t b)
+{
+    const uint32_t v = (uint32_t)b * 0x01010101u;
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+        const uint32_t m = bytes_below((int)i - 4 * d);
+        o.w[d] = (o.w[d] & m) | (v & ~m);
+    }
+}
+// sixteen 2-bit codes, the first in the top bits -> their letters, the first in the lowest byte
+__device__ __forceinline__ uint4 codes_to_bytes(uint32_t c)
+{
+    uint32_t r[4];
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+        const uint32_t v = (c >> (24 - 8 * d)) & 0xffu;
+        r[d] = (uint32_t)bit2nuc(v >> 6) | ((uint32_t)bit2nuc(v >> 4) << 8) | ((uint32_t)bit2nuc(v >> 2) << 16) | ((uint32_t)bit2nuc(v) << 24);
+    }
+    return make_uint4(r[0], r[1], r[2], r[3]);
+}
+// the first `len` (1 .. 16) bytes of the chunk -> dst: one store for a whole chunk (dst is then 16-byte aligned)
+__device__ __forceinline__ void chunk_store(uint8_t *dst, const Chunk16 &o, uint32_t len)
+{
+    if (len == 16u) {
+        *reinterpret_cast<uint4 *>(dst) = make_uint4(o.w[0], o.w[1], o.w[2], o.w[3]);
+        return;
+    }
+    const uint64_t lo = ((uint64_t)o.w[1] << 32) | o.w[0], hi = ((uint64_t)o.w[3] << 32) | o.w[2];
+    for (uint32_t i = 0; i < len; i++)
+        dst[i] = (uint8_t)((i < 8u ? lo >> (8u * i) : hi >> (8u * (i - 8u))) & 0xffu);
+}
+// ... and byte i of a chunk being put together byte by byte
+__device__ __forceinline__ void chunk_or(uint64_t &lo, uint64_t &hi, uint32_t i, uint8_t b)
+{
+    if (i < 8u)
+        lo |= (uint64_t)b << (8u * i);
+    else
+        hi |= (uint64_t)b << (8u * (i - 8u));
+}
+
 // ---- successor table: next_nucs (mod.rs:118-128) of every indexed k-mer, worked out once --------------------------------
 // A walk step asks for the FOUR successors of a solid k-mer (graph.rs:62, gap_size.rs:58) -- four rounds of a lane.  Which
 // of them are solid is a property of the set alone, so it is tabulated beside the index: one byte per slot of every line,
@@ -1450,6 +1541,8 @@ __global__ __launch_bounds__(256, walk_waves(M)) void lane_walk_kernel(LaneArgs 
 // a fix writes one base and consumes `used` bases of the read; everything else is copied through).  Copying is
 // OUTPUT-centric: every thread produces 16 aligned output bytes, finds the fix its first byte lies behind by bisection
 // of the fixes' output offsets (LDS), and in the common case -- no fix inside its 16 bytes -- moves them as one vector.
+// A chunk with fixes is put together in registers from one 16-byte load per stretch of copied bytes (Chunk16 above) and
+// leaves as one vector too: no byte makes a trip to memory of its own.
 
 __global__ __launch_bounds__(AP_BS) void lane_apply_kernel(LaneArgs a)
 {
@@ -1461,8 +1554,8 @@ __global__ __launch_bounds__(AP_BS) void lane_apply_kernel(LaneArgs a)
     __shared__ uint32_t pc_off[AP_PIECES + 1]; // ... and how many came before
     __shared__ uint32_t sh_part[AP_BS / 64];
     __shared__ uint32_t sh_np, sh_next_u, sh_state;
-    // the records of the read's first 256 units, loaded side by side: the chain is walked by ONE lane, and every
-    // dependent trip to global memory it makes is a microsecond the other 255 wait
+    // the records of the read's first AP_BS units, loaded side by side: the chain is walked by ONE lane, and every
+    // dependent trip to global memory it makes is a microsecond the others wait
     __shared__ uint4 sh_ra[AP_BS], sh_rb[AP_BS];
     __shared__ uint64_t sh_eat[AP_BS];
     for (uint32_t r = blockIdx.x; r < p.n_reads; r += gridDim.x) {
@@ -1576,9 +1669,13 @@ __global__ __launch_bounds__(AP_BS) void lane_apply_kernel(LaneArgs a)
                     part += ((e >> 4) - prev_end) + 1u;
                 }
                 uint32_t inc = part; // inclusive scan of the 256 partial sums: inside the wave by shuffles, then the four waves
+                // (the lane number behind an empty asm: the six lane tests of the scan are otherwise worked out once per kernel
+                // and held in twelve scalar registers, which this kernel does not have to spare)
+                uint32_t scan_lane = threadIdx.x & 63u;
+                asm volatile("" : "+v"(scan_lane));
                 for (int o = 1; o < 64; o <<= 1) {
                     const uint32_t v = __shfl_up(inc, o);
-                    if ((int)(threadIdx.x & 63u) >= o)
+                    if ((int)scan_lane >= o)
                         inc += v;
                 }
                 if ((threadIdx.x & 63u) == 63u)
@@ -1622,14 +1719,58 @@ __global__ __launch_bounds__(AP_BS) void lane_apply_kernel(LaneArgs a)
                         const uint32_t copied_end = e_os[m + 1] - 1u; // the fix's own base sits here
                         if (x1 - x0 == 16u && x1 <= copied_end) {
                             *reinterpret_cast<uint4 *>(ob + x0) = ld16_logical(in, n, e_in[m] + (x0 - e_os[m]), p.flip);
-                        } else {
+                            continue;
+                        }
+                        // fixes inside the chunk (or a chunk of fewer than 16 bytes: the ends of a batch): one load per stretch,
+                        // each at the address that puts the stretch's bytes where the chunk wants them (Chunk16 above), AP_CH
+                        // stretches at a time until the chunk is covered
+                        Chunk16 o = {{0u, 0u, 0u, 0u}};
+                        uint32_t bad = n >= 16u ? 0u : ~0u; // (masks, minima and maxima: a compare each would cost a pair of scalar registers)
+                        for (uint32_t mm = m; bad == 0u; mm += AP_CH) {
+                            uint4 q[AP_CH];
+                            uint32_t s_lo[AP_CH], s_fix[AP_CH]; // the stretch's first byte in the chunk, its fix's place << 8 | base
+#pragma unroll
+                            for (uint32_t i = 0; i < AP_CH; i++) {
+                                const uint32_t mi = min(mm + i, nb - 1u);
+                                const uint32_t os = e_os[mi], fp = e_os[mi + 1] - 1u; // the stretch's first byte, its fix's base
+                                const uint32_t j = e_in[mi] + x0 - os;               // (wraps below 0 at the start of a read)
+                                s_lo[i] = min(max(os, x0) - x0, 16u);
+                                const uint32_t need = (uint32_t)((int)(max(os, x0) - min(fp, x1)) >> 31); // ~0: copied bytes in the chunk
+                                const uint32_t outside = (uint32_t)((int)((n - 16u - j) | j) >> 31);     // ~0: the load would leave the read
+                                bad |= need & outside;
+                                q[i] = ld16_raw(in, n, j & need & ~outside, p.flip);
+                                s_fix[i] = (min(fp - x0, 16u) << 8) | (uint32_t)bit2nuc(e_raw[mi] & 3u);
+                            }
+                            // in order: a stretch takes the chunk from its first byte on, its fix's base the bytes behind its
+                            // copied ones, and the next stretch the rest from one byte further on
+#pragma unroll
+                            for (uint32_t i = 0; i < AP_CH; i++) {
+                                chunk_take_from(o, ld16_turn(q[i], p.flip), (int)s_lo[i]);
+                                chunk_fill_from(o, s_fix[i] >> 8, (uint8_t)(s_fix[i] & 0xffu));
+                            }
+                            if (e_os[min(mm + AP_CH, nb)] >= x1)
+                                break;
+                        }
+                        const bool vec = bad == 0u;
+                        if (!vec) {
+                            // the byte way (a load would leave the read: its last bytes, its first ones behind bases put in, reads
+                            // of fewer than 16): the bytes are still gathered before any is stored
+                            uint64_t blo = 0, bhi = 0;
                             for (uint32_t x = x0; x < x1; x++) {
                                 while (x >= e_os[m + 1])
                                     m++;
                                 const uint32_t rel = x - e_os[m];
-                                ob[x] = x + 1u == e_os[m + 1] ? bit2nuc(e_raw[m] & 3u) : ld_logical(in, n, e_in[m] + rel, p.flip);
+                                chunk_or(blo, bhi, x - x0, x + 1u == e_os[m + 1] ? bit2nuc(e_raw[m] & 3u) : ld_logical(in, n, e_in[m] + rel, p.flip));
                             }
+                            o.w[0] = (uint32_t)blo;
+                            o.w[1] = (uint32_t)(blo >> 32);
+                            o.w[2] = (uint32_t)bhi;
+                            o.w[3] = (uint32_t)(bhi >> 32);
                         }
+#ifdef BRX_AP_COUNT
+                        atomicAdd(p.ctrl + (vec ? CTL_AP_VEC : (x1 - x0 == 16u ? CTL_AP_BYTEWAY : CTL_AP_PARTIAL)), 1ull);
+#endif
+                        chunk_store(ob + x0, o, x1 - x0);
                     }
                 }
                 total += batch_total;
@@ -1796,9 +1937,11 @@ __global__ __launch_bounds__(256) void lane_apply_walk_kernel(LaneArgs a)
                 partw += ((e_uc[t] & 0xffffu) + 15u) / 16u + ((e_pos[t] >> 31) ? 2u : 0u);
             }
             uint32_t inc = part, incw = partw;
+            uint32_t scan_lane = threadIdx.x & 63u; // (behind an empty asm, as in lane_apply_kernel)
+            asm volatile("" : "+v"(scan_lane));
             for (int o = 1; o < 64; o <<= 1) {
                 const uint32_t v = __shfl_up(inc, o), vw = __shfl_up(incw, o);
-                if ((int)(threadIdx.x & 63u) >= o) {
+                if ((int)scan_lane >= o) {
                     inc += v;
                     incw += vw;
                 }
@@ -1888,16 +2031,67 @@ __global__ __launch_bounds__(256) void lane_apply_walk_kernel(LaneArgs a)
                     const uint32_t copied_end = e_os[m + 1] - (e_uc[m] & 0xffffu); // the fix's own bases start here
                     if (x1 - x0 == 16u && x1 <= copied_end) {
                         *reinterpret_cast<uint4 *>(ob + x0) = ld16_logical(in, n, e_in[m] + (x0 - e_os[m]), p.flip);
-                    } else {
-                        // (the word of written bases in hand is kept from byte to byte: a fix of a walking corrector writes
-                        // several bases, and a load per byte was most of what this kernel cost beyond One's)
+                        continue;
+                    }
+                    // fixes inside the chunk, or a chunk of fewer than 16 bytes (Chunk16 above): per stretch one load of copied
+                    // bytes and the two words that hold the sixteen written bases the chunk can take from its fix, AP_CH
+                    // stretches at a time until the chunk is covered
+                    Chunk16 o = {{0u, 0u, 0u, 0u}};
+                    uint32_t bad = n >= 16u ? 0u : ~0u;
+                    for (uint32_t mm = m; bad == 0u; mm += AP_CH) {
+                        uint4 q[AP_CH];
+                        uint32_t w0[AP_CH], w1[AP_CH];
+                        uint32_t s_lo[AP_CH], s_mid[AP_CH]; // copied bytes from lo, written bases from mid
+                        int s_t0[AP_CH];                     // written base of the fix at byte 0 of the chunk
+#pragma unroll
+                        for (uint32_t i = 0; i < AP_CH; i++) {
+                            const uint32_t mi = min(mm + i, nb - 1u);
+                            const uint32_t os = e_os[mi], oe = e_os[mi + 1], cnt = e_uc[mi] & 0xffffu, fs = oe - cnt;
+                            const uint32_t j = e_in[mi] + x0 - os; // (wraps below 0 at the start of a read)
+                            s_lo[i] = min(max(os, x0) - x0, 16u);
+                            s_mid[i] = min(max(fs, x0) - x0, 16u);
+                            const uint32_t need = (uint32_t)((int)(max(os, x0) - min(fs, x1)) >> 31); // ~0: copied bytes in the chunk
+                            const uint32_t outside = (uint32_t)((int)((n - 16u - j) | j) >> 31);     // ~0: the load would leave the read
+                            bad |= need & outside;
+                            q[i] = ld16_raw(in, n, j & need & ~outside, p.flip);
+                            // (a stretch without written bases in the chunk reads its piece's first word: any valid address)
+                            const bool needw = fs < x1 && oe > x0 && cnt != 0u;
+                            const int t0 = (int)(x0 - fs);
+                            const uint32_t wi = needw && t0 > 0 ? (uint32_t)t0 >> 4 : 0u, nw = (cnt + 15u) / 16u;
+                            const uint64_t src = pc_src[e_pi[mi]];
+                            const uint32_t *W = a.BW[src >> 60] + (src & 0x0fffffffffffffffull);
+                            if (needw)
+                                W += (e_ws[mi] - e_ws[pc_off[e_pi[mi]]]) + ((e_pos[mi] >> 31) ? 2u : 0u);
+                            s_t0[i] = t0;
+                            w0[i] = W[wi];
+                            w1[i] = W[needw && wi + 1u < nw ? wi + 1u : wi];
+                        }
+                        // in order: a stretch takes the chunk from its first byte on, its fix's bases from where they begin,
+                        // and the next stretch takes the rest from where they end
+#pragma unroll
+                        for (uint32_t i = 0; i < AP_CH; i++) {
+                            chunk_take_from(o, ld16_turn(q[i], p.flip), (int)s_lo[i]);
+                            const uint32_t codes = s_t0[i] >= 0 ? (uint32_t)(((((uint64_t)w0[i] << 32) | w1[i]) << (2u * ((uint32_t)s_t0[i] & 15u))) >> 32)
+                                                                 : w0[i] >> (2u * ((uint32_t)(-s_t0[i]) & 15u));
+                            chunk_take_from(o, codes_to_bytes(codes), (int)s_mid[i]);
+                        }
+                        if (e_os[min(mm + AP_CH, nb)] >= x1)
+                            break;
+                    }
+#ifdef BRX_AP_COUNT
+                    atomicAdd(p.ctrl + (bad == 0u ? CTL_AP_VEC : (x1 - x0 == 16u ? CTL_AP_BYTEWAY : CTL_AP_PARTIAL)), 1ull);
+#endif
+                    if (bad != 0u) {
+                        // the byte way (a load would leave the read): the bytes are gathered before any is stored (the word of
+                        // written bases in hand is kept from byte to byte)
+                        uint64_t blo = 0, bhi = 0;
                         uint32_t w = 0, w_m = 0xffffffffu, w_i = 0;
                         for (uint32_t x = x0; x < x1; x++) {
                             while (x >= e_os[m + 1])
                                 m++;
                             const uint32_t rel = x - e_os[m], seglen = (e_pos[m] & 0x7fffffffu) - e_in[m];
                             if (rel < seglen) {
-                                ob[x] = ld_logical(in, n, e_in[m] + rel, p.flip);
+                                chunk_or(blo, bhi, x - x0, ld_logical(in, n, e_in[m] + rel, p.flip));
                             } else {
                                 const uint32_t tb = rel - seglen; // base tb of the fix
                                 if (w_m != m || w_i != (tb >> 4)) {
@@ -1907,10 +2101,15 @@ __global__ __launch_bounds__(256) void lane_apply_walk_kernel(LaneArgs a)
                                     w_i = tb >> 4;
                                     w = a.BW[src >> 60][(src & 0x0fffffffffffffffull) + (e_ws[m] - e_ws[first_fix]) + ((e_pos[m] >> 31) ? 2u : 0u) + w_i];
                                 }
-                                ob[x] = bit2nuc((w >> (30u - 2u * (tb & 15u))) & 3u);
+                                chunk_or(blo, bhi, x - x0, bit2nuc((w >> (30u - 2u * (tb & 15u))) & 3u));
                             }
                         }
+                        o.w[0] = (uint32_t)blo;
+                        o.w[1] = (uint32_t)(blo >> 32);
+                        o.w[2] = (uint32_t)bhi;
+                        o.w[3] = (uint32_t)(bhi >> 32);
                     }
+                    chunk_store(ob + x0, o, x1 - x0);
                 }
             }
             total += batch_total;
