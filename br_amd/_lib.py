@@ -36,6 +36,12 @@ class Synth(C.Structure):
                 ("sub_e4", C.c_uint32), ("ins_e4", C.c_uint32), ("del_e4", C.c_uint32)]
 
 
+class OutputOpts(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("min_len", C.c_uint32), ("report_fd", C.c_int), ("stats", C.c_uint32)]
+
+
+OUT_MODES = {"plain": 0, "mask": 1, "split": 2}
+
 _vp, _u8p, _u64p = C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)
 _pp = C.POINTER(C.c_void_p)
 
@@ -71,6 +77,12 @@ SIGNATURES = {
     "brx_set_index_drop": (C.c_int, [_vp]),
     "brx_set_index_info": (C.c_int, [_vp, _u64p]),
     "brx_set_get_batch_indexed": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _u64p]),
+    "brx_set_cover_batch_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "brx_set_cover_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "brx_set_cover_split_batch_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp,
+                                                   _vp, _vp, C.c_uint32, C.POINTER(C.c_uint32), _u64p, _vp]),
+    "brx_set_cover_split_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.POINTER(_u8p), C.POINTER(_u64p),
+                                            C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(_u64p), C.POINTER(C.c_uint32)]),
     "brx_set_free": (None, [_vp]),
     "brx_set_count_begin": (C.c_int, [C.c_uint8, C.c_int, C.c_int, _pp]),
     "brx_set_count_add_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
@@ -108,6 +120,8 @@ SIGNATURES = {
     "brx_devpool_trim": (None, []),
     "brx_devpool_bytes": (C.c_uint64, []),
     "brx_run_correction_fd": (C.c_int, [_vp, C.POINTER(Method), C.c_uint32, C.c_bool, C.c_int, C.c_int, C.c_uint32, _u64p]),
+    "brx_run_correction_fd_opts": (C.c_int, [_vp, C.POINTER(Method), C.c_uint32, C.c_bool, C.c_int, C.c_int, C.c_uint32,
+                                             C.POINTER(OutputOpts), _u64p, _u64p]),
     "brx_count_fasta_fd": (C.c_int, [_vp, C.c_int, C.c_uint32, _u64p]),
     "brx_set_insert_fasta_fd": (C.c_int, [_vp, C.c_int, C.c_uint32, _u64p]),
     "brx_set_insert_batch_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp]),

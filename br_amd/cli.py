@@ -14,6 +14,12 @@ pick the threshold from the count spectrum (br_amd/spectrum.py: pcon's published
 reference's tests).  `count -i table` loads a pcon count table ([k][2^(2k-1) u8 counters], layout unpinned: the
 reference holds no such fixture) and thresholds it the same way; `large-kmer -f fasta` (N4) builds a sparse set for odd k <= 31.  `-t` (rayon
 pool size) is accepted and ignored: the GPU is the pool.
+
+Not in the reference, like `--device` (include/brx.h "coverage"; a base is covered when it lies inside a solid k-mer):
+    --mask-weak                write the corrected reads with the bases no solid k-mer covers in lower case
+    --trim-split [MINLEN]      write the covered stretches of at least MINLEN (default 0) bases of every corrected read
+                               as records `name_i [description]` (what LoRDEC's trim-split does after its correction)
+    --cover-report PATH        one per -o: TSV of k-mers / solid k-mers / covered bases / runs per read, before and after
 """
 from __future__ import annotations
 
@@ -43,6 +49,25 @@ def u8(text: str) -> int:
     if not 0 <= v <= 255:
         raise argparse.ArgumentTypeError("%r is not in 0..=255" % text)
     return v
+
+
+def min_len(text: str) -> int:
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("invalid digit found in string: %r" % text)
+    if not 0 <= v < 1 << 32:
+        raise argparse.ArgumentTypeError("%r is not in 0..2^32" % text)
+    return v
+
+
+def output_form(args):
+    """(output_mode, min_len, report paths or None) of the parsed flags; the reports pair with the outputs"""
+    mode = "mask" if args.mask_weak else ("split" if args.trim_split is not None else "plain")
+    n_out = len(args.outputs) if args.outputs else 1
+    if args.cover_report is not None and len(args.cover_report) != n_out:
+        raise SystemExit("Error: %d --cover-report for %d output(s): give one per -o" % (len(args.cover_report), n_out))
+    return mode, (args.trim_split or 0), args.cover_report
 
 
 def open_input(path: str) -> BinaryIO:
@@ -76,6 +101,13 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("-v", "--verbosity", action="count", default=0)
     p.add_argument("-T", "--timestamp", default=None)
     p.add_argument("--device", type=int, default=0, help="GPU index (not in the reference)")
+    form = p.add_mutually_exclusive_group()
+    form.add_argument("--mask-weak", action="store_true",
+                      help="lower-case the bases of the output that no solid k-mer covers (not in the reference)")
+    form.add_argument("--trim-split", type=min_len, nargs="?", const=0, default=None, metavar="MINLEN",
+                      help="write the covered stretches of at least MINLEN bases as records name_i (not in the reference)")
+    p.add_argument("--cover-report", action="append", default=None, metavar="PATH",
+                   help="per-read cover statistics before and after as TSV, one per -o (not in the reference)")
     sub = p.add_subparsers(dest="subcommand", required=True)
 
     def abundance_methods(sp):
@@ -181,6 +213,7 @@ def presence_set(path: str, fmt: str, k: int, dev: int) -> Pcon:
 
 def main(argv: Optional[List[str]] = None) -> int:
     args = parser().parse_args(argv)
+    mode, split_min, report_paths = output_form(args)
     kmer_set = build_set(args)
     names = args.corrections or METHOD_NAMES                          # src/cli.rs:121-131: all five by default
     confirm = 5 if args.confirm is None else args.confirm            # src/cli.rs:135-137
@@ -188,12 +221,14 @@ def main(argv: Optional[List[str]] = None) -> int:
     methods = build_methods(names, kmer_set, confirm, max_search)
     inputs = [open_input(p) for p in args.inputs] if args.inputs else [sys.stdin.buffer]
     outputs = [open(p, "wb") for p in args.outputs] if args.outputs else [io.BufferedWriter(sys.stdout.buffer)]
+    reports = [open(p, "wb") for p in report_paths] if report_paths else None
     try:
-        run_correction(inputs, outputs, methods, args.two_side, args.record_buffer or 8192)
+        run_correction(inputs, outputs, methods, args.two_side, args.record_buffer or 8192, output_mode=mode, min_len=split_min,
+                       reports=reports)
     finally:
-        for f in outputs:
+        for f in outputs + (reports or []):
             f.flush()
-        for f in inputs + outputs:
+        for f in inputs + outputs + (reports or []):
             if f not in (sys.stdin.buffer,):
                 try:
                     f.close()

@@ -13,6 +13,7 @@
 // the input order, so the batch size cannot change a byte); they are what fills the GPU.
 #include "brx_internal.hpp"
 
+#include <algorithm>
 #include <condition_variable>
 #include <deque>
 #include <thread>
@@ -108,6 +109,14 @@ struct Batch {
     uint64_t text_len = 0;
     uint64_t out_total = 0;       // corrected bases of the batch
     bool last = false;
+    // output forms (brx_run_correction_fd_opts): cover statistics of the records as they came in [0, n) and as they go out
+    // [n, 2n), the corrected records' offsets, the batch's report lines; the pieces' definition lines of a split run
+    std::vector<brx_cover_stats_t> cover_st;
+    std::vector<uint64_t> out_off_h;
+    std::string report;
+    std::string pdefs;
+    std::vector<uint32_t> pdef_end;
+    std::vector<uint32_t> piece_read;
     void clear()
     {
         offsets.assign(1, 0);
@@ -115,6 +124,8 @@ struct Batch {
         def_end.clear();
         total = 0;
         last = false;
+        cover_st.clear();
+        report.clear();
     }
     uint32_t n() const { return (uint32_t)def_end.size(); }
 };
@@ -517,8 +528,35 @@ struct Shared {
     }
 };
 
+// what brx_run_correction_fd_opts asks for beyond the plain run; all off = brx_run_correction_fd
+struct OutOpts {
+    uint32_t mode = BRX_OUT_PLAIN;
+    uint32_t min_len = 0;
+    int report_fd = -1;
+    bool stats = false; // cover statistics of the records before and after (a report implies them)
+    bool any() const { return mode != BRX_OUT_PLAIN || stats; }
+};
+
 // device-side buffers of one GPU worker
 struct DevBufs {
+    // output forms: statistics in / out (2 n), the split form of the batch and its piece table
+    brx_cover_stats_t *d_cover_st = nullptr;
+    uint8_t *d_split = nullptr;
+    uint64_t *d_split_off = nullptr;
+    uint32_t *d_piece_read = nullptr;
+    uint64_t cover_st_cap = 0, split_cap = 0, piece_cap = 0;
+    template <typename T>
+    static int grow(T **p, uint64_t *cap, uint64_t need)
+    {
+        if (need <= *cap && *p)
+            return BRX_OK;
+        if (*p)
+            (void)hipFree(*p);
+        *p = nullptr;
+        *cap = need + need / 8 + 64;
+        BRX_HIP(hipMalloc((void **)p, *cap * sizeof(T)));
+        return BRX_OK;
+    }
     uint8_t *d_in = nullptr, *d_out = nullptr;
     uint64_t *d_off = nullptr, *d_out_off = nullptr;
     uint64_t in_cap = 0, out_cap = 0, off_cap = 0;
@@ -599,13 +637,106 @@ struct DevBufs {
             (void)hipFree(d_off);
         if (d_out_off)
             (void)hipFree(d_out_off);
-        for (void *q : {(void *)d_defs, (void *)d_text, (void *)d_def_end, (void *)d_text_off})
+        for (void *q : {(void *)d_defs, (void *)d_text, (void *)d_def_end, (void *)d_text_off, (void *)d_cover_st, (void *)d_split,
+                        (void *)d_split_off, (void *)d_piece_read})
             if (q)
                 (void)hipFree(q);
     }
 };
 
-int correct_one_batch(brx_chain_t *chain, DevBufs &dv, hipStream_t s, Batch &b)
+// The cover passes of one batch (brx_cover.hip), between the correction and the text: statistics of d_in and d_out,
+// case rewritten in place in d_out (mask), or d_out cut into its covered runs (split; the pieces' definition lines are
+// made here on the host from the piece table).  Leaves in seqs / seq_off / n_text what the format kernels lay out.
+int cover_one_batch(const brx_set_t *set, const OutOpts &oo, DevBufs &dv, hipStream_t s, Batch &b, uint64_t out_total,
+                    const uint8_t *&seqs, const uint64_t *&seq_off, uint32_t &n_text)
+{
+    const uint32_t n = b.n();
+    if (oo.stats) {
+        BRX_TRY(DevBufs::grow(&dv.d_cover_st, &dv.cover_st_cap, 2ull * n));
+        BRX_TRY(brx_set_cover_batch_device(set, dv.d_in, dv.d_off, n, b.total, nullptr, nullptr, dv.d_cover_st, s));
+    }
+    if (oo.stats || oo.mode == BRX_OUT_MASK)
+        BRX_TRY(brx_set_cover_batch_device(set, dv.d_out, dv.d_out_off, n, out_total, nullptr, oo.mode == BRX_OUT_MASK ? dv.d_out : nullptr,
+                                           oo.stats ? dv.d_cover_st + n : nullptr, s));
+    if (oo.stats) {
+        b.cover_st.resize(2ull * n);
+        BRX_HIP(hipMemcpyAsync(b.cover_st.data(), dv.d_cover_st, 2ull * n * sizeof(brx_cover_stats_t), hipMemcpyDeviceToHost, s));
+        if (oo.report_fd >= 0) {
+            b.out_off_h.resize((size_t)n + 1);
+            BRX_HIP(hipMemcpyAsync(b.out_off_h.data(), dv.d_out_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
+        }
+        BRX_HIP(hipStreamSynchronize(s));
+        if (oo.report_fd >= 0) {
+            char num[256];
+            for (uint32_t r = 0; r < n; r++) {
+                const uint32_t d0 = r ? b.def_end[r - 1] : 0u;
+                size_t nl = 0; // the name: the definition up to its first blank
+                while (d0 + nl < b.def_end[r] && b.defs[d0 + nl] != ' ')
+                    nl++;
+                b.report.append(b.defs, d0, nl);
+                const brx_cover_stats_t &a = b.cover_st[r], &z = b.cover_st[n + r];
+                snprintf(num, sizeof num, "\t%llu\t%u\t%u\t%u\t%u\t%llu\t%u\t%u\t%u\t%u\n",
+                         (unsigned long long)(b.offsets[r + 1] - b.offsets[r]), a.kmers, a.solid, a.covered, a.runs,
+                         (unsigned long long)(b.out_off_h[r + 1] - b.out_off_h[r]), z.kmers, z.solid, z.covered, z.runs);
+                b.report += num;
+            }
+        }
+    }
+    if (oo.mode != BRX_OUT_SPLIT)
+        return BRX_OK;
+    // the bounds of include/brx.h: no retry
+    const uint64_t unit = (uint64_t)std::max<uint32_t>(std::max<uint32_t>((uint32_t)set->k, oo.min_len), 1u) + 1ull;
+    const uint64_t piece_cap = (uint64_t)n + out_total / unit;
+    if (piece_cap >= 0xffffffffull) {
+        set_error("split: batch too large");
+        return BRX_ERR_ARG;
+    }
+    BRX_TRY(DevBufs::grow(&dv.d_split, &dv.split_cap, out_total + 64));
+    uint64_t cap2 = dv.piece_cap;
+    BRX_TRY(DevBufs::grow(&dv.d_split_off, &cap2, piece_cap + 1));
+    BRX_TRY(DevBufs::grow(&dv.d_piece_read, &dv.piece_cap, piece_cap + 1));
+    uint32_t np = 0;
+    uint64_t bytes = 0;
+    BRX_TRY(brx_set_cover_split_batch_device(set, dv.d_out, dv.d_out_off, n, out_total, oo.min_len, dv.d_split, out_total, dv.d_split_off,
+                                             dv.d_piece_read, nullptr, (uint32_t)piece_cap, &np, &bytes, s));
+    b.piece_read.resize(np);
+    if (np) {
+        BRX_HIP(hipMemcpyAsync(b.piece_read.data(), dv.d_piece_read, (size_t)np * 4, hipMemcpyDeviceToHost, s));
+        BRX_HIP(hipStreamSynchronize(s));
+    }
+    // piece i (1-based) of record `name [description]` is `name_i [description]`
+    b.pdefs.clear();
+    b.pdef_end.clear();
+    b.pdef_end.reserve(np);
+    char num[16];
+    uint32_t nth = 0;
+    size_t nl = 0; // length of the current record's name: its definition up to the first blank
+    for (uint32_t p = 0; p < np; p++) {
+        const uint32_t r = b.piece_read[p];
+        const uint32_t d0 = r ? b.def_end[r - 1] : 0u, d1 = b.def_end[r];
+        if (p && b.piece_read[p - 1] == r) {
+            nth++;
+        } else {
+            nth = 1;
+            const void *sp = memchr(b.defs.data() + d0, ' ', d1 - d0);
+            nl = sp ? (size_t)((const char *)sp - (b.defs.data() + d0)) : (size_t)(d1 - d0);
+        }
+        b.pdefs.append(b.defs, d0, nl);
+        char *q = num + sizeof num; // "_" + nth in decimal, written back to front
+        for (uint32_t v = nth; v; v /= 10u)
+            *--q = (char)('0' + v % 10u);
+        *--q = '_';
+        b.pdefs.append(q, (size_t)(num + sizeof num - q));
+        b.pdefs.append(b.defs, d0 + nl, d1 - d0 - nl);
+        b.pdef_end.push_back((uint32_t)b.pdefs.size());
+    }
+    seqs = dv.d_split;
+    seq_off = dv.d_split_off;
+    n_text = np;
+    return BRX_OK;
+}
+
+int correct_one_batch(brx_chain_t *chain, DevBufs &dv, hipStream_t s, Batch &b, const OutOpts &oo)
 {
     const uint32_t n = b.n();
     b.text_len = 0;
@@ -637,18 +768,28 @@ int correct_one_batch(brx_chain_t *chain, DevBufs &dv, hipStream_t s, Batch &b)
     b.out_total = out_total;
     const double t3 = now_s();
     // the FASTA text, on the device: record starts from the corrected lengths and the definitions' lengths, then the text
-    BRX_TRY(dv.ensure_text_meta(b.defs.size(), n));
-    if (!b.defs.empty())
-        BRX_HIP(hipMemcpyAsync(dv.d_defs, b.defs.data(), b.defs.size(), hipMemcpyHostToDevice, s));
-    BRX_HIP(hipMemcpyAsync(dv.d_def_end, b.def_end.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-    text_offsets_kernel<<<1, 1024, 0, s>>>(dv.d_out_off, dv.d_def_end, n, dv.d_text_off);
+    const uint8_t *seqs = dv.d_out;
+    const uint64_t *seq_off = dv.d_out_off;
+    uint32_t n_text = n;
+    if (oo.any())
+        BRX_TRY(cover_one_batch(chain->set, oo, dv, s, b, out_total, seqs, seq_off, n_text));
+    const bool split = oo.mode == BRX_OUT_SPLIT;
+    const std::string &defs = split ? b.pdefs : b.defs;
+    const std::vector<uint32_t> &def_end = split ? b.pdef_end : b.def_end;
+    if (n_text == 0) // (a split batch without a piece)
+        return BRX_OK;
+    BRX_TRY(dv.ensure_text_meta(defs.size(), n_text));
+    if (!defs.empty())
+        BRX_HIP(hipMemcpyAsync(dv.d_defs, defs.data(), defs.size(), hipMemcpyHostToDevice, s));
+    BRX_HIP(hipMemcpyAsync(dv.d_def_end, def_end.data(), (size_t)n_text * 4, hipMemcpyHostToDevice, s));
+    text_offsets_kernel<<<1, 1024, 0, s>>>(seq_off, dv.d_def_end, n_text, dv.d_text_off);
     uint64_t text_len = 0;
-    BRX_HIP(hipMemcpyAsync(&text_len, dv.d_text_off + n, 8, hipMemcpyDeviceToHost, s));
+    BRX_HIP(hipMemcpyAsync(&text_len, dv.d_text_off + n_text, 8, hipMemcpyDeviceToHost, s));
     BRX_HIP(hipStreamSynchronize(s));
     BRX_TRY(dv.ensure_text(text_len));
     BRX_TRY(b.text.reserve(text_len + 64, 0));
     const double t4 = now_s();
-    format_kernel<<<n < 4096u ? n : 4096u, 256, 0, s>>>(dv.d_out, dv.d_out_off, dv.d_defs, dv.d_def_end, dv.d_text_off, n, dv.d_text);
+    format_kernel<<<n_text < 4096u ? n_text : 4096u, 256, 0, s>>>(seqs, seq_off, dv.d_defs, dv.d_def_end, dv.d_text_off, n_text, dv.d_text);
     BRX_HIP(hipGetLastError());
     if (text_len)
         BRX_HIP(hipMemcpyAsync(b.text.p, dv.d_text, text_len, hipMemcpyDeviceToHost, s));
@@ -747,18 +888,19 @@ int stream_fasta_batches(int device, int in_fd, uint32_t max_batch_records, hipS
     return BRX_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int brx_run_correction_fd(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, bool two_side, int in_fd,
-                          int out_fd, uint32_t max_batch_records, uint64_t *stats8)
+int run_correction_impl(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, bool two_side, int in_fd, int out_fd,
+                        uint32_t max_batch_records, const OutOpts &oo, uint64_t *stats8, uint64_t *cover_totals8)
 {
     if (!set || (!methods && n_methods) || n_methods == 0) {
         set_error("null argument / empty method list");
         return BRX_ERR_ARG;
     }
     BRX_TRY(use_device(set->device));
+    uint64_t cover_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (oo.report_fd >= 0) {
+        static const char head[] = "#name\tlen_in\tkmers_in\tsolid_in\tcovered_in\truns_in\tlen_out\tkmers_out\tsolid_out\tcovered_out\truns_out\n";
+        BRX_TRY(write_all(oo.report_fd, head, sizeof head - 1));
+    }
     const int device = set->device;
     const double t_start = now_s();
     std::vector<Batch> slots(N_SLOTS);
@@ -823,7 +965,7 @@ int brx_run_correction_fd(const brx_set_t *set, const brx_method_t *methods, uin
         while (q_ready.pop(b)) {
             if (!sh.failed()) {
                 const double t0 = now_s();
-                st = correct_one_batch(chain, dv, s, *b); // (leaves the batch's FASTA text in b->text)
+                st = correct_one_batch(chain, dv, s, *b, oo); // (leaves the batch's FASTA text in b->text)
                 const double dt = now_s() - t0;
                 if (st != BRX_OK)
                     sh.fail(st);
@@ -867,7 +1009,8 @@ int brx_run_correction_fd(const brx_set_t *set, const brx_method_t *methods, uin
         const int v = e ? atoi(e) : 1;
         return v < 1 ? 1 : (v > 4 ? 4 : v);
     }();
-    const bool positional = n_writers_env > 1 && base_off >= 0 && fl >= 0 && !(fl & O_APPEND) && fstat(out_fd, &st_out) == 0 &&
+    // (a report goes out batch by batch beside the text: one writer, in stream order)
+    const bool positional = oo.report_fd < 0 && n_writers_env > 1 && base_off >= 0 && fl >= 0 && !(fl & O_APPEND) && fstat(out_fd, &st_out) == 0 &&
                             S_ISREG(st_out.st_mode);
     const int n_writers = positional ? n_writers_env : 1;
     // stream offsets: len_of[seq] is recorded when the batch arrives in `done`; [0, frontier_seq) have their offsets
@@ -922,6 +1065,8 @@ int brx_run_correction_fd(const brx_set_t *set, const brx_method_t *methods, uin
             if (!sh.failed())
                 st = positional ? pwrite_all(out_fd, (const char *)b->text.p, b->text_len, (uint64_t)base_off + off)
                                 : write_all(out_fd, (const char *)b->text.p, b->text_len);
+            if (st == BRX_OK && !sh.failed() && oo.report_fd >= 0 && !b->report.empty())
+                st = write_all(oo.report_fd, b->report.data(), b->report.size());
             const double dt = now_s() - t0;
             if (pipe_trace())
                 fprintf(stderr, "[brx pipe] t=%.1f ms: batch %llu written (%.1f ms)\n", (now_s() - t_start) * 1e3,
@@ -936,6 +1081,15 @@ int brx_run_correction_fd(const brx_set_t *set, const brx_method_t *methods, uin
                     bases_in += b->total;
                     bases_out += b->out_total;
                     n_batches++;
+                    const uint32_t nb = b->n();
+                    for (size_t i = 0; i < b->cover_st.size(); i++) {
+                        const brx_cover_stats_t &c = b->cover_st[i];
+                        uint64_t *t = cover_sum + (i < nb ? 0 : 4);
+                        t[0] += c.kmers;
+                        t[1] += c.solid;
+                        t[2] += c.covered;
+                        t[3] += c.runs;
+                    }
                 }
             }
             q_free.push(b);
@@ -970,11 +1124,46 @@ int brx_run_correction_fd(const brx_set_t *set, const brx_method_t *methods, uin
         stats8[6] = (uint64_t)(t_write * 1e9);
         stats8[7] = (uint64_t)((now_s() - t_start) * 1e9);
     }
+    if (cover_totals8)
+        for (int i = 0; i < 8; i++)
+            cover_totals8[i] = cover_sum[i];
     if (sh.status != BRX_OK) {
         set_error("%s", sh.message.c_str());
         return sh.status;
     }
     return BRX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int brx_run_correction_fd(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, bool two_side, int in_fd,
+                          int out_fd, uint32_t max_batch_records, uint64_t *stats8)
+{
+    return run_correction_impl(set, methods, n_methods, two_side, in_fd, out_fd, max_batch_records, OutOpts{}, stats8, nullptr);
+}
+
+int brx_run_correction_fd_opts(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, bool two_side, int in_fd,
+                               int out_fd, uint32_t max_batch_records, const brx_output_opts_t *opts, uint64_t *stats8,
+                               uint64_t *cover_totals8)
+{
+    OutOpts oo;
+    if (opts) {
+        if (opts->mode > BRX_OUT_SPLIT) {
+            set_error("brx_run_correction_fd_opts: output mode %u (0 plain, 1 mask, 2 split)", opts->mode);
+            return BRX_ERR_ARG;
+        }
+        if (opts->mode != BRX_OUT_SPLIT && opts->min_len) {
+            set_error("brx_run_correction_fd_opts: min_len belongs to the split form");
+            return BRX_ERR_ARG;
+        }
+        oo.mode = opts->mode;
+        oo.min_len = opts->min_len;
+        oo.report_fd = opts->report_fd >= 0 ? opts->report_fd : -1;
+        oo.stats = opts->stats != 0 || oo.report_fd >= 0;
+    }
+    return run_correction_impl(set, methods, n_methods, two_side, in_fd, out_fd, max_batch_records, oo, stats8, cover_totals8);
 }
 
 int brx_set_insert_fasta_fd(brx_set_t *set, int in_fd, uint32_t max_batch_records, uint64_t *stats8)

@@ -133,6 +133,71 @@ class Pcon(KmerSet):
         _lib.check(_lib.lib().brx_set_get_batch(self._h, km.ctypes.data, km.size, out.ctypes.data))
         return out.astype(bool)
 
+    # ---- coverage (include/brx.h "coverage", br_amd/cover.py: no counterpart in the reference) ----
+    def cover_batch(self, bases: np.ndarray, offsets: np.ndarray, flags: bool = True, masked: bool = False,
+                    stats: bool = True):
+        """(flags uint8[total] | None, masked uint8[total] | None, stats cover.STATS_DTYPE[n] | None) of a
+        bases / offsets batch: one probe per k-mer, on the GPU (brx_set_cover_batch)."""
+        from . import cover
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        fl = np.zeros(bases.size, dtype=np.uint8) if flags else None
+        mk = np.zeros(bases.size, dtype=np.uint8) if masked else None
+        st = np.zeros(n, dtype=cover.STATS_DTYPE) if stats else None
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        _lib.check(_lib.lib().brx_set_cover_batch(self._h, bases.ctypes.data, offsets.ctypes.data, n, ptr(fl), ptr(mk),
+                                                  ptr(st)))
+        return fl, mk, st
+
+    def cover_batch_device(self, d_bases: int, d_offsets: int, n_reads: int, total_bases: int, d_flags: Optional[int] = None,
+                           d_masked: Optional[int] = None, d_stats: Optional[int] = None,
+                           stream: Optional[int] = None) -> None:
+        _lib.check(_lib.lib().brx_set_cover_batch_device(self._h, d_bases, d_offsets, n_reads, total_bases, d_flags,
+                                                         d_masked, d_stats, stream))
+
+    def cover_reads(self, reads: Sequence[bytes]):
+        """(list of per-read flag arrays, stats array) of `reads`"""
+        from . import cover
+        bases, offs = pack_reads(reads)
+        fl, _, st = self.cover_batch(bases, offs)
+        return cover.unpack_flags(fl, offs), st
+
+    def mask_reads(self, reads: Sequence[bytes]) -> list:
+        """the masked form of every read: upper case where a solid k-mer covers the base, lower case where none does"""
+        bases, offs = pack_reads(reads)
+        _, mk, _ = self.cover_batch(bases, offs, flags=False, masked=True, stats=False)
+        return [mk[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(len(reads))]
+
+    def split_batch(self, bases: np.ndarray, offsets: np.ndarray, min_len: int = 0):
+        """(out uint8[], out_offsets uint64[p+1], piece_read uint32[p], piece_start uint64[p]): the split form"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if not 0 <= int(min_len) < 1 << 32:
+            raise ValueError(f"min_len={min_len} does not fit 32 bits")
+        L = _lib.lib()
+        ob, oo = C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint64)()
+        pr, ps, n = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)(), C.c_uint32(0)
+        _lib.check(L.brx_set_cover_split_batch(self._h, bases.ctypes.data, offsets.ctypes.data, offsets.size - 1, int(min_len),
+                                               C.byref(ob), C.byref(oo), C.byref(pr), C.byref(ps), C.byref(n)))
+        try:
+            p = n.value
+            out_off = np.ctypeslib.as_array(oo, shape=(p + 1,)).copy()
+            total = int(out_off[-1])
+            out = np.ctypeslib.as_array(ob, shape=(max(total, 1),))[:total].copy()
+            piece_read = np.ctypeslib.as_array(pr, shape=(max(p, 1),))[:p].copy()
+            piece_start = np.ctypeslib.as_array(ps, shape=(max(p, 1),))[:p].copy()
+        finally:
+            for q in (ob, oo, pr, ps):
+                L.brx_buf_free(C.cast(q, C.c_void_p))
+        return out, out_off, piece_read, piece_start
+
+    def split_reads(self, reads: Sequence[bytes], min_len: int = 0) -> list:
+        """[(read index, start, bytes)] of the runs of at least min_len covered bases, in order"""
+        bases, offs = pack_reads(reads)
+        out, oo, pr, ps = self.split_batch(bases, offs, min_len)
+        return [(int(pr[i]), int(ps[i]), out[int(oo[i]):int(oo[i + 1])].tobytes()) for i in range(pr.size)]
+
     # ---- Solid-level helpers ----------------------------------------------------------
     def set(self, kmer: int, value: bool = True) -> None:
         _lib.check(_lib.lib().brx_set_set(self._h, kmer, value))

@@ -74,7 +74,7 @@ int brx_version(void);
 int brx_device_count(int *n); /* BRX_OK and *n == 0 when no GPU is visible */
 
 /* per-kernel HIP-event timers (events recorded on the launch stream).  Names:
- * "count_dense", "threshold", "correct_pass", "compact", ...          */
+ * "count_dense", "threshold", "correct_pass", "compact", "cover", ... */
 int brx_profile_enable(int on);
 int brx_profile_reset(void);
 int brx_profile_get(const char *kernel, double *total_ms, uint64_t *launches);
@@ -152,6 +152,52 @@ int brx_set_index_info(const brx_set_t *set, uint64_t *info8);
 int brx_set_get_batch_indexed(const brx_set_t *set, const uint64_t *forward_kmers, uint32_t n, uint8_t *out,
                               uint64_t *n_fallback);
 void brx_set_free(brx_set_t *set);
+
+/* ---- coverage: which bases of a read the set supports.  No counterpart in the reference --------------------------
+ * For a read s of n bytes and a set of k-mer length k:
+ *   solid[i], 0 <= i <= n-k, is KmerSet::get (src/set/pcon.rs:189-191) of the forward k-mer s[i..i+k), every byte coded
+ *     as nuc2bit codes it -- a byte that is not ACGT is a base like any other; n < k gives no k-mers;
+ *   covered[j], 0 <= j < n, is true if some solid[i] holds with j-k+1 <= i <= j;
+ *   a RUN is a maximal stretch of covered bases (at least k long);
+ *   the MASKED form of a read has every letter (either case) in upper case where covered and in lower case where not;
+ *     other bytes stay.  Lower-case letters have the same 2-bit codes, so masking never changes a k-mer;
+ *   the SPLIT form with min_len is the runs of at least min_len bases (0 keeps every run), reads in order, the runs of
+ *     a read in order of their start, each a piece of its own; a read without such a run yields nothing.
+ * One probe per k-mer of the batch, 64 neighbouring positions per wave step, through whatever holds the set (bit
+ * vector, key list + probe index, chained table): a cover call never mutates the set, never drops its index and never
+ * materialises a lazy bit vector (brx_set_bits_state stays 1).  The probe index is built on first use like the
+ * correction entries do.  Scratch comes from the device pool per call, so any number of host threads may cover
+ * against one set on their own streams.  A read holds fewer than 2^32 - 16 bases.                                   */
+#define BRX_COVER_SOLID_START 1u /* the k-mer that starts at this base is in the set */
+#define BRX_COVER_COVERED 2u     /* the base lies inside at least one solid k-mer     */
+typedef struct brx_cover_stats {
+    uint32_t kmers;   /* max(n-k+1, 0)    */
+    uint32_t solid;   /* sum of solid[]   */
+    uint32_t covered; /* sum of covered[] */
+    uint32_t runs;
+} brx_cover_stats_t;
+/* d_flags: one byte per base, laid out like d_bases (the two bits above); d_masked: the masked form, may alias d_bases;
+ * d_stats: n_reads entries.  Any of the three may be NULL.  The work is enqueued on `stream`; the call returns after
+ * its kernels have completed (its scratch goes back to the pool).                                                   */
+int brx_set_cover_batch_device(const brx_set_t *set, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads,
+                               uint64_t total_bases, uint8_t *d_flags, uint8_t *d_masked, brx_cover_stats_t *d_stats,
+                               void *stream);
+/* same on host buffers (offsets[0] == 0); `masked` may alias `bases`                                                  */
+int brx_set_cover_batch(const brx_set_t *set, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, uint8_t *flags,
+                        uint8_t *masked, brx_cover_stats_t *stats);
+/* split form.  Piece p is d_out[d_out_offsets[p] .. d_out_offsets[p+1]) (piece_cap + 1 offsets), bases
+ * d_piece_start[p] .. of read d_piece_read[p] (either table may be NULL).  Bounds a caller can allocate by without a
+ * retry: *out_total <= total_bases, *n_pieces <= n_reads + total_bases / (max(k, min_len, 1) + 1).  BRX_ERR_OVERFLOW
+ * with the needed values in *n_pieces / *out_total (and nothing written) if piece_cap or out_cap is too small -- a call
+ * with both 0 and NULL outputs asks for the sizes.  The order of the pieces is fixed by the definition, never by timing. */
+int brx_set_cover_split_batch_device(const brx_set_t *set, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads,
+                                     uint64_t total_bases, uint32_t min_len, uint8_t *d_out, uint64_t out_cap,
+                                     uint64_t *d_out_offsets, uint32_t *d_piece_read, uint64_t *d_piece_start, uint32_t piece_cap,
+                                     uint32_t *n_pieces, uint64_t *out_total, void *stream);
+/* same on host buffers; the four outputs (*n_pieces + 1 offsets) are allocated by the library: release with brx_buf_free */
+int brx_set_cover_split_batch(const brx_set_t *set, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, uint32_t min_len,
+                              uint8_t **out_bases, uint64_t **out_offsets, uint32_t **piece_read, uint64_t **piece_start,
+                              uint32_t *n_pieces);
 
 /* ---- set build by counting: src/main.rs:72-115 -------------------------------------------
  * Counter::<u8>::new(k) -> count_fasta -> Solid::from_count(k, counts, abundance).
@@ -296,6 +342,29 @@ uint64_t brx_devpool_bytes(void);
  * over the workers) / writing / wall.                                                                        */
 int brx_run_correction_fd(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, bool two_side, int in_fd,
                           int out_fd, uint32_t max_batch_records, uint64_t *stats8);
+/* brx_run_correction_fd with an output form (no counterpart in the reference; "coverage" above has the definitions):
+ *   BRX_OUT_MASK   the corrected records in their masked form: lower case where no solid k-mer covers the base;
+ *   BRX_OUT_SPLIT  the covered runs of at least min_len bases of every corrected record, piece i (1-based, counted over
+ *                  the pieces written) of record `name [description]` as `name_i [description]`; a record without such
+ *                  a run writes nothing (what LoRDEC's trim-split does after its own correction).
+ * The cover pass runs on the corrected batch on the device, between the correction and the layout of the text.
+ * report_fd >= 0: a '#'-headed TSV, one line per input record in input order:
+ *   name len_in kmers_in solid_in covered_in runs_in len_out kmers_out solid_out covered_out runs_out
+ * (the _in columns cost one more cover pass, over the records as they came in; it runs only for a report or stats).
+ * cover_totals8 (may be NULL; filled when stats != 0 or a report is written, else zeros): kmers, solid, covered, runs
+ * summed over the INPUT records [0..3] and over the corrected records [4..7].
+ * opts == NULL, or mode PLAIN without report and stats, is byte for byte brx_run_correction_fd and launches no cover
+ * kernel (profile timer "cover").                                                                                   */
+enum { BRX_OUT_PLAIN = 0, BRX_OUT_MASK = 1, BRX_OUT_SPLIT = 2 };
+typedef struct brx_output_opts {
+    uint32_t mode;    /* BRX_OUT_PLAIN / MASK / SPLIT */
+    uint32_t min_len; /* split only */
+    int report_fd;    /* -1: none */
+    uint32_t stats;   /* non-zero: fill cover_totals8 (a report implies it) */
+} brx_output_opts_t;
+int brx_run_correction_fd_opts(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, bool two_side, int in_fd,
+                               int out_fd, uint32_t max_batch_records, const brx_output_opts_t *opts, uint64_t *stats8,
+                               uint64_t *cover_totals8);
 /* Counter::count_fasta(reader, record_buffer) (src/main.rs:73-78): counts every record of the FASTA stream */
 int brx_count_fasta_fd(brx_counter_t *c, int in_fd, uint32_t max_batch_records, uint64_t *stats8);
 /* Pcon::from_fasta / Hash::from_fasta (src/set/pcon.rs:47-112, src/set/hash.rs:40-60): every record of the stream
