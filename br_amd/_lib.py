@@ -107,6 +107,10 @@ SIGNATURES = {
     "brx_comm_last_stats": (C.c_int, [_vp, _u64p]),
     "brx_comm_free": (None, [_vp]),
     "brx_chain_new": (C.c_int, [_vp, C.POINTER(Method), C.c_uint32, C.c_bool, _pp]),
+    "brx_chain_new_pass": (C.c_int, [_vp, C.POINTER(Method), C.c_uint32, C.c_int, _pp]),
+    "brx_chain_second_pass": (C.c_int, [_vp]),
+    "brx_revcomp_batch_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp]),
+    "brx_revcomp_batch": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_int]),
     "brx_chain_correct_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(_u8p), C.POINTER(_u64p)]),
     "brx_chain_correct_batch_async": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
     "brx_chain_correct_batch_wait": (C.c_int, [_vp, C.POINTER(_u8p), C.POINTER(_u64p)]),
@@ -121,6 +125,8 @@ SIGNATURES = {
     "brx_devpool_bytes": (C.c_uint64, []),
     "brx_run_correction_fd": (C.c_int, [_vp, C.POINTER(Method), C.c_uint32, C.c_bool, C.c_int, C.c_int, C.c_uint32, _u64p]),
     "brx_run_correction_fd_opts": (C.c_int, [_vp, C.POINTER(Method), C.c_uint32, C.c_bool, C.c_int, C.c_int, C.c_uint32,
+                                             C.POINTER(OutputOpts), _u64p, _u64p]),
+    "brx_run_correction_fd_pass": (C.c_int, [_vp, C.POINTER(Method), C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32,
                                              C.POINTER(OutputOpts), _u64p, _u64p]),
     "brx_count_fasta_fd": (C.c_int, [_vp, C.c_int, C.c_uint32, _u64p]),
     "brx_set_insert_fasta_fd": (C.c_int, [_vp, C.c_int, C.c_uint32, _u64p]),

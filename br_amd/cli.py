@@ -20,6 +20,8 @@ Not in the reference, like `--device` (include/brx.h "coverage"; a base is cover
     --trim-split [MINLEN]      write the covered stretches of at least MINLEN (default 0) bases of every corrected read
                                as records `name_i [description]` (what LoRDEC's trim-split does after its correction)
     --cover-report PATH        one per -o: TSV of k-mers / solid k-mers / covered bases / runs per read, before and after
+    --second-pass MODE         reverse (default: the reference's second scan, reads reversed and not complemented),
+                               revcomp (the second scan on the reverse complement: br_amd/strand.py) or none (= -s)
 """
 from __future__ import annotations
 
@@ -31,7 +33,7 @@ import lzma
 import sys
 from typing import BinaryIO, List, Optional
 
-from . import _lib, fasta, spectrum
+from . import _lib, fasta, spectrum, strand
 from .correct import build_methods
 from .driver import run_correction
 from .set import Counter, Pcon
@@ -68,6 +70,13 @@ def output_form(args):
     if args.cover_report is not None and len(args.cover_report) != n_out:
         raise SystemExit("Error: %d --cover-report for %d output(s): give one per -o" % (len(args.cover_report), n_out))
     return mode, (args.trim_split or 0), args.cover_report
+
+
+def second_pass_of(args) -> str:
+    """the second-pass mode of the parsed flags: --second-pass wins where given, -s means none, both must agree"""
+    if args.two_side and args.second_pass not in (None, "none"):
+        raise SystemExit("Error: -s/--two-side means one scan and contradicts --second-pass %s" % args.second_pass)
+    return strand.resolve_second_pass(args.second_pass, args.two_side)
 
 
 def open_input(path: str) -> BinaryIO:
@@ -108,6 +117,9 @@ def parser() -> argparse.ArgumentParser:
                       help="write the covered stretches of at least MINLEN bases as records name_i (not in the reference)")
     p.add_argument("--cover-report", action="append", default=None, metavar="PATH",
                    help="per-read cover statistics before and after as TSV, one per -o (not in the reference)")
+    p.add_argument("--second-pass", choices=["reverse", "revcomp", "none"], default=None,
+                   help="second scan of every read: reverse (default, the reference's), revcomp (on the reverse complement) "
+                        "or none (what -s means) (not in the reference)")
     sub = p.add_subparsers(dest="subcommand", required=True)
 
     def abundance_methods(sp):
@@ -214,6 +226,7 @@ def presence_set(path: str, fmt: str, k: int, dev: int) -> Pcon:
 def main(argv: Optional[List[str]] = None) -> int:
     args = parser().parse_args(argv)
     mode, split_min, report_paths = output_form(args)
+    second_pass = second_pass_of(args)
     kmer_set = build_set(args)
     names = args.corrections or METHOD_NAMES                          # src/cli.rs:121-131: all five by default
     confirm = 5 if args.confirm is None else args.confirm            # src/cli.rs:135-137
@@ -224,7 +237,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     reports = [open(p, "wb") for p in report_paths] if report_paths else None
     try:
         run_correction(inputs, outputs, methods, args.two_side, args.record_buffer or 8192, output_mode=mode, min_len=split_min,
-                       reports=reports)
+                       reports=reports, second_pass=second_pass if args.second_pass is not None else None)
     finally:
         for f in outputs + (reports or []):
             f.flush()

@@ -11,15 +11,20 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, strand
 from .set import Pcon, pack_reads
 
 
 class Chain:
     """The Vec<Box<dyn Corrector>> of build_methods plus the two_side flag, i.e. everything
-    run_correction's per-record closure captures (src/lib.rs:93-128)."""
+    run_correction's per-record closure captures (src/lib.rs:93-128).
 
-    def __init__(self, solid: Pcon, methods: Sequence[Tuple[str, int, int]], two_side: bool = False):
+    second_pass (not in the reference; br_amd/strand.py): "none", "reverse" or "revcomp".  None keeps two_side's
+    meaning (True = one scan, False = the reference's reversed second scan); two_side=True beside another mode raises."""
+
+    def __init__(self, solid: Pcon, methods: Sequence[Tuple[str, int, int]], two_side: bool = False,
+                 second_pass: Optional[str] = None):
+        mode = strand.resolve_second_pass(second_pass, two_side)
         self.solid = solid  # keep the set alive (the reference borrows it: src/lib.rs:143)
         arr = (_lib.Method * max(len(methods), 1))()
         for i, (name, confirm, max_search) in enumerate(methods):
@@ -29,7 +34,18 @@ class Chain:
             arr[i].confirm = confirm
             arr[i].max_search = max_search
         self._h = C.c_void_p()
-        _lib.check(_lib.lib().brx_chain_new(solid._h, arr, len(methods), two_side, C.byref(self._h)))
+        if second_pass is None:
+            _lib.check(_lib.lib().brx_chain_new(solid._h, arr, len(methods), bool(two_side), C.byref(self._h)))
+        else:
+            _lib.check(_lib.lib().brx_chain_new_pass(solid._h, arr, len(methods), strand.PASS_IDS[mode], C.byref(self._h)))
+
+    @property
+    def second_pass(self) -> str:
+        """the chain's second-pass mode, as the library holds it"""
+        v = _lib.lib().brx_chain_second_pass(self._h)
+        if v < 0:
+            _lib.check(v)
+        return {i: nm for nm, i in strand.PASS_IDS.items()}[v]
 
     def __del__(self):
         try:

@@ -2634,8 +2634,27 @@ extern "C" {
 int brx_chain_new(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, bool two_side,
                   brx_chain_t **out)
 {
+    return brx_chain_new_pass(set, methods, n_methods, two_side ? BRX_PASS_NONE : BRX_PASS_REVERSE, out);
+}
+
+int brx_chain_second_pass(const brx_chain_t *ch)
+{
+    if (!ch) {
+        set_error("null argument");
+        return BRX_ERR_ARG;
+    }
+    return ch->second_pass;
+}
+
+int brx_chain_new_pass(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, int second_pass,
+                       brx_chain_t **out)
+{
     if (!set || !out || (!methods && n_methods)) {
         set_error("null argument");
+        return BRX_ERR_ARG;
+    }
+    if (second_pass != BRX_PASS_NONE && second_pass != BRX_PASS_REVERSE && second_pass != BRX_PASS_REVCOMP) {
+        set_error("unknown second-pass mode %d (0 none, 1 reverse, 2 revcomp)", second_pass);
         return BRX_ERR_ARG;
     }
     for (uint32_t m = 0; m < n_methods; m++)
@@ -2648,7 +2667,8 @@ int brx_chain_new(const brx_set_t *set, const brx_method_t *methods, uint32_t n_
     ch->set = set;
     ch->device = set->device;
     ch->methods.assign(methods, methods + n_methods);
-    ch->two_side = two_side;
+    ch->two_side = second_pass == BRX_PASS_NONE;
+    ch->second_pass = second_pass;
     ch->stream = nullptr;
     ch->d_stage[0] = ch->d_stage[1] = nullptr;
     ch->stage_bytes = 0;
@@ -2736,7 +2756,7 @@ static int redo_poisoned_reads(brx_chain *ch, const uint8_t *d_bases, const uint
     BRX_HIP(hipStreamSynchronize(s));
     if (!ch->sub) {
         brx_chain *sub = nullptr;
-        BRX_TRY(brx_chain_new(ch->set, ch->methods.data(), (uint32_t)ch->methods.size(), ch->two_side, &sub));
+        BRX_TRY(brx_chain_new_pass(ch->set, ch->methods.data(), (uint32_t)ch->methods.size(), ch->second_pass, &sub));
         sub->is_sub = true;
         ch->sub = sub;
     }
@@ -2768,7 +2788,11 @@ static int redo_poisoned_reads(brx_chain *ch, const uint8_t *d_bases, const uint
             }
             continue;
         }
-        if (stage_reversed) { // the last pass stored its reads back to front
+        if (ch->second_pass == BRX_PASS_REVCOMP) { // the stage holds the second scan's reads: the other strand
+            rev.assign(src, src + len);
+            revcomp_host(rev.data(), rev.size());
+            src = rev.data();
+        } else if (stage_reversed) { // the last pass stored its reads back to front
             rev.assign(src, src + len);
             std::reverse(rev.begin(), rev.end());
             src = rev.data();
@@ -2844,6 +2868,10 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
             idx.line_bits = nullptr;
 
     const int n_dirs = ch->two_side ? 1 : 2;
+    // BRX_PASS_REVCOMP: the second scan runs over the reverse complement of the first scan's output, materialised in the
+    // other staging buffer.  It meets as many solid k-mers as the first, so it IS a forward pass in every respect
+    // (lane automata, group widths, index rule) and only the byte map around it differs.
+    const bool revcomp = ch->second_pass == BRX_PASS_REVCOMP;
     const int n_methods = (int)ch->methods.size();
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::vector<SideRead> side; // redone reads that do not fit their staging slot (redo_poisoned_reads)
@@ -2885,7 +2913,14 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
         int cur_staged = 0, cur_rev = 0, pp = 0;
         bool any_overflow = false;
         BRX_HIP(hipMemsetAsync(ch->d_ctrl, 0, CTL_N * 8, s));
-        for (int dir = 0; dir < n_dirs && !any_overflow; dir++) {
+        for (int scan = 0; scan < n_dirs && !any_overflow; scan++) {
+            const int dir = revcomp ? 0 : scan; // 1: a scan of the reads back to front (tuned for absent k-mers)
+            if (revcomp && scan == 1 && cur_staged) { // (an empty method list leaves nothing staged: rejected below)
+                revcomp_stage(cur, cur_lens, d_offsets, n_reads, slack, ch->d_stage[pp], ch->d_lens[pp], s);
+                cur = ch->d_stage[pp];
+                cur_lens = ch->d_lens[pp];
+                pp ^= 1;
+            }
             for (int m = 0; m < n_methods; m++) {
                 PassParams p;
                 p.bits = no_bits(ch->set) ? nullptr : ch->set->d_bits;
@@ -3062,7 +3097,9 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
                       (unsigned long long)out_cap);
             return BRX_ERR_OVERFLOW;
         }
-        {
+        if (revcomp) {
+            revcomp_compact(cur, cur_lens, d_offsets, n_reads, slack, d_out_offsets, d_out, s);
+        } else {
             KernelTimer t("compact", s);
             const uint32_t grid = n_reads < (1u << 20) ? n_reads : (1u << 20);
             compact_kernel<<<grid, 256, 0, s>>>(cur, cur_lens, d_offsets, n_reads, slack, cur_rev, d_out_offsets, d_out);

@@ -130,6 +130,16 @@ bool index_wanted(int k);
 
 namespace brx { struct PartState; }
 
+namespace brx {
+// reverse complement of staged reads (brx_strand.hip; profile timers "strand" / "strand_compact"): into the other staging buffer, lengths
+// carried over (a poisoned length stays poisoned), and into the compact output (compact_kernel's sibling)
+void revcomp_stage(const uint8_t *stage_in, const uint32_t *lens_in, const uint64_t *d_offsets, uint32_t n_reads, uint32_t slack,
+                   uint8_t *stage_out, uint32_t *lens_out, hipStream_t s);
+void revcomp_compact(const uint8_t *stage, const uint32_t *lens, const uint64_t *d_offsets, uint32_t n_reads, uint32_t slack,
+                     const uint64_t *d_out_offsets, uint8_t *d_out, hipStream_t s);
+void revcomp_host(uint8_t *p, size_t n); // in place, on the host (the few reads redone outside their batch)
+}
+
 struct brx_counter {
     int k;
     int device;
@@ -149,7 +159,8 @@ struct brx_chain {
     const brx_set *set;
     int device;
     std::vector<brx_method_t> methods;
-    bool two_side;
+    bool two_side;           // second_pass == BRX_PASS_NONE
+    int second_pass = BRX_PASS_REVERSE; // BRX_PASS_*
     hipStream_t stream; // owned
     // workspace (grown on demand)
     uint8_t *d_stage[2];

@@ -888,11 +888,15 @@ int stream_fasta_batches(int device, int in_fd, uint32_t max_batch_records, hipS
     return BRX_OK;
 }
 
-int run_correction_impl(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, bool two_side, int in_fd, int out_fd,
+int run_correction_impl(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, int second_pass, int in_fd, int out_fd,
                         uint32_t max_batch_records, const OutOpts &oo, uint64_t *stats8, uint64_t *cover_totals8)
 {
     if (!set || (!methods && n_methods) || n_methods == 0) {
         set_error("null argument / empty method list");
+        return BRX_ERR_ARG;
+    }
+    if (second_pass != BRX_PASS_NONE && second_pass != BRX_PASS_REVERSE && second_pass != BRX_PASS_REVCOMP) {
+        set_error("unknown second-pass mode %d (0 none, 1 reverse, 2 revcomp)", second_pass);
         return BRX_ERR_ARG;
     }
     BRX_TRY(use_device(set->device));
@@ -954,7 +958,7 @@ int run_correction_impl(const brx_set_t *set, const brx_method_t *methods, uint3
         DevBufs dv;
         int st = use_device(device);
         if (st == BRX_OK)
-            st = brx_chain_new(set, methods, n_methods, two_side, &chain);
+            st = brx_chain_new_pass(set, methods, n_methods, second_pass, &chain);
         if (st == BRX_OK && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) {
             set_error("hipStreamCreate failed");
             st = BRX_ERR_HIP;
@@ -1141,10 +1145,19 @@ extern "C" {
 int brx_run_correction_fd(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, bool two_side, int in_fd,
                           int out_fd, uint32_t max_batch_records, uint64_t *stats8)
 {
-    return run_correction_impl(set, methods, n_methods, two_side, in_fd, out_fd, max_batch_records, OutOpts{}, stats8, nullptr);
+    return run_correction_impl(set, methods, n_methods, two_side ? BRX_PASS_NONE : BRX_PASS_REVERSE, in_fd, out_fd, max_batch_records,
+                               OutOpts{}, stats8, nullptr);
 }
 
 int brx_run_correction_fd_opts(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, bool two_side, int in_fd,
+                               int out_fd, uint32_t max_batch_records, const brx_output_opts_t *opts, uint64_t *stats8,
+                               uint64_t *cover_totals8)
+{
+    return brx_run_correction_fd_pass(set, methods, n_methods, two_side ? BRX_PASS_NONE : BRX_PASS_REVERSE, in_fd, out_fd,
+                                      max_batch_records, opts, stats8, cover_totals8);
+}
+
+int brx_run_correction_fd_pass(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, int second_pass, int in_fd,
                                int out_fd, uint32_t max_batch_records, const brx_output_opts_t *opts, uint64_t *stats8,
                                uint64_t *cover_totals8)
 {
@@ -1163,7 +1176,7 @@ int brx_run_correction_fd_opts(const brx_set_t *set, const brx_method_t *methods
         oo.report_fd = opts->report_fd >= 0 ? opts->report_fd : -1;
         oo.stats = opts->stats != 0 || oo.report_fd >= 0;
     }
-    return run_correction_impl(set, methods, n_methods, two_side, in_fd, out_fd, max_batch_records, oo, stats8, cover_totals8);
+    return run_correction_impl(set, methods, n_methods, second_pass, in_fd, out_fd, max_batch_records, oo, stats8, cover_totals8);
 }
 
 int brx_set_insert_fasta_fd(brx_set_t *set, int in_fd, uint32_t max_batch_records, uint64_t *stats8)

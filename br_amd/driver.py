@@ -12,7 +12,7 @@ from typing import BinaryIO, Dict, Optional, Sequence
 
 import contextlib
 
-from . import _lib, cover, fasta, hostio
+from . import _lib, cover, fasta, hostio, strand
 from .correct import Chain, Corrector
 
 RECORD_BATCH = 8192
@@ -23,7 +23,8 @@ REPORT_HEADER = b"#name\tlen_in\tkmers_in\tsolid_in\tcovered_in\truns_in\tlen_ou
 def run_correction(inputs: Sequence[BinaryIO], outputs: Sequence[BinaryIO], methods: Sequence[Corrector],
                    two_side: bool, record_buffer_len: int = 8192, native: Optional[bool] = None,
                    batch_records: int = 0, output_mode: str = "plain", min_len: int = 0,
-                   reports: Optional[Sequence[Optional[BinaryIO]]] = None, cover_stats: bool = False) -> Dict[str, int]:
+                   reports: Optional[Sequence[Optional[BinaryIO]]] = None, cover_stats: bool = False,
+                   second_pass: Optional[str] = None) -> Dict[str, int]:
     """native (default; BRX_HOST_PIPELINE=0 selects the other): the C++ pipeline of libbrx (brx_run_correction_fd:
     parse / GPU / format on their own threads, batches that fill the GPU).  native=False: the same job record by
     record in Python (fasta.py + Chain.correct_reads), kept as the readable statement of the behaviour and
@@ -34,7 +35,12 @@ def run_correction(inputs: Sequence[BinaryIO], outputs: Sequence[BinaryIO], meth
     with the bases no solid k-mer covers in lower case, "split" writes their covered runs of at least min_len bases as
     records `name_i [description]`; reports (one binary file object per output, or None) receive one TSV line of cover
     statistics per input record, before and after; cover_stats (implied by reports) adds the totals `kmers_in` ..
-    `runs_out` to the returned dict.  Both paths write the same bytes; a plain run is untouched."""
+    `runs_out` to the returned dict.  Both paths write the same bytes; a plain run is untouched.
+
+    second_pass (not in the reference; br_amd/strand.py): "none", "reverse" or "revcomp" -- the second scan on the
+    reverse complement of the first scan's output.  None keeps two_side's meaning; two_side=True beside another mode
+    raises.  With None the calls into the library are the ones made before the option existed."""
+    mode = strand.resolve_second_pass(second_pass, two_side)
     if output_mode not in _lib.OUT_MODES:
         raise ValueError(f"output_mode={output_mode!r}: plain, mask or split")
     if min_len and output_mode != "split":
@@ -56,7 +62,7 @@ def run_correction(inputs: Sequence[BinaryIO], outputs: Sequence[BinaryIO], meth
         specs = (_lib.Method * len(methods))(*[_lib.Method(*_spec_codes(m)) for m in methods])
         for inp, out, rep in zip(inputs, outputs, reports):
             st = (C.c_uint64 * 8)()
-            if not extra:
+            if not extra and second_pass is None:
                 with hostio.input_fd(inp) as ifd, hostio.output_fd(out) as ofd:
                     _lib.check(_lib.lib().brx_run_correction_fd(solid._h, specs, len(methods), two_side, ifd, ofd, batch_records, st))
             else:
@@ -64,15 +70,19 @@ def run_correction(inputs: Sequence[BinaryIO], outputs: Sequence[BinaryIO], meth
                 with hostio.input_fd(inp) as ifd, hostio.output_fd(out) as ofd, \
                         (hostio.output_fd(rep) if rep is not None else contextlib.nullcontext(-1)) as rfd:
                     opts = _lib.OutputOpts(_lib.OUT_MODES[output_mode], int(min_len), rfd, 1 if want_stats else 0)
-                    _lib.check(_lib.lib().brx_run_correction_fd_opts(solid._h, specs, len(methods), two_side, ifd, ofd, batch_records,
-                                                                     C.byref(opts), st, ct))
+                    if second_pass is None:
+                        _lib.check(_lib.lib().brx_run_correction_fd_opts(solid._h, specs, len(methods), two_side, ifd, ofd,
+                                                                         batch_records, C.byref(opts), st, ct))
+                    else:
+                        _lib.check(_lib.lib().brx_run_correction_fd_pass(solid._h, specs, len(methods), strand.PASS_IDS[mode], ifd,
+                                                                         ofd, batch_records, C.byref(opts), st, ct))
                 if want_stats:
                     for key, v in zip(COVER_KEYS, ct):
                         totals[key] = totals.get(key, 0) + int(v)
             for key, v in zip(totals, st):
                 totals[key] += int(v)
         return totals
-    chain = Chain(solid, [m.spec() for m in methods], two_side=two_side)
+    chain = Chain(solid, [m.spec() for m in methods], two_side=two_side, second_pass=second_pass)
     if want_stats:
         totals.update({key: 0 for key in COVER_KEYS})
     form = (output_mode, int(min_len), want_stats) if extra else None

@@ -282,6 +282,27 @@ void brx_comm_free(brx_comm_t *comm);
  * -s flag was given, i.e. the reverse pass is SKIPPED (src/lib.rs:48,110).                  */
 int brx_chain_new(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, bool two_side,
                   brx_chain_t **out);
+/* The second scan of a chain (no counterpart in the reference beyond NONE / REVERSE).  With fwd(x) = mn(..m1(x)), every
+ * mi one Corrector::correct (src/correct/mod.rs:44-108), and rc(x) = the bytes of x in reverse order with A<->T, C<->G,
+ * a<->t, c<->g exchanged and every other byte left as it is, a record s becomes
+ *   BRX_PASS_NONE     fwd(s)                         (-s, two_side = true)
+ *   BRX_PASS_REVERSE  rev(fwd(rev(fwd(s))))          (the reference's default, src/lib.rs:48-55,111: reversed, NOT complemented)
+ *   BRX_PASS_REVCOMP  rc(fwd(rc(fwd(s))))            (the second scan runs along the other strand: it meets as many solid
+ *                                                     k-mers as the first and attacks the right edge of every weak stretch)
+ * brx_chain_new(.., two_side, ..) is brx_chain_new_pass with NONE / REVERSE.  brx_chain_last_stats[3] counts the fixes of
+ * both scans.  brx_chain_second_pass returns the mode (negative brx_status for a null chain).                            */
+enum { BRX_PASS_NONE = 0, BRX_PASS_REVERSE = 1, BRX_PASS_REVCOMP = 2 };
+int brx_chain_new_pass(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, int second_pass,
+                       brx_chain_t **out);
+int brx_chain_second_pass(const brx_chain_t *chain);
+/* rc() of every read of a batch, read r to d_out[d_offsets[r] .. d_offsets[r+1]) (same layout; d_out must not alias
+ * d_bases; a read holds fewer than 2^32 - 1 bases).  Enqueued on `stream` of the current device; returns after the kernel
+ * has completed.  Profile timers: "strand" (this entry and the step between the scans) and "strand_compact" (the
+ * compaction of a REVCOMP chain); a chain in another mode starts neither.                                               */
+int brx_revcomp_batch_device(const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
+                             uint8_t *d_out, void *stream);
+/* same on host buffers, through GPU `device`; `out` holds offsets[n_reads] bytes                                         */
+int brx_revcomp_batch(const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, uint8_t *out, int device);
 /* one batch of records through the whole per-record body of run_correction
  * (src/lib.rs:42-55): every method in order, then (unless two_side) reverse, every method,
  * reverse back.  Output in input order.  *out_bases / *out_offsets are malloc'd by the
@@ -363,6 +384,11 @@ typedef struct brx_output_opts {
     uint32_t stats;   /* non-zero: fill cover_totals8 (a report implies it) */
 } brx_output_opts_t;
 int brx_run_correction_fd_opts(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, bool two_side, int in_fd,
+                               int out_fd, uint32_t max_batch_records, const brx_output_opts_t *opts, uint64_t *stats8,
+                               uint64_t *cover_totals8);
+/* brx_run_correction_fd_opts with the second-pass mode of its chains (BRX_PASS_*; two_side false / true = REVERSE / NONE).
+ * Mask, split, report and totals work on the result as before.                                                         */
+int brx_run_correction_fd_pass(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, int second_pass, int in_fd,
                                int out_fd, uint32_t max_batch_records, const brx_output_opts_t *opts, uint64_t *stats8,
                                uint64_t *cover_totals8);
 /* Counter::count_fasta(reader, record_buffer) (src/main.rs:73-78): counts every record of the FASTA stream */
