@@ -92,6 +92,10 @@ static void resolve(TimerSlot &s)
         if (hipEventSynchronize(p.second) == hipSuccess && hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) {
             s.total_ms += ms;
             s.launches++;
+        } else {
+            // (events of a timer whose stream is gone by now, e.g. a finished pipeline's: the runtime keeps the failed
+            // query as the thread's last error, and the next launch that asks hipGetLastError would take it for its own)
+            (void)hipGetLastError();
         }
         g_pool.push_back(p.first);
         g_pool.push_back(p.second);

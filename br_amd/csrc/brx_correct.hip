@@ -3101,7 +3101,7 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
             revcomp_compact(cur, cur_lens, d_offsets, n_reads, slack, d_out_offsets, d_out, s);
         } else {
             KernelTimer t("compact", s);
-            const uint32_t grid = n_reads < (1u << 20) ? n_reads : (1u << 20);
+            const uint32_t grid = read_grid(n_reads, 1u << 20);
             compact_kernel<<<grid, 256, 0, s>>>(cur, cur_lens, d_offsets, n_reads, slack, cur_rev, d_out_offsets, d_out);
         }
         BRX_HIP(hipStreamSynchronize(s));

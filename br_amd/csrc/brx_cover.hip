@@ -385,7 +385,7 @@ int cover_launch(const brx_set *set, CoverArgs &a, uint64_t total_bases, Scratch
         KernelTimer t("cover_tiles", s);
         cover_tiles_of_kernel<<<(n_reads + 255u) / 256u, 256, 0, s>>>(a);
         BRX_TRY(exclusive_scan_lens(a.tiles_of, n_reads, tmp, a.tile_base, a.n_tiles, s));
-        cover_tile_list_kernel<<<n_reads < 2048u ? n_reads : 2048u, 256, 0, s>>>(a);
+        cover_tile_list_kernel<<<read_grid(n_reads, 2048u), 256, 0, s>>>(a);
     }
     {
         KernelTimer t("cover", s);
@@ -552,7 +552,7 @@ int brx_set_cover_split_batch_device(const brx_set_t *set, const uint8_t *d_base
             {
                 KernelTimer t("cover_runs", s);
                 cover_runs_kernel<<<(uint32_t)((tile_bound + 3ull) / 4ull), 256, 0, s>>>(a);
-                cover_keep_kernel<<<(uint32_t)((n_runs + 255ull) / 256ull < 4096ull ? (n_runs + 255ull) / 256ull : 4096ull), 256, 0, s>>>(a);
+                cover_keep_kernel<<<read_grid((n_runs + 255ull) / 256ull, 4096u), 256, 0, s>>>(a);
             }
             BRX_TRY(exclusive_scan_lens(a.keep_flag, (uint32_t)n_runs, tmp2, piece_of, d_totals + 1, s));
             BRX_TRY(exclusive_scan_lens(a.keep_len, (uint32_t)n_runs, tmp2, byte_of, d_totals + 2, s));
@@ -589,7 +589,7 @@ int brx_set_cover_split_batch_device(const brx_set_t *set, const uint8_t *d_base
     {
         KernelTimer t("cover_copy", s);
         const uint64_t want = (n_runs + 3ull) / 4ull;
-        cover_copy_kernel<<<(uint32_t)(want < 8192ull ? want : 8192ull), 256, 0, s>>>(a);
+        cover_copy_kernel<<<read_grid(want, 8192u), 256, 0, s>>>(a);
     }
     st = hipGetLastError() == hipSuccess ? BRX_OK : BRX_ERR_HIP;
     return sync(st);

@@ -61,6 +61,18 @@ class KernelTimer {
     bool on_;
 };
 
+// unsigned value of an environment variable (brx_onelane.hip), read per call: the tests and fuzzers sweep these
+uint32_t env_u32(const char *name, uint32_t dflt);
+// BRX_READ_GRID: fewer blocks for the helper kernels whose blocks loop over reads, records, runs (so that a small batch
+// takes a block through several of them); unset or 0: the kernel's own cap
+inline uint32_t read_grid(uint64_t want, uint32_t cap)
+{
+    const uint32_t v = env_u32("BRX_READ_GRID", 0u);
+    if (v && v < cap)
+        cap = v;
+    return want < cap ? (uint32_t)want : cap;
+}
+
 // number of 32-bit words of the bitset for a given k (at least 1)
 inline uint64_t set_nbits(int k) { return 1ull << (2 * k - 1); }
 inline uint64_t set_nwords(int k) { uint64_t b = set_nbits(k); return b < 32 ? 1 : b / 32; }

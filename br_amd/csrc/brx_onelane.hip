@@ -2162,12 +2162,6 @@ int grow_dev(void **ptr, uint64_t bytes)
     return BRX_OK;
 }
 
-uint32_t env_u32(const char *name, uint32_t dflt)
-{
-    const char *e = getenv(name); // (read per call: the fuzzers sweep these)
-    return e && *e ? (uint32_t)strtoul(e, nullptr, 10) : dflt;
-}
-
 template <bool IDX, int M>
 void launch_lane_walk(const LaneArgs &a, uint32_t blocks, hipStream_t s)
 {
@@ -2193,6 +2187,12 @@ void launch_lane(const LaneArgs &a, uint32_t blocks, hipStream_t s)
 } // namespace
 
 namespace brx {
+
+uint32_t env_u32(const char *name, uint32_t dflt)
+{
+    const char *e = getenv(name); // (read per call: the fuzzers sweep these)
+    return e && *e ? (uint32_t)strtoul(e, nullptr, 10) : dflt;
+}
 
 void lane_ws_free(brx_chain *ch)
 {
@@ -2388,7 +2388,7 @@ int lane_pass(brx_chain *ch, const PassParams &p, const LanePassInfo &info, hipS
         BRX_HIP(hipMemsetAsync(w->u_res, 0xff, units_bound * 32ull, s));
         lane_units_kernel<<<rb, 256, 0, s>>>(a);
         BRX_TRY(exclusive_scan_lens(w->nu, p.n_reads, ch->d_scan_tmp, w->ubase, p.ctrl + CTL_LANE_UNITS, s));
-        const uint32_t grid = p.n_reads < (1u << 16) ? p.n_reads : (1u << 16);
+        const uint32_t grid = read_grid(p.n_reads, 1u << 16);
         lane_pack_kernel<<<grid, 256, 0, s>>>(a);
     }
     if (use_mask) {

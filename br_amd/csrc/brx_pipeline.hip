@@ -789,7 +789,7 @@ int correct_one_batch(brx_chain_t *chain, DevBufs &dv, hipStream_t s, Batch &b, 
     BRX_TRY(dv.ensure_text(text_len));
     BRX_TRY(b.text.reserve(text_len + 64, 0));
     const double t4 = now_s();
-    format_kernel<<<n_text < 4096u ? n_text : 4096u, 256, 0, s>>>(seqs, seq_off, dv.d_defs, dv.d_def_end, dv.d_text_off, n_text, dv.d_text);
+    format_kernel<<<read_grid(n_text, 4096u), 256, 0, s>>>(seqs, seq_off, dv.d_defs, dv.d_def_end, dv.d_text_off, n_text, dv.d_text);
     BRX_HIP(hipGetLastError());
     if (text_len)
         BRX_HIP(hipMemcpyAsync(b.text.p, dv.d_text, text_len, hipMemcpyDeviceToHost, s));

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void revcomp_kernel(const uint8_t *__restrict_
     }
 }
 
-inline uint32_t grid_of(uint32_t n_reads) { return n_reads < (1u << 20) ? n_reads : (1u << 20); }
+inline uint32_t grid_of(uint32_t n_reads) { return read_grid(n_reads, 1u << 20); }
 
 } // namespace
 

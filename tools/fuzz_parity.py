@@ -181,6 +181,10 @@ while time.time() < t_end:
     rev64 = bool(xrng.random() < 0.5)
     env["BRX_REV_VERIFY_G"] = str(xrng.choice(["", "4"]))  # lanes per open trigger of the verify pass
     env["BRX_REV_LEAN_ONE"] = str(xrng.choice(["", "1"]))  # One's reverse pass in the lean form, too
+    # blocks of the replay kernels and of the other block-per-read helpers (compaction, strand, unit packing): few enough
+    # that every block loops over many reads of the job
+    env["BRX_AP_GRID"] = str(xrng.choice(["", "1", "5"]))
+    env["BRX_READ_GRID"] = str(xrng.choice(["", "1", "5"]))
     if focus == "walklane":
         names[-1] = str(frng.choice(["graph", "gap_size"]))
         env.update({"BRX_LANE": "", "BRX_LANE_WALK": "", "BRX_LANE_CHUNK": str(frng.choice(["64", "100"])),
