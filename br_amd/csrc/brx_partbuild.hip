@@ -45,8 +45,7 @@ constexpr int F_BITS = 12;      // hashes per fine bucket = 4096 (8 KiB of u16 c
 constexpr int MAX_LEVELS = 4;
 constexpr int MAX_DIGIT_BITS = 9;
 // (the scans below keep per-thread partial sums in fixed-size arrays: ln_colscan_kernel tot[2] / run[2] covers 512 digits
-// with 256 threads, col_scan_digits_kernel one wave's 16 digits per lane covers 1024; col_scan_columns_kernel v[8] covers
-// 2048 chunks, which part_add_batch guarantees by doubling the chunk length)
+// with 256 threads, col_scan_digits_kernel one wave's 16 digits per lane covers 1024)
 static_assert(MAX_DIGIT_BITS <= 9, "the digit scans of the partition passes are written for at most 512 digits");
 
 struct Plan {
@@ -191,8 +190,10 @@ struct L1Args {
     uint64_t total;          // bases in the batch
     uint32_t n_items;
     int k, nbits, bits;      // digit = hash >> (nbits - bits)
-    uint32_t *matrix;        // [n_items][B] per-tile digit counts (hist): a tile's B counters are one coalesced row ...
-    const uint64_t *pos;     // ... and, same layout, where the tile's keys of each digit go (col_scan_* below)
+    uint32_t *matrix;        // [n_items][B] per-tile digit counts (hist): a tile's B counters are one coalesced row
+    uint32_t n_ranges;       // ranges of tiles = blocks of the partition kernels (l1_range)
+    uint64_t *rsum;          // [n_ranges][B]: keys of digit b in range r (hist), then in the ranges before r (col_scan_columns)
+    const uint64_t *coff;    // [B + 1] keys of all digits < b (col_scan_digits)
     uint32_t *keys_out;      // hash with the digit stripped
     uint64_t out_cap;        // entries of keys_out (checked under BRX_DEBUG_BOUNDS)
 };
@@ -244,7 +245,8 @@ __device__ __forceinline__ void l1_prepare(const L1Args &a, uint32_t item, uint3
     __syncthreads();
 }
 
-// a block's tiles: a contiguous range, taken in rising order
+// a block's tiles: a contiguous range, taken in rising order.  The partition kernels are launched with one block per range
+// (part_add_batch), so the histogram's range sums, the scan and the scatter speak of the same ranges.
 __device__ __forceinline__ void l1_range(uint32_t n_items, uint32_t &lo, uint32_t &hi)
 {
     lo = (uint32_t)(((uint64_t)blockIdx.x * n_items) / gridDim.x);
@@ -252,12 +254,14 @@ __device__ __forceinline__ void l1_range(uint32_t n_items, uint32_t &lo, uint32_
 }
 
 // The same preparation, one tile ahead.  A tile's global loads -- its bases, the first read offsets behind its start, its
-// row of counts -- are three round trips to memory with everybody waiting (the second depends on sh_r0), and a block has
-// only its own four waves to hide them behind: measured, most of a tile's 13 us.  l1_fetch() issues them for the NEXT
-// tile into registers as soon as sh_r0 of the current one is known; l1_consume() is l1_prepare() fed from them.
+// row of counts -- are round trips to memory with everybody waiting, and a block has only its own four waves to hide
+// them behind.  l1_fetch() issues them for a LATER tile into registers and does nothing else: no arithmetic on a loaded
+// value lives here (a single subtraction made the compiler wait for every load of the fetch right behind it, vmcnt counts
+// in issue order), and offsets[0] comes in as a value read once per kernel.  l1_landed() is the one wait for them and
+// l1_consume() is l1_prepare() fed from the registers; a k-mer loop always lies between the fetch and that wait.
 struct L1Next {
     uint4 q0, q1;  // 16 bases at window word t, and at word 256 + t (the k + 32 bases behind the tile)
-    uint64_t off;  // offsets[r_first + t] - offsets[0]
+    uint64_t off;  // offsets[r_first + t], as loaded
     uint32_t m[(1u << MAX_DIGIT_BITS) / 256u]; // matrix[item][t + 256 q] (scatter only)
 };
 
@@ -269,9 +273,8 @@ __device__ __forceinline__ uint32_t l1_window_words(const L1Args &a, uint32_t it
 }
 
 template <bool ROW>
-__device__ __forceinline__ void l1_fetch(const L1Args &a, uint32_t item, uint32_t r_first, L1Next &nx)
+__device__ __forceinline__ void l1_fetch(const L1Args &a, uint64_t off0, uint32_t item, uint32_t r_first, L1Next &nx)
 {
-    const uint64_t off0 = a.offsets[0];
     const uint8_t *bases = a.bases + off0;
     const uint64_t g0 = (uint64_t)item * L1_TILE;
     uint32_t n_here;
@@ -284,7 +287,7 @@ __device__ __forceinline__ void l1_fetch(const L1Args &a, uint32_t item, uint32_
     if (256u + threadIdx.x < nwords && p1 + 16 <= a.total)
         __builtin_memcpy(&nx.q1, bases + p1, 16);
     const uint32_t r = r_first + threadIdx.x;
-    nx.off = a.offsets[r <= a.n_reads ? r : a.n_reads] - off0;
+    nx.off = a.offsets[r <= a.n_reads ? r : a.n_reads];
     if (ROW) {
         const uint32_t B = 1u << a.bits;
 #pragma unroll
@@ -295,11 +298,27 @@ __device__ __forceinline__ void l1_fetch(const L1Args &a, uint32_t item, uint32_
     }
 }
 
-__device__ __forceinline__ uint32_t l1_pack16(const L1Args &a, const uint4 &q, uint64_t p)
+// One wait for everything l1_fetch loaded, at one place for all lanes.  The compiler waits for a load where its value is
+// first used; l1_consume uses most of them under lane conditions (window words, digits < B), the waits would stand inside
+// those branches, and behind the join the loads count as possibly still in flight: the next l1_fetch then waits for
+// "them" before it overwrites the registers -- with vmcnt(0), which drains the stores the kernel has just issued.
+template <bool ROW>
+__device__ __forceinline__ void l1_landed(const L1Next &nx)
+{
+    asm volatile("" ::"v"(nx.q0.x), "v"(nx.q0.y), "v"(nx.q0.z), "v"(nx.q0.w), "v"(nx.q1.x), "v"(nx.q1.y), "v"(nx.q1.z), "v"(nx.q1.w),
+                 "v"(nx.off));
+    if (ROW) {
+#pragma unroll
+        for (uint32_t q = 0; q < (1u << MAX_DIGIT_BITS) / 256u; q++)
+            asm volatile("" ::"v"(nx.m[q]));
+    }
+}
+
+__device__ __forceinline__ uint32_t l1_pack16(const L1Args &a, uint64_t off0, const uint4 &q, uint64_t p)
 {
     uint32_t v[4] = {q.x, q.y, q.z, q.w};
     if (p + 16 > a.total) { // the batch ends inside these 16 bases (its last tile only): byte by byte, beyond the end reads as A
-        const uint8_t *bases = a.bases + a.offsets[0];
+        const uint8_t *bases = a.bases + off0;
         v[0] = v[1] = v[2] = v[3] = 0;
         for (uint32_t j = 0; j < 16; j++)
             if (p + j < a.total)
@@ -308,46 +327,55 @@ __device__ __forceinline__ uint32_t l1_pack16(const L1Args &a, const uint4 &q, u
     return (pack4(v[0]) << 24) | (pack4(v[1]) << 16) | (pack4(v[2]) << 8) | pack4(v[3]);
 }
 
-// nx = l1_fetch(item, sh_r0[0] + sh_r0[1] of the tile before); `first`: sh_r0[0] was searched for, sh_r0[1] == 0
-__device__ __forceinline__ void l1_consume(const L1Args &a, uint32_t item, const L1Next &nx, uint32_t *pk, uint32_t *bnd, uint32_t *sh_r0,
-                                           uint32_t &n_here, bool first)
+// nx = l1_fetch(item, r_first); r_first = the first read that starts after the tile's first position (searched for at the
+// head of a range, afterwards the r_first of the tile before + its sh_r0[1], the reads that start at or before ITS last
+// position).  Leaves pk[], bnd[] and sh_r0[1] of `item` behind; the CALLER ends it with a barrier.
+// The 256 offsets that came with the fetch nearly always reach past the window: offsets are sorted, so thread 255 can
+// tell, and publishes it in sh_r0[2] before the barrier that is here anyway.  Only a window with more than 256 read
+// starts goes back to memory (correct, and as slow as it was).
+__device__ __forceinline__ void l1_consume(const L1Args &a, uint64_t off0, uint32_t item, const L1Next &nx, uint32_t r_first, uint32_t *pk,
+                                           uint32_t *bnd, uint32_t *sh_r0, uint32_t &n_here)
 {
-    const uint64_t off0 = a.offsets[0];
     const uint64_t g0 = (uint64_t)item * L1_TILE;
     const uint32_t nwords = l1_window_words(a, item, n_here);
     if (threadIdx.x < nwords)
-        pk[threadIdx.x] = l1_pack16(a, nx.q0, g0 + 16ull * threadIdx.x);
+        pk[threadIdx.x] = l1_pack16(a, off0, nx.q0, g0 + 16ull * threadIdx.x);
     if (256u + threadIdx.x < nwords)
-        pk[256u + threadIdx.x] = l1_pack16(a, nx.q1, g0 + 16ull * (256u + threadIdx.x));
+        pk[256u + threadIdx.x] = l1_pack16(a, off0, nx.q1, g0 + 16ull * (256u + threadIdx.x));
     for (uint32_t w = threadIdx.x; w < BND_WORDS; w += 256)
         bnd[w] = 0;
-    if (threadIdx.x == 0 && !first) {
-        sh_r0[0] += sh_r0[1];
-        sh_r0[1] = 0;
-    }
-    __syncthreads();
     const uint64_t lim = g0 + n_here + (uint64_t)a.k; // boundaries at window-local positions <= n_here + k - 1 matter
-    uint32_t before_next = 0;
-    uint64_t o = nx.off;
-    for (uint32_t r = sh_r0[0] + threadIdx.x; r <= a.n_reads; r += 256) {
-        if (o >= lim)
-            break;
-        const uint32_t p = (uint32_t)(o - g0);
-        atomicOr(&bnd[p >> 5], 1u << (p & 31u));
-        before_next += o <= g0 + L1_TILE ? 1u : 0u;
-        if (r + 256u <= a.n_reads)
-            o = a.offsets[r + 256u] - off0;
-    }
-    if (before_next)
-        atomicAdd(&sh_r0[1], before_next);
+    const uint32_t r = r_first + threadIdx.x;
+    const uint64_t o = nx.off - off0; // offsets[n_reads] - off0 == total: the batch end is a boundary too
+    const bool mine = r <= a.n_reads && o < lim;
+    if (threadIdx.x == 0)
+        sh_r0[1] = 0;
+    if (threadIdx.x == 255)
+        sh_r0[2] = mine ? 1u : 0u; // the window reaches past the offsets that were fetched
     __syncthreads();
+    if (mine) {
+        uint32_t p = (uint32_t)(o - g0);
+        atomicOr(&bnd[p >> 5], 1u << (p & 31u));
+        uint32_t before_next = o <= g0 + L1_TILE ? 1u : 0u;
+        if (sh_r0[2])
+            for (uint32_t r2 = r + 256u; r2 <= a.n_reads; r2 += 256u) {
+                const uint64_t o2 = a.offsets[r2] - off0;
+                if (o2 >= lim)
+                    break;
+                p = (uint32_t)(o2 - g0);
+                atomicOr(&bnd[p >> 5], 1u << (p & 31u));
+                before_next += o2 <= g0 + L1_TILE ? 1u : 0u;
+            }
+        if (before_next)
+            atomicAdd(&sh_r0[1], before_next);
+    }
 }
 
-// upper_bound(offsets, first position of tile `item`) into sh_r0[0], 0 into sh_r0[1]; ends with a barrier
-__device__ __forceinline__ void l1_search(const L1Args &a, uint32_t item, uint32_t *sh_r0)
+// upper_bound(offsets, first position of tile `item`) into sh_r0[0]; ends with a barrier
+__device__ __forceinline__ void l1_search(const L1Args &a, uint64_t off0, uint32_t item, uint32_t *sh_r0)
 {
     if (threadIdx.x == 0) {
-        const uint64_t off0 = a.offsets[0], g0 = (uint64_t)item * L1_TILE;
+        const uint64_t g0 = (uint64_t)item * L1_TILE;
         uint32_t lo = 0, hi = a.n_reads + 1;
         while (lo < hi) {
             const uint32_t mid = lo + (hi - lo) / 2;
@@ -357,7 +385,6 @@ __device__ __forceinline__ void l1_search(const L1Args &a, uint32_t item, uint32
                 hi = mid;
         }
         sh_r0[0] = lo;
-        sh_r0[1] = 0;
     }
     __syncthreads();
 }
@@ -413,70 +440,99 @@ __device__ __forceinline__ void l1_for_each_hash(const uint32_t *__restrict__ pk
 #ifndef BRX_L1HIST_WAVES
 #define BRX_L1HIST_WAVES 1 // (1 = the compiler's choice: 76 registers, six waves; tools/ab_build.sh sweeps it)
 #endif
+constexpr uint32_t L1_OWN = ((1u << MAX_DIGIT_BITS) + 255u) / 256u; // digits per lane: t, t + 256
+
+// One block per range of tiles.  Per tile: the k-mer loop, a barrier, then -- with pk[] and bnd[] dead -- the NEXT tile is
+// consumed from the registers its loads went to before that loop, and only then this tile's row of counts is stored and
+// the loads of the tile after the next are issued: three barriers per tile, and nothing waits for memory except the wait
+// in l1_consume, a k-mer loop behind the loads it waits for.  Each lane also adds up its digits over the range:
+// rsum[range][B], from which the scan forms where every range starts (col_scan_* below).
 __global__ __launch_bounds__(256, BRX_L1HIST_WAVES) void l1_hist_kernel(L1Args a)
 {
     extern __shared__ uint32_t lds[]; // hist[B]
     __shared__ uint32_t pk[PACK_WORDS];
     __shared__ uint32_t bnd[BND_WORDS];
-    __shared__ uint32_t sh_r0[2];
+    __shared__ uint32_t sh_r0[3];
     const uint32_t B = 1u << a.bits;
     const int shift = a.nbits - a.bits;
     uint32_t lo, hi;
     l1_range(a.n_items, lo, hi);
-    if (lo >= hi)
-        return;
-    l1_search(a, lo, sh_r0);
-    L1Next nx;
-    l1_fetch<false>(a, lo, sh_r0[0], nx);
-    for (uint32_t item = lo; item < hi; item++) {
+    uint64_t rs[L1_OWN];
+#pragma unroll
+    for (uint32_t q = 0; q < L1_OWN; q++)
+        rs[q] = 0;
+    if (lo < hi) {
+        const uint64_t off0 = a.offsets[0];
+        l1_search(a, off0, lo, sh_r0);
+        uint32_t r_first = sh_r0[0];
+        L1Next nx;
+        l1_fetch<false>(a, off0, lo, r_first, nx);
         for (uint32_t b = threadIdx.x; b < B; b += 256)
             lds[b] = 0;
         uint32_t n_here;
-        l1_consume(a, item, nx, pk, bnd, sh_r0, n_here, item == lo);
-        if (item + 1 < hi)
-            l1_fetch<false>(a, item + 1, sh_r0[0] + sh_r0[1], nx);
-        l1_for_each_hash(pk, bnd, n_here, a.k, [&](uint64_t h) { atomicAdd(&lds[(uint32_t)(h >> shift)], 1u); });
+        l1_landed<false>(nx);
+        l1_consume(a, off0, lo, nx, r_first, pk, bnd, sh_r0, n_here);
         __syncthreads();
-        for (uint32_t b = threadIdx.x; b < B; b += 256)
-            a.matrix[(uint64_t)item * B + b] = lds[b];
-        __syncthreads();
+        r_first += sh_r0[1];
+        l1_fetch<false>(a, off0, lo + 1 < hi ? lo + 1 : lo, r_first, nx);
+        for (uint32_t item = lo; item < hi; item++) {
+            l1_for_each_hash(pk, bnd, n_here, a.k, [&](uint64_t h) { atomicAdd(&lds[(uint32_t)(h >> shift)], 1u); });
+            __syncthreads();
+            uint32_t row[L1_OWN];
+#pragma unroll
+            for (uint32_t q = 0; q < L1_OWN; q++) {
+                const uint32_t b = threadIdx.x + 256u * q;
+                row[q] = 0;
+                if (b < B) {
+                    row[q] = lds[b];
+                    lds[b] = 0;
+                }
+            }
+            l1_landed<false>(nx); // (in front of the branch: the last tile's fetch below overwrites nx, too)
+            if (item + 1 < hi) {
+                l1_consume(a, off0, item + 1, nx, r_first, pk, bnd, sh_r0, n_here);
+                __syncthreads();
+                r_first += sh_r0[1];
+            }
+#pragma unroll
+            for (uint32_t q = 0; q < L1_OWN; q++) {
+                const uint32_t b = threadIdx.x + 256u * q;
+                if (b < B)
+                    a.matrix[(uint64_t)item * B + b] = row[q];
+                rs[q] += row[q];
+            }
+            // (past the end of the range: the last tile once more, into registers nobody reads)
+            l1_fetch<false>(a, off0, item + 2 < hi ? item + 2 : hi - 1, r_first, nx);
+        }
+    }
+#pragma unroll
+    for (uint32_t q = 0; q < L1_OWN; q++) {
+        const uint32_t b = threadIdx.x + 256u * q;
+        if (b < B && store_ok((uint64_t)blockIdx.x * B + b, (uint64_t)a.n_ranges * B))
+            a.rsum[(uint64_t)blockIdx.x * B + b] = rs[q];
     }
 }
 
-// ---- positions from the [n_items][B] count matrix -------------------------------------------------------------------
-// pos[item][b] = (keys of all digits < b) + (keys of digit b in the tiles before `item`): a scan down the COLUMNS of a
-// tile-major matrix.  Tile-major because a tile then reads and writes its B counters as one coalesced row -- digit-major
-// ([B][n_items], one flat exclusive scan) made every tile touch B separate cache lines, twice in the histogram pass and
-// twice in the scatter: 0.25 random line accesses per key, which at the platform's ~55 G lines/s was most of level 1.
-// Three small passes over chunks of CH tiles: column sums per chunk, one block turning them into chunk bases (and the
-// digit offsets the next level needs), then the positions.
-__global__ __launch_bounds__(256) void col_scan_partial_kernel(const uint32_t *__restrict__ m, uint32_t n_items, uint32_t B, uint32_t CH,
-                                                               uint64_t *__restrict__ part)
-{
-    const uint32_t chunk = blockIdx.x;
-    const uint32_t lo = chunk * CH, hi = (lo + CH < n_items) ? lo + CH : n_items;
-    for (uint32_t b = threadIdx.x; b < B; b += 256) {
-        uint64_t sum = 0;
-        for (uint32_t it = lo; it < hi; it++)
-            sum += m[(uint64_t)it * B + b];
-        part[(uint64_t)chunk * B + b] = sum;
-    }
-}
-
-// block b: exclusive scan of column b of part[n_chunks][B] in place (n_chunks <= 2048: 8 per thread), its total -> coltot[b]
-__global__ __launch_bounds__(256) void col_scan_columns_kernel(uint64_t *__restrict__ part, uint32_t n_chunks, uint32_t B,
+// ---- where every range of tiles starts, from the [n_ranges][B] range sums ----------------------------------------------
+// The scatter needs, per block, where each digit's keys of its first tile go: (keys of all digits < b) + (keys of digit b
+// in the ranges before); from there it follows its own tiles' counts.  The per-tile counts stay tile-major
+// (matrix[n_items][B]: a tile reads and writes its B counters as one coalesced row -- digit-major made every tile touch
+// B separate cache lines, 0.25 random line accesses per key), but no position per (tile, digit) is formed any more: the
+// histogram blocks leave one row of sums per range, one block per digit scans its column in place, one wave scans the
+// column totals into the digit offsets, and the scatter adds the two.
+// block b: exclusive scan of column b of part[n_rows][B] in place, its total -> coltot[b]
+__global__ __launch_bounds__(256) void col_scan_columns_kernel(uint64_t *__restrict__ part, uint32_t n_rows, uint32_t B,
                                                                uint64_t *__restrict__ coltot)
 {
     __shared__ uint64_t wsum[4];
     const uint32_t b = blockIdx.x;
-    const uint32_t per = (n_chunks + 255u) / 256u; // <= 8
+    const uint32_t per = (n_rows + 255u) / 256u;
     const uint32_t c0 = threadIdx.x * per;
-    uint64_t v[8];
     uint64_t mine = 0;
-    for (uint32_t q = 0; q < per && q < 8u; q++) {
+    for (uint32_t q = 0; q < per; q++) {
         const uint32_t c = c0 + q;
-        v[q] = c < n_chunks ? part[(uint64_t)c * B + b] : 0;
-        mine += v[q];
+        if (c < n_rows)
+            mine += part[(uint64_t)c * B + b];
     }
     uint64_t incl = mine;
     for (int d = 1; d < 64; d <<= 1) {
@@ -491,11 +547,13 @@ __global__ __launch_bounds__(256) void col_scan_columns_kernel(uint64_t *__restr
     for (uint32_t w = 0; w < (threadIdx.x >> 6); w++)
         base += wsum[w];
     uint64_t run = base + incl - mine;
-    for (uint32_t q = 0; q < per && q < 8u; q++) {
+    for (uint32_t q = 0; q < per; q++) {
         const uint32_t c = c0 + q;
-        if (c < n_chunks)
+        if (c < n_rows) {
+            const uint64_t v = part[(uint64_t)c * B + b];
             part[(uint64_t)c * B + b] = run;
-        run += v[q];
+            run += v;
+        }
     }
     if (threadIdx.x == 255)
         coltot[b] = base + incl;
@@ -522,21 +580,6 @@ __global__ __launch_bounds__(64) void col_scan_digits_kernel(const uint64_t *__r
     if (threadIdx.x == 0) {
         coff[B] = carry;
         *total = carry;
-    }
-}
-
-__global__ __launch_bounds__(256) void col_scan_positions_kernel(const uint32_t *__restrict__ m, uint32_t n_items, uint32_t B, uint32_t CH,
-                                                                 const uint64_t *__restrict__ part, const uint64_t *__restrict__ coff,
-                                                                 uint64_t *__restrict__ pos)
-{
-    const uint32_t chunk = blockIdx.x;
-    const uint32_t lo = chunk * CH, hi = (lo + CH < n_items) ? lo + CH : n_items;
-    for (uint32_t b = threadIdx.x; b < B; b += 256) {
-        uint64_t run = part[(uint64_t)chunk * B + b] + coff[b];
-        for (uint32_t it = lo; it < hi; it++) {
-            pos[(uint64_t)it * B + b] = run;
-            run += m[(uint64_t)it * B + b];
-        }
     }
 }
 
@@ -578,17 +621,18 @@ __global__ __launch_bounds__(256) void flat_insert_kernel(L1Args a, uint32_t *__
     }
 }
 
-// shared tail of the scatter kernels: block scan of cntv -> lofs/lcur, returns nothing (all in LDS)
-__device__ __forceinline__ void block_scan_bins(uint32_t B, const uint32_t *cntv, uint32_t *lofs, uint32_t *lcur, uint32_t *sh_wsum)
+// shared by the scatter kernels: block scan of cntv -> lofs/lcur (all in LDS), in two halves around one barrier so that
+// a caller with a barrier of its own there can share it
+__device__ __forceinline__ void scan_bins_begin(uint32_t B, const uint32_t *cntv, uint32_t *sh_wsum, uint32_t &mine, uint32_t &incl)
 {
     const uint32_t BPT = (B + 255u) / 256u; // bins per thread (1 or 2)
-    uint32_t mine = 0;
+    mine = 0;
     for (uint32_t q = 0; q < BPT; q++) {
         const uint32_t b = threadIdx.x * BPT + q;
         if (b < B)
             mine += cntv[b];
     }
-    uint32_t incl = mine;
+    incl = mine;
     for (int d = 1; d < 64; d <<= 1) {
         const uint32_t t = __shfl_up(incl, d);
         if ((threadIdx.x & 63) >= (unsigned)d)
@@ -596,7 +640,12 @@ __device__ __forceinline__ void block_scan_bins(uint32_t B, const uint32_t *cntv
     }
     if ((threadIdx.x & 63) == 63)
         sh_wsum[threadIdx.x >> 6] = incl;
-    __syncthreads();
+}
+
+__device__ __forceinline__ void scan_bins_end(uint32_t B, const uint32_t *cntv, uint32_t *lofs, uint32_t *lcur, const uint32_t *sh_wsum,
+                                              uint32_t mine, uint32_t incl)
+{
+    const uint32_t BPT = (B + 255u) / 256u;
     uint32_t wbase = 0;
     for (uint32_t w = 0; w < (threadIdx.x >> 6); w++)
         wbase += sh_wsum[w];
@@ -611,6 +660,14 @@ __device__ __forceinline__ void block_scan_bins(uint32_t B, const uint32_t *cntv
     }
 }
 
+__device__ __forceinline__ void block_scan_bins(uint32_t B, const uint32_t *cntv, uint32_t *lofs, uint32_t *lcur, uint32_t *sh_wsum)
+{
+    uint32_t mine, incl;
+    scan_bins_begin(B, cntv, sh_wsum, mine, incl);
+    __syncthreads();
+    scan_bins_end(B, cntv, lofs, lcur, sh_wsum, mine, incl);
+}
+
 // Level-1 write-out in whole 32-byte sectors.  A tile leaves T / B = 8 keys per digit on average: written where they
 // belong, that is a 32-byte run at a 4-byte-aligned place, 1.87 sectors touched per run (WRITE_SIZE counted exactly that,
 // profiles/r2j_*), every one of them a partial write.  But the runs of one digit from CONSECUTIVE tiles lie end to end
@@ -619,8 +676,12 @@ __device__ __forceinline__ void block_scan_bins(uint32_t B, const uint32_t *cntv
 // only the two ends of a block's range are partial.  The first sector of a range starts with the `ph` places that belong
 // to the range before (phantoms: kept as holes in the carry, never stored).
 constexpr uint32_t L1_SECTOR = 8;                              // keys per 32-byte sector
-constexpr uint32_t L1_OWN = ((1u << MAX_DIGIT_BITS) + 255u) / 256u; // digits per lane: t, t + 256
 
+// A tile: its counts, bases and read offsets are consumed from the registers l1_fetch filled a tile ago, the loads of the
+// next tile are issued, and the k-mer loop and the write-out run while those are under way.  Six barriers per tile.
+// Consuming tile i + 1 between the k-mer loop and the write-out of tile i, so that the wait for the loads would not also
+// count the stores just issued (vmcnt is in issue order), takes two barriers fewer and was measured SLOWER
+// (profiles/r7_partition_waits.txt): the order here is the one that measured best.
 #ifndef BRX_L1SCAT_WAVES
 #define BRX_L1SCAT_WAVES 5
 #endif
@@ -630,7 +691,7 @@ __global__ __launch_bounds__(256, BRX_L1SCAT_WAVES) void l1_scatter_kernel(L1Arg
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     __shared__ uint32_t pk[PACK_WORDS];
     __shared__ uint32_t bnd[BND_WORDS];
-    __shared__ uint32_t sh_r0[2];
+    __shared__ uint32_t sh_r0[3];
     __shared__ uint32_t sh_wsum[4];
     const uint32_t T = L1_TILE;
     const uint32_t B = 1u << a.bits;
@@ -646,7 +707,8 @@ __global__ __launch_bounds__(256, BRX_L1SCAT_WAVES) void l1_scatter_kernel(L1Arg
     if (lo >= hi)
         return;
     for (uint32_t b = threadIdx.x; b < B; b += 256) {
-        const unsigned long long p0 = a.pos[(uint64_t)lo * B + b];
+        // where digit b of this range starts: behind all smaller digits and behind digit b of the ranges before
+        const unsigned long long p0 = a.coff[b] + a.rsum[(uint64_t)blockIdx.x * B + b];
         const unsigned long long ph = p0 & (L1_SECTOR - 1);
         gsm[b] = (p0 / L1_SECTOR) | (ph << 32) | (ph << 36);
     }
@@ -656,19 +718,26 @@ __global__ __launch_bounds__(256, BRX_L1SCAT_WAVES) void l1_scatter_kernel(L1Arg
 #pragma unroll
         for (uint32_t jj = 0; jj < L1_SECTOR; jj++)
             creg[q][jj] = 0;
-    l1_search(a, lo, sh_r0);
+    const uint64_t off0 = a.offsets[0];
+    l1_search(a, off0, lo, sh_r0);
+    uint32_t r_first = sh_r0[0];
     L1Next nx;
-    l1_fetch<true>(a, lo, sh_r0[0], nx);
+    l1_fetch<true>(a, off0, lo, r_first, nx);
     for (uint32_t item = lo; item < hi; item++) {
+        l1_landed<true>(nx);
 #pragma unroll
         for (uint32_t q = 0; q < L1_OWN; q++)
             if (threadIdx.x + 256u * q < B)
                 cntv[threadIdx.x + 256u * q] = nx.m[q]; // the histogram pass already counted this tile
         uint32_t n_here;
-        l1_consume(a, item, nx, pk, bnd, sh_r0, n_here, item == lo);
-        if (item + 1 < hi)
-            l1_fetch<true>(a, item + 1, sh_r0[0] + sh_r0[1], nx);
-        block_scan_bins(B, cntv, lofs, lcur, sh_wsum);
+        l1_consume(a, off0, item, nx, r_first, pk, bnd, sh_r0, n_here);
+        uint32_t mine, incl;
+        scan_bins_begin(B, cntv, sh_wsum, mine, incl); // (shares the barrier that ends l1_consume)
+        __syncthreads();
+        r_first += sh_r0[1];
+        scan_bins_end(B, cntv, lofs, lcur, sh_wsum, mine, incl);
+        // (past the end of the range: the last tile once more, into registers nobody reads)
+        l1_fetch<true>(a, off0, item + 1 < hi ? item + 1 : item, r_first, nx);
         __syncthreads();
         l1_for_each_hash<BRX_L1_UNROLL>(pk, bnd, n_here, a.k, [&](uint64_t h) {
             const uint32_t d = (uint32_t)(h >> shift);
@@ -749,49 +818,79 @@ __global__ void tiles_from_offsets_kernel(const uint64_t *__restrict__ poff, uin
     ntiles[p] = (uint32_t)((n + tile - 1) / tile);
 }
 
-// item -> parent map (instead of a binary search per work item)
-__global__ void fill_item_parent_kernel(const uint64_t *__restrict__ item_off, uint64_t n_parents,
-                                        uint32_t *__restrict__ item_parent)
+// One record per work item (tile): where its keys start and how many they are.  A tile used to open with three dependent
+// loads (item -> parent -> first item of the parent -> the parent's key range); now it is one load, and the kernels issue it
+// a tile ahead.  The row of the item in matrix / pos is the item's own index: items are numbered parent by parent.
+struct LnItem {
+    uint64_t lo; // first key
+    uint32_t n;  // keys of the tile (1 .. tile)
+    uint32_t pad;
+};
+
+__global__ void fill_items_kernel(const uint64_t *__restrict__ poff, const uint64_t *__restrict__ item_off, uint64_t n_parents,
+                                  uint32_t tile, LnItem *__restrict__ items)
 {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n_parents)
         return;
-    const uint64_t lo = item_off[p], hi = item_off[p + 1];
-    for (uint64_t i = lo; i < hi; i++)
-        item_parent[i] = (uint32_t)p;
+    const uint64_t i0 = item_off[p], i1 = item_off[p + 1];
+    const uint64_t k1 = poff[p + 1];
+    uint64_t k = poff[p];
+    for (uint64_t i = i0; i < i1; i++, k += tile) {
+        LnItem it;
+        it.lo = k;
+        it.n = (uint32_t)(k1 - k < tile ? k1 - k : tile);
+        it.pad = 0;
+        items[i] = it;
+    }
 }
 
 struct LnArgs {
     const uint32_t *keys_in;
-    const uint64_t *poff;        // parent bucket offsets into keys_in
-    uint64_t n_parents;
-    const uint64_t *item_off;    // n_parents + 1: first work item of each parent
-    const uint32_t *item_parent; // per work item
+    const LnItem *items;         // per work item
     const unsigned long long *n_items; // device scalar
     uint32_t tile;
     int rem_in, bits;            // digit = key >> (rem_in - bits)
-    uint32_t *matrix;            // [parent][B][tiles of the parent] digit counts, index B*item_off[p] + b*ntiles_p + t
-    const uint64_t *pos;         // exclusive scan of matrix
+    uint32_t *matrix;            // [item][B] digit counts: tile-major inside a parent, one coalesced row per tile
+    const uint64_t *pos;         // where the tile's keys of each digit go (ln_colscan_kernel)
     void *keys_out;
     uint64_t in_cap, out_cap;    // entries of keys_in / keys_out (checked under BRX_DEBUG_BOUNDS)
 };
 
-template <int KPT>
-__device__ __forceinline__ uint32_t ln_load(const LnArgs &a, uint64_t parent, uint64_t t, uint32_t (&key)[KPT])
+// the item's record: one 16-byte load (ln_item_load only issues it), then into scalar registers -- the same for every
+// lane, and the key addresses are then a scalar base + the lane's offset instead of a 64-bit vector address per load
+__device__ __forceinline__ uint4 ln_item_load(const LnArgs &a, unsigned long long item)
 {
-    const uint64_t lo = a.poff[parent] + t * a.tile;
-    const uint64_t hi_p = a.poff[parent + 1];
-    const uint64_t hi = (lo + a.tile < hi_p) ? lo + a.tile : hi_p;
-    uint32_t cnt = 0;
+    return *reinterpret_cast<const uint4 *>(a.items + item);
+}
+
+__device__ __forceinline__ LnItem ln_item_get(const uint4 &v)
+{
+    LnItem it;
+    it.lo = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)v.y) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)v.x);
+    it.n = (uint32_t)__builtin_amdgcn_readfirstlane((int)v.z);
+    it.pad = 0;
+    return it;
+}
+
+// issues the loads of a tile's keys (thread t: keys t, t + 256, ...) and nothing else; how many of them are this thread's
+// follows from the record alone (ln_count).  No branch per load: behind the end of a partial tile a lane reads the tile's
+// first key again (a tile holds at least one) and nobody looks at it.
+template <int KPT>
+__device__ __forceinline__ void ln_load(const LnArgs &a, const LnItem &it, uint32_t (&key)[KPT])
+{
 #pragma unroll
     for (int q = 0; q < KPT; q++) {
-        const uint64_t i = lo + (uint64_t)q * 256 + threadIdx.x;
-        if (i < hi && store_ok(i, a.in_cap)) {
+        const uint32_t j = (uint32_t)q * 256u + threadIdx.x;
+        const uint64_t i = it.lo + (j < it.n ? j : 0u);
+        if (store_ok(i, a.in_cap))
             key[q] = a.keys_in[i];
-            cnt = q + 1;
-        }
     }
-    return cnt;
+}
+
+__device__ __forceinline__ uint32_t ln_count(const LnItem &it)
+{
+    return it.n > threadIdx.x ? (it.n - threadIdx.x + 255u) / 256u : 0u;
 }
 
 template <int KPT>
@@ -805,22 +904,26 @@ __global__ __launch_bounds__(256, BRX_LNHIST_WAVES) void ln_hist_kernel(LnArgs a
     const int shift = a.rem_in - a.bits;
     const unsigned long long n_items = *a.n_items;
     const ItemRange ir = xcd_items(n_items);
+    if (ir.first >= ir.end)
+        return;
+    uint4 it_raw = ln_item_load(a, ir.first);
     for (unsigned long long item = ir.first; item < ir.end; item += ir.step) {
-        const uint64_t parent = a.item_parent[item];
-        const uint64_t io = a.item_off[parent];
-        const uint64_t t = item - io;
+        const LnItem it = ln_item_get(it_raw);
+        uint32_t key[KPT];
+        ln_load<KPT>(a, it, key);
+        const uint32_t cnt = ln_count(it);
+        const unsigned long long next = item + ir.step;
+        it_raw = ln_item_load(a, next < ir.end ? next : item); // the record of the next tile, while this one is counted
         for (uint32_t b = threadIdx.x; b < B; b += 256)
             lds[b] = 0;
         __syncthreads();
-        uint32_t key[KPT];
-        const uint32_t cnt = ln_load<KPT>(a, parent, t, key);
 #pragma unroll
         for (int q = 0; q < KPT; q++)
             if ((uint32_t)q < cnt)
                 atomicAdd(&lds[(key[q] >> shift) & (B - 1u)], 1u);
         __syncthreads();
         for (uint32_t b = threadIdx.x; b < B; b += 256)
-            a.matrix[B * (io + t) + b] = lds[b]; // tile-major inside the parent: one coalesced row per tile
+            a.matrix[B * item + b] = lds[b]; // one coalesced row per tile
         __syncthreads();
     }
 }
@@ -878,6 +981,9 @@ __global__ __launch_bounds__(256) void ln_colscan_kernel(const uint32_t *__restr
     }
 }
 
+// The loads of a tile -- its record, then its count row, its position row and its keys -- are issued at the end of the
+// tile before, behind that tile's stores.  Loading keys and rows a whole tile ahead into a second set of registers, with
+// the wait for them in front of the write-out, was measured slower (profiles/r7_partition_waits.txt).
 template <int KPT, typename OUT>
 __global__ __launch_bounds__(256) void ln_scatter_kernel(LnArgs a)
 {
@@ -896,17 +1002,33 @@ __global__ __launch_bounds__(256) void ln_scatter_kernel(LnArgs a)
     OUT *out = (OUT *)a.keys_out;
     const unsigned long long n_items = *a.n_items;
     const ItemRange ir = xcd_items(n_items);
-    for (unsigned long long item = ir.first; item < ir.end; item += ir.step) {
-        const uint64_t parent = a.item_parent[item];
-        const uint64_t io = a.item_off[parent];
-        const uint64_t t = item - io;
-        for (uint32_t b = threadIdx.x; b < B; b += 256) {
-            const uint64_t mi = B * (io + t) + b;
-            cntv[b] = a.matrix[mi];
-            gbase[b] = a.pos[mi];
+    if (ir.first >= ir.end)
+        return;
+    constexpr uint32_t OWN = ((1u << MAX_DIGIT_BITS) + 255u) / 256u; // digits per lane: t, t + 256
+    auto load_rows = [&](unsigned long long item, uint32_t(&rc)[OWN], uint64_t(&rp)[OWN]) {
+#pragma unroll
+        for (uint32_t q = 0; q < OWN; q++) {
+            const uint32_t b = threadIdx.x + 256u * q;
+            const uint64_t mi = B * item + (b < B ? b : 0u); // (no branch: digits past B read digit 0 and drop it)
+            rc[q] = a.matrix[mi];
+            rp[q] = a.pos[mi];
         }
-        uint32_t key[KPT];
-        const uint32_t cnt = ln_load<KPT>(a, parent, t, key);
+    };
+    LnItem it = ln_item_get(ln_item_load(a, ir.first));
+    uint32_t key[KPT], rc[OWN];
+    uint64_t rp[OWN];
+    load_rows(ir.first, rc, rp);
+    ln_load<KPT>(a, it, key);
+    for (unsigned long long item = ir.first; item < ir.end; item += ir.step) {
+#pragma unroll
+        for (uint32_t q = 0; q < OWN; q++) {
+            const uint32_t b = threadIdx.x + 256u * q;
+            if (b < B) {
+                cntv[b] = rc[q];
+                gbase[b] = rp[q];
+            }
+        }
+        const uint32_t cnt = ln_count(it);
         __syncthreads();
         block_scan_bins(B, cntv, lofs, lcur, sh_wsum);
         __syncthreads();
@@ -925,6 +1047,12 @@ __global__ __launch_bounds__(256) void ln_scatter_kernel(LnArgs a)
             const uint64_t at = gbase[d] + (idx - lofs[d]);
             if (store_ok(at, a.out_cap))
                 out[at] = (OUT)stage_key[idx];
+        }
+        const unsigned long long next = item + ir.step;
+        if (next < ir.end) {
+            it = ln_item_get(ln_item_load(a, next));
+            load_rows(next, rc, rp);
+            ln_load<KPT>(a, it, key);
         }
         __syncthreads();
     }
@@ -1492,14 +1620,12 @@ struct PartState {
     uint64_t ntiles_cap = 0;
     uint64_t *d_item_off = nullptr;    // per parent + 1
     uint64_t item_off_cap = 0;
-    uint32_t *d_item_parent = nullptr; // per work item
-    uint64_t item_parent_cap = 0;
+    LnItem *d_items = nullptr;         // per work item
+    uint64_t items_cap = 0;
     uint32_t *d_matrix = nullptr;      // per-tile digit counts
     uint64_t matrix_cap = 0;
-    uint64_t *d_pos = nullptr;         // exclusive scan of the matrix
+    uint64_t *d_pos = nullptr;         // levels >= 2: exclusive scan of the matrix; level 1: [n_ranges + 1][B] range starts
     uint64_t pos_cap = 0;
-    uint64_t *d_colpart = nullptr;     // level 1: per-chunk column sums / bases of the tile-major matrix
-    uint64_t colpart_cap = 0;
     uint64_t *d_scan_tmp = nullptr;
     uint64_t scan_tmp_cap = 0;
     unsigned long long *d_scalars = nullptr; // [0] n_items, [1] total keys of the last scan, [2..3] hf_sample_kernel
@@ -1638,8 +1764,8 @@ void part_free(brx_counter *c)
             if (b.d_l1off)
                 (void)hipFree(b.d_l1off);
         }
-    for (void *p : {(void *)st->d_ntiles, (void *)st->d_item_off, (void *)st->d_item_parent, (void *)st->d_matrix,
-                    (void *)st->d_pos, (void *)st->d_colpart, (void *)st->d_scan_tmp, (void *)st->d_scalars, (void *)st->d_coff[0],
+    for (void *p : {(void *)st->d_ntiles, (void *)st->d_item_off, (void *)st->d_items, (void *)st->d_matrix,
+                    (void *)st->d_pos, (void *)st->d_scan_tmp, (void *)st->d_scalars, (void *)st->d_coff[0],
                     (void *)st->d_coff[1], (void *)st->d_coff[2], (void *)st->d_coff[3], (void *)st->d_keys_mid,
                     (void *)st->d_keys_mid2, (void *)st->d_keys_fin,
                     (void *)st->d_merged, (void *)st->d_l1off_all, (void *)st->d_cnts, (void *)st->d_shift})
@@ -1697,14 +1823,15 @@ int part_add_partitioned(brx_counter *c, const uint32_t *d_keys, const uint64_t 
     return BRX_OK;
 }
 
-// matrix / pos / scan scratch for `n_entries` per-tile counters
-static int ensure_matrix(PartState *st, uint64_t n_entries)
+// matrix / scan scratch for `n_entries` per-tile counters, pos for `n_pos` positions (levels >= 2: one per counter;
+// level 1: one per range and digit)
+static int ensure_matrix(PartState *st, uint64_t n_entries, uint64_t n_pos)
 {
     uint64_t capb = st->matrix_cap;
     BRX_TRY(ensure_dev((void **)&st->d_matrix, &capb, (n_entries + 1) * 4));
     st->matrix_cap = capb;
     capb = st->pos_cap;
-    BRX_TRY(ensure_dev((void **)&st->d_pos, &capb, (n_entries + 2) * 8));
+    BRX_TRY(ensure_dev((void **)&st->d_pos, &capb, (n_pos + 2) * 8));
     st->pos_cap = capb;
     capb = st->scan_tmp_cap;
     BRX_TRY(ensure_dev((void **)&st->d_scan_tmp, &capb, scan_tmp_bytes((uint32_t)n_entries) + 64));
@@ -1753,7 +1880,17 @@ int part_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_off
     }
     const uint32_t n_items = (uint32_t)n_items64;
     const uint64_t n_entries = (uint64_t)B * n_items;
-    BRX_TRY(ensure_matrix(st, n_entries));
+    // One partition of the tiles into contiguous ranges, a block per range in both kernels: the histogram leaves the
+    // range sums the scan turns into range starts, the scatter carries sector remainders from tile to tile of its range.
+    // Twice the blocks the chip holds of the scatter at once (5 per CU at 27 KB of LDS): the ranges stay long (~100 tiles
+    // at 1 Gbp) and the last round of blocks short.  (BRX_L1_GRID: tests shrink the number of ranges so that small inputs
+    // give every block several tiles)
+    const char *genv = getenv("BRX_L1_GRID");
+    const long gev = genv ? atol(genv) : 0;
+    const uint32_t want_ranges = gev > 0 ? (uint32_t)gev : 2560u;
+    const uint32_t n_ranges = n_items < want_ranges ? n_items : want_ranges;
+    BRX_TRY(ensure_matrix(st, n_entries, ((uint64_t)n_ranges + 1) * B));
+    uint64_t *coltot = st->d_pos + (uint64_t)n_ranges * B;
     L1Args a;
     memset(&a, 0, sizeof(a));
     a.bases = d_bases;
@@ -1765,45 +1902,28 @@ int part_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_off
     a.nbits = pl.nbits;
     a.bits = pl.bits[0];
     a.matrix = st->d_matrix;
-    a.pos = st->d_pos;
+    a.n_ranges = n_ranges;
+    a.rsum = st->d_pos;
+    a.coff = b.d_l1off;
     a.keys_out = b.d_keys;
     a.out_cap = b.cap;
-    // both level-1 kernels give a block a contiguous range of tiles (BRX_L1_GRID: tests shrink the grid so that small
-    // inputs give every block several tiles)
-    const char *genv = getenv("BRX_L1_GRID");
-    const long gev = genv ? atol(genv) : 0;
-    const uint32_t hist_blocks = gev > 0 ? (uint32_t)gev : 2048u, scatter_blocks = gev > 0 ? (uint32_t)gev : 2560u;
-    const int grid = (int)(n_items < hist_blocks ? n_items : hist_blocks);
     {
         KernelTimer t("part_l1_hist", s);
-        l1_hist_kernel<<<grid, 256, (size_t)B * 4, s>>>(a);
+        l1_hist_kernel<<<n_ranges, 256, (size_t)B * 4, s>>>(a);
     }
     trace_stage(s, "partition level 1: histograms");
     {
-        // positions of every (tile, digit) run and the digit offsets, from the tile-major counts (col_scan_* above)
+        // where every range starts in every digit, and the digit offsets, from the range sums (col_scan_* above)
         KernelTimer t("offsets_scan", s);
-        uint32_t CH = 64;
-        while ((n_items + CH - 1) / CH > 2048u)
-            CH *= 2;
-        const uint32_t n_chunks = (n_items + CH - 1) / CH;
-        uint64_t capb = st->colpart_cap;
-        BRX_TRY(ensure_dev((void **)&st->d_colpart, &capb, ((uint64_t)n_chunks + 1) * B * 8));
-        st->colpart_cap = capb;
-        uint64_t *coltot = st->d_colpart + (uint64_t)n_chunks * B;
-        col_scan_partial_kernel<<<n_chunks, 256, 0, s>>>(st->d_matrix, n_items, B, CH, st->d_colpart);
-        col_scan_columns_kernel<<<B, 256, 0, s>>>(st->d_colpart, n_chunks, B, coltot);
+        col_scan_columns_kernel<<<B, 256, 0, s>>>(st->d_pos, n_ranges, B, coltot);
         col_scan_digits_kernel<<<1, 64, 0, s>>>(coltot, B, b.d_l1off, st->d_scalars + 1);
-        col_scan_positions_kernel<<<n_chunks, 256, 0, s>>>(st->d_matrix, n_items, B, CH, st->d_colpart, b.d_l1off, st->d_pos);
     }
     {
         KernelTimer t("part_l1_scatter", s);
         const size_t lds1 = l1_scatter_lds_bytes(a.bits);
         if (lds1 > 64 * 1024)
             BRX_HIP(hipFuncSetAttribute((const void *)l1_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        // contiguous tile ranges, one per block (the kernel's carries): twice the blocks the chip holds at once
-        // (5 per CU at 27 KB of LDS): the ranges stay long (~100 tiles at 1 Gbp) and the last round of blocks short
-        const uint32_t sgrid = n_items < scatter_blocks ? n_items : scatter_blocks;
-        l1_scatter_kernel<<<sgrid, 256, lds1, s>>>(a);
+        l1_scatter_kernel<<<n_ranges, 256, lds1, s>>>(a);
     }
     trace_stage(s, "partition level 1: scatter");
     BRX_HIP(hipGetLastError());
@@ -1841,24 +1961,21 @@ static int run_level(PartState *st, int l, const uint32_t *keys_in, const uint64
         capb = st->item_off_cap;
         BRX_TRY(ensure_dev((void **)&st->d_item_off, &capb, (n_parents + 2) * 8));
         st->item_off_cap = capb;
-        capb = st->item_parent_cap;
-        BRX_TRY(ensure_dev((void **)&st->d_item_parent, &capb, (ub_items + 1) * 4));
-        st->item_parent_cap = capb;
+        capb = st->items_cap;
+        BRX_TRY(ensure_dev((void **)&st->d_items, &capb, (ub_items + 1) * sizeof(LnItem)));
+        st->items_cap = capb;
     }
-    BRX_TRY(ensure_matrix(st, n_entries > n_parents ? n_entries : n_parents));
+    BRX_TRY(ensure_matrix(st, n_entries > n_parents ? n_entries : n_parents, n_entries > n_parents ? n_entries : n_parents));
     tiles_from_offsets_kernel<<<(unsigned)((n_parents + 255) / 256), 256, 0, s>>>(poff, n_parents, tile, st->d_ntiles);
     BRX_TRY(exclusive_scan_lens(st->d_ntiles, (uint32_t)n_parents, st->d_scan_tmp, st->d_item_off, st->d_scalars, s));
-    fill_item_parent_kernel<<<(unsigned)((n_parents + 255) / 256), 256, 0, s>>>(st->d_item_off, n_parents, st->d_item_parent);
+    fill_items_kernel<<<(unsigned)((n_parents + 255) / 256), 256, 0, s>>>(poff, st->d_item_off, n_parents, tile, st->d_items);
     trace_stage(s, tag_hist);
     BRX_HIP(hipMemsetAsync(st->d_matrix, 0, n_entries * 4, s));
     LnArgs a;
     memset(&a, 0, sizeof(a));
     a.keys_in = keys_in;
     a.in_cap = total;
-    a.poff = poff;
-    a.n_parents = n_parents;
-    a.item_off = st->d_item_off;
-    a.item_parent = st->d_item_parent;
+    a.items = st->d_items;
     a.n_items = st->d_scalars;
     a.tile = tile;
     a.rem_in = pl.rem_in[l];
@@ -1940,7 +2057,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
         uint64_t capb = st->merged_cap;
         BRX_TRY(ensure_dev((void **)&st->d_merged, &capb, (total + 1) * 4));
         st->merged_cap = capb;
-        BRX_TRY(ensure_matrix(st, B1 + 1));
+        BRX_TRY(ensure_matrix(st, B1 + 1, B1 + 1));
         BRX_HIP(hipMemsetAsync(st->d_cnts, 0, (uint64_t)B1 * 4, s));
         for (auto &b : st->batches)
             add_counts_kernel<<<(B1 + 255) / 256, 256, 0, s>>>(b.d_l1off, B1, st->d_cnts, nullptr);
