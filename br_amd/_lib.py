@@ -18,7 +18,7 @@ BRX_ERR_NODEVICE = -4
 BRX_ERR_UNSUPPORTED = -6
 
 METHOD_IDS = {"one": 0, "two": 1, "graph": 2, "greedy": 3, "gap_size": 4, "gap-size": 4}
-COUNT_AUTO, COUNT_DENSE, COUNT_SORTED = 0, 1, 2
+COUNT_AUTO, COUNT_DENSE, COUNT_SORTED, COUNT_TABLE = 0, 1, 2, 3
 
 
 class BrxError(RuntimeError):
@@ -96,6 +96,7 @@ SIGNATURES = {
     "brx_counter_clamp": (C.c_int, [_vp, C.c_uint8, _vp]),
     "brx_counter_l1_view": (C.c_int, [_vp, _pp, _pp, C.POINTER(C.c_uint32), _u64p]),
     "brx_counter_add_partitioned_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
+    "brx_counter_table_info": (C.c_int, [_vp, _u64p, _vp]),
     "brx_counter_free": (None, [_vp]),
     "brx_comm_unique_id": (C.c_int, [_vp]),
     "brx_comm_init": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _pp]),

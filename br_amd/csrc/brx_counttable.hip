@@ -1,0 +1,334 @@
+// Counting table (BRX_COUNT_TABLE): k-mer counts with an abundance threshold for every odd k up to 31.
+//
+// The dense counter is a 2^(2k-1)-byte table (k <= 19) and the partitioned counter carries 32-bit keys (k <= 21); this
+// one counts into the chained 64-byte-line table that sparse sets are made of (brx_index.hpp: 7 keys per line, addressed
+// by the k-mer's minimizer, chained into the next line), with one u32 counter per slot in an array of its own beside the
+// lines -- counts[line * 8 + slot] -- so that the line format and every probe stay what they are.
+//
+//   count    flat_count_kernel (brx_partbuild.hip, beside flat_insert_kernel<true>): find or claim the k-mer's slot with
+//            one 64-bit CAS, then one atomic add on the slot's counter unless it has reached 255 (table_count_bump).
+//   regrow   the table is kept at most about half full (keys so far + bases of the next batch against 7 slots per line,
+//            as index_insert_reads does): a larger one is allocated and table_rehash_counts_kernel moves every key with
+//            min(255, its count).
+//   finish   table_select_kernel: one pass over the slots, keys with min(255, count) > abundance compacted in the wave
+//            (one global atomic per wave) into the destination's key list -- the closed set the partitioned finish
+//            leaves at k = 21: the probe index is built from the list on first use.  A set with a bit vector (k <= 19)
+//            gets its bits written in the same pass.
+//   spectrum table_spectrum_kernel: bins 1..255 from the counters.
+//
+// The exact number of distinct keys lives on the device (d_nkeys) and is read back -- one synchronisation of the stream
+// -- only when the bound "keys known + bases counted since" no longer fits under the load limit, and by finish.
+#include "brx_internal.hpp"
+#include "brx_index.hpp"
+
+using namespace brx;
+
+namespace brx {
+
+struct TabState {
+    uint64_t *d_lines = nullptr;   // 8 u64 per line
+    uint32_t *d_counts = nullptr;  // 8 u32 per line (entry 7 unused)
+    uint32_t log_lines = 0, m = 0;
+    unsigned long long *d_nkeys = nullptr; // distinct keys in the table
+    uint64_t keys_known = 0;       // d_nkeys when it was last read back
+    uint64_t pending = 0;          // bases counted since: at most that many more keys
+    uint64_t bases_total = 0;      // bases counted in all: at most that many occurrences
+    uint64_t peak_bytes = 0;       // lines + counters held at once (both tables during a regrow)
+};
+
+} // namespace brx
+
+namespace {
+
+constexpr int TAB_MIN_LOG_LINES = 12, TAB_MAX_LOG_LINES = 30;
+
+// moves every key of one counting table into another, with its count
+__global__ __launch_bounds__(256) void table_rehash_counts_kernel(const uint64_t *__restrict__ old_lines, const uint32_t *__restrict__ old_counts,
+                                                                  uint64_t n_old_slots, int k, uint64_t *__restrict__ lines,
+                                                                  uint32_t *__restrict__ counts, uint32_t line_shift, uint32_t m, uint32_t w)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_old_slots; i += stride) {
+        const uint64_t v = (i & 7ull) == 7ull ? 0ull : old_lines[i]; // (entry 7 is the line's header)
+        if (v) {
+            const uint64_t h = v - 1ull;
+            bool fresh;
+            const uint64_t slot = table_find_or_claim(lines, line_shift, m, w, k, (h << 1) | (uint64_t)(popc64(h) & 1), fresh);
+            table_count_bump(counts + slot, table_count_read(old_counts[i])); // (a key sits in the old table once)
+        }
+    }
+}
+
+// keys with min(255, count) > abundance: listed (LIST), their bits set (bits != nullptr).  A wave takes 64 consecutive
+// slots per trip (n_slots is a multiple of 64), counts its keepers with a ballot and asks for their places with one atomic.
+template <bool LIST>
+__global__ __launch_bounds__(256) void table_select_kernel(const uint64_t *__restrict__ lines, const uint32_t *__restrict__ counts,
+                                                           uint64_t n_slots, uint32_t abundance, uint64_t *__restrict__ out, uint64_t cap,
+                                                           unsigned long long *__restrict__ n_out, uint32_t *__restrict__ bits, uint64_t nbits)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_slots; i += stride) {
+        const uint64_t v = (i & 7ull) == 7ull ? 0ull : lines[i];
+        const bool keep = v && table_count_read(counts[i]) > abundance;
+        if (keep && bits && v - 1ull < nbits)
+            atomicOr(bits + ((v - 1ull) >> 5), 1u << ((v - 1ull) & 31u));
+        if (LIST) {
+            const unsigned long long mask = __ballot(keep);
+            if (mask) { // wave-uniform, and every lane of the wave is here: n_slots and the stride are multiples of 256
+                unsigned long long first = 0;
+                if (lane == 0u)
+                    first = atomicAdd(n_out, (unsigned long long)__popcll(mask));
+                first = __shfl(first, 0);
+                const uint64_t pos = first + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+                if (keep && pos < cap)
+                    out[pos] = v - 1ull;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void table_spectrum_kernel(const uint64_t *__restrict__ lines, const uint32_t *__restrict__ counts,
+                                                             uint64_t n_slots, unsigned long long *__restrict__ hist)
+{
+    __shared__ unsigned long long h[256];
+    h[threadIdx.x] = 0ull;
+    __syncthreads();
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_slots; i += stride)
+        if ((i & 7ull) != 7ull && lines[i])
+            atomicAdd(&h[table_count_read(counts[i])], 1ull);
+    __syncthreads();
+    if (h[threadIdx.x])
+        atomicAdd(hist + threadIdx.x, h[threadIdx.x]);
+}
+
+uint32_t slot_grid(uint64_t n_slots) { return read_grid((n_slots + 255ull) / 256ull, 256u * 16u); }
+
+void free_table(TabState *t)
+{
+    if (t->d_lines)
+        (void)hipFree(t->d_lines);
+    if (t->d_counts)
+        (void)hipFree(t->d_counts);
+    t->d_lines = nullptr;
+    t->d_counts = nullptr;
+    t->log_lines = 0;
+}
+
+// brings keys_known up to date (synchronises `s`)
+int read_keys(TabState *t, hipStream_t s)
+{
+    unsigned long long n = 0;
+    BRX_HIP(hipMemcpyAsync(&n, t->d_nkeys, 8, hipMemcpyDeviceToHost, s));
+    BRX_HIP(hipStreamSynchronize(s));
+    t->keys_known = n;
+    t->pending = 0;
+    return BRX_OK;
+}
+
+// true: a table of 2^log_lines lines stays at most half full with `need` keys
+inline bool fits_half(uint32_t log_lines, uint64_t need) { return (7ull << log_lines) >= 2ull * need; }
+
+// a table for `need` keys (an upper bound), the counted keys carried over
+int regrow(brx_counter *c, uint64_t need, hipStream_t s)
+{
+    TabState *t = c->tab;
+    const int k = c->k;
+    int log_lines = TAB_MIN_LOG_LINES;
+    while (log_lines < TAB_MAX_LOG_LINES && (7ull << log_lines) < 3ull * need)
+        log_lines++;
+    if ((7ull << log_lines) < need + need / 4) {
+        // more keys than slots would send a chain walk round the table for ever: refuse before any kernel runs
+        set_error("counting table: %llu k-mers (%llu counted so far + the bases of this batch) do not fit the largest table of 2^%d lines "
+                  "(%llu slots)", (unsigned long long)need, (unsigned long long)t->keys_known, TAB_MAX_LOG_LINES,
+                  (unsigned long long)(7ull << TAB_MAX_LOG_LINES));
+        return BRX_ERR_NOMEM;
+    }
+    int m = (int)env_u32("BRX_INDEX_M", 0u);
+    if (m <= 0)
+        m = index_auto_m(k, need);
+    if ((!(m & 1) && m != 16) || m < 3 || m > IDX_MAX_M || m > k - 1) {
+        set_error("counting table: bad minimizer length %d for k=%d", m, k);
+        return BRX_ERR_ARG;
+    }
+    const uint64_t line_bytes = 64ull << log_lines, count_bytes = 32ull << log_lines;
+    uint64_t *nl = nullptr;
+    uint32_t *nc = nullptr;
+    hipError_t e = hipMalloc((void **)&nl, line_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&nc, count_bytes);
+    if (e != hipSuccess) {
+        if (nl)
+            (void)hipFree(nl);
+        set_error("hipMalloc(%llu B counting table of 2^%d lines for up to %llu k-mers): %s", (unsigned long long)(line_bytes + count_bytes),
+                  log_lines, (unsigned long long)need, hipGetErrorString(e));
+        return BRX_ERR_NOMEM;
+    }
+    const uint64_t held = t->d_lines ? (96ull << t->log_lines) : 0ull;
+    if (held + line_bytes + count_bytes > t->peak_bytes)
+        t->peak_bytes = held + line_bytes + count_bytes;
+    {
+        KernelTimer z("tab_zero", s);
+        e = hipMemsetAsync(nl, 0, line_bytes, s);
+        if (e == hipSuccess)
+            e = hipMemsetAsync(nc, 0, count_bytes, s);
+    }
+    if (e == hipSuccess && t->d_lines && t->keys_known) {
+        KernelTimer r("tab_rehash", s);
+        const uint64_t n_old = 8ull << t->log_lines;
+        table_rehash_counts_kernel<<<slot_grid(n_old), 256, 0, s>>>(t->d_lines, t->d_counts, n_old, k, nl, nc, 32u - (uint32_t)log_lines,
+                                                                    (uint32_t)m, (uint32_t)(k - m + 1));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s); // the old table is freed below
+    if (e != hipSuccess) {
+        (void)hipFree(nl);
+        (void)hipFree(nc);
+        set_error("counting table regrow: %s", hipGetErrorString(e));
+        return BRX_ERR_HIP;
+    }
+    free_table(t);
+    t->d_lines = nl;
+    t->d_counts = nc;
+    t->log_lines = (uint32_t)log_lines;
+    t->m = (uint32_t)m;
+    return BRX_OK;
+}
+
+} // namespace
+
+namespace brx {
+
+int tab_begin(brx_counter *c)
+{
+    if (!(c->k & 1) || c->k < 5 || c->k > 31) {
+        set_error("table count strategy (BRX_COUNT_TABLE) supports odd 5 <= k <= 31 (got %d)", c->k);
+        return BRX_ERR_UNSUPPORTED;
+    }
+    TabState *t = new TabState();
+    c->tab = t;
+    BRX_HIP(hipMalloc((void **)&t->d_nkeys, 8));
+    BRX_HIP(hipMemset(t->d_nkeys, 0, 8));
+    return BRX_OK;
+}
+
+void tab_free(brx_counter *c)
+{
+    TabState *t = c->tab;
+    if (!t)
+        return;
+    free_table(t);
+    if (t->d_nkeys)
+        (void)hipFree(t->d_nkeys);
+    delete t;
+    c->tab = nullptr;
+}
+
+int tab_reset(brx_counter *c, hipStream_t s)
+{
+    TabState *t = c->tab;
+    if (t->d_lines) {
+        KernelTimer z("tab_zero", s);
+        BRX_HIP(hipMemsetAsync(t->d_lines, 0, 64ull << t->log_lines, s));
+        BRX_HIP(hipMemsetAsync(t->d_counts, 0, 32ull << t->log_lines, s));
+    }
+    BRX_HIP(hipMemsetAsync(t->d_nkeys, 0, 8, s));
+    t->keys_known = t->pending = t->bases_total = 0;
+    return BRX_OK;
+}
+
+int tab_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases, hipStream_t s)
+{
+    TabState *t = c->tab;
+    if (!n_reads || !total_bases)
+        return BRX_OK;
+    // every k-mer of the batch could be new
+    if (!t->d_lines || !fits_half(t->log_lines, t->keys_known + t->pending + total_bases)) {
+        if (t->pending)
+            BRX_TRY(read_keys(t, s)); // the bound was what did not fit: now the exact number
+        if (!t->d_lines || !fits_half(t->log_lines, t->keys_known + total_bases))
+            BRX_TRY(regrow(c, t->keys_known + total_bases, s));
+    }
+    {
+        KernelTimer kt("tab_count", s);
+        BRX_TRY(flat_table_count(d_bases, d_offsets, n_reads, total_bases, c->k, t->d_lines, t->d_counts, 32u - t->log_lines, t->m,
+                                 t->d_nkeys, s));
+    }
+    t->pending += total_bases;
+    t->bases_total += total_bases;
+    return BRX_OK;
+}
+
+int tab_finish_into(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set *dst)
+{
+    TabState *t = c->tab;
+    if (t->pending)
+        BRX_TRY(read_keys(t, s));
+    if (!dst->d_keylist_n)
+        BRX_HIP(hipMalloc((void **)&dst->d_keylist_n, 8));
+    BRX_HIP(hipMemsetAsync(dst->d_keylist_n, 0, 8, s));
+    if (!dst->sparse) { // the bits are written here, in the same pass (nothing left lazy)
+        BRX_HIP(hipMemsetAsync(dst->d_bits, 0, dst->nwords * 4, s));
+        dst->bits_stale = false;
+    }
+    const bool list = dst->sparse || index_wanted(c->k);
+    if (t->keys_known && t->d_lines) {
+        if (list) {
+            // a listed key was seen more than `abundance` times, and is one of the distinct keys
+            uint64_t want = t->bases_total / ((uint64_t)abundance + 1ull);
+            if (want > t->keys_known)
+                want = t->keys_known;
+            want += 64;
+            if (dst->keylist_cap < want || !dst->d_keylist) {
+                if (dst->d_keylist)
+                    (void)hipFree(dst->d_keylist);
+                dst->d_keylist = nullptr;
+                dst->keylist_cap = 0;
+                BRX_HIP(hipMalloc((void **)&dst->d_keylist, want * 8));
+                dst->keylist_cap = want;
+            }
+        }
+        KernelTimer kt("tab_select", s);
+        const uint64_t n_slots = 8ull << t->log_lines;
+        if (list)
+            table_select_kernel<true><<<slot_grid(n_slots), 256, 0, s>>>(t->d_lines, t->d_counts, n_slots, abundance, dst->d_keylist,
+                                                                        dst->keylist_cap, dst->d_keylist_n, dst->sparse ? nullptr : dst->d_bits,
+                                                                        dst->nwords * 32);
+        else
+            table_select_kernel<false><<<slot_grid(n_slots), 256, 0, s>>>(t->d_lines, t->d_counts, n_slots, abundance, nullptr, 0, nullptr,
+                                                                         dst->d_bits, dst->nwords * 32);
+        BRX_HIP(hipGetLastError());
+    }
+    dst->keylist_valid = list; // (nothing counted: the empty list)
+    trace_stage(s, "table select");
+    return BRX_OK;
+}
+
+// bins 1..255 of the count spectrum into d_hist (256 x u64, zeroed by the caller); the counter is left as it was
+int tab_spectrum(brx_counter *c, hipStream_t s, unsigned long long *d_hist)
+{
+    TabState *t = c->tab;
+    if (!t->d_lines)
+        return BRX_OK;
+    KernelTimer kt("tab_spectrum", s);
+    const uint64_t n_slots = 8ull << t->log_lines;
+    table_spectrum_kernel<<<slot_grid(n_slots), 256, 0, s>>>(t->d_lines, t->d_counts, n_slots, d_hist);
+    BRX_HIP(hipGetLastError());
+    return BRX_OK;
+}
+
+int tab_info(brx_counter *c, uint64_t *info4, hipStream_t s)
+{
+    TabState *t = c->tab;
+    if (t->pending)
+        BRX_TRY(read_keys(t, s));
+    info4[0] = t->d_lines ? t->log_lines : 0;
+    info4[1] = t->d_lines ? t->m : 0;
+    info4[2] = t->keys_known;
+    info4[3] = t->peak_bytes;
+    return BRX_OK;
+}
+
+} // namespace brx

@@ -630,6 +630,9 @@ int brx_exchange_build_partitioned(brx_comm_t *cm, brx_counter_t *c, uint8_t abu
         set_error("exchange: communicator on device %d, counter on %d (k=%d), set on %d (k=%d)", cm->device, c->device, c->k,
                   dst->device, dst->k);
         local = BRX_ERR_ARG;
+    } else if (c->strategy == BRX_COUNT_TABLE) {
+        set_error("exchange: not available with the table count strategy (BRX_COUNT_TABLE); sets of k >= 23 are built on one GPU");
+        local = BRX_ERR_UNSUPPORTED;
     }
     BRX_TRY(use_device(cm->device));
     std::lock_guard<std::mutex> g(cm->mu);

@@ -251,6 +251,52 @@ __device__ __forceinline__ bool table_find_or_insert(uint64_t *lines, uint32_t l
         line = (line + 1u) & line_mask; // the table is kept at most half full: this ends
     }
 }
+
+// Counting table (BRX_COUNT_TABLE, brx_counttable.hip): the same chained table with one u32 counter per slot in an
+// array of its own, counts[line * 8 + slot] (entry 7 of a line is never used), so that the lines keep their format.
+// table_find_or_insert's walk, giving the index of the key's slot (`fresh`: this call put the key there).  The key
+// goes in with the one CAS, so no slot is ever claimed but unfilled and nobody waits for anybody.
+__device__ __forceinline__ uint64_t table_find_or_claim(uint64_t *lines, uint32_t line_shift, uint32_t m, uint32_t w, int k, uint64_t fwd,
+                                                        bool &fresh)
+{
+    const uint64_t rc = revcomp(fwd, k);
+    const unsigned long long key = (((popc64(fwd) & 1) ? rc : fwd) >> 1) + 1ull;
+    const uint32_t line_mask = 0xffffffffu >> line_shift;
+    uint32_t line = index_line_of(minimizer_of(fwd, rc, m, w), line_shift);
+    bool first = true;
+    for (;;) {
+        unsigned long long *L = reinterpret_cast<unsigned long long *>(lines) + (uint64_t)line * 8ull;
+        for (int j = 0; j < IDX_SLOTS; j++) {
+            unsigned long long v = __hip_atomic_load(L + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            fresh = false;
+            if (v == 0ull) {
+                v = atomicCAS(L + j, 0ull, key);
+                fresh = v == 0ull;
+            }
+            if (fresh || v == key)
+                return (uint64_t)line * 8ull + (uint64_t)j;
+        }
+        {
+            const unsigned long long want = (unsigned long long)IDX_OVERFLOW | (first ? (unsigned long long)idx_sig_bit(key) : 0ull);
+            if ((__hip_atomic_load(L + 7, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & want) != want)
+                atomicOr(L + 7, want);
+        }
+        first = false;
+        line = (line + 1u) & line_mask; // the host keeps the table at most about half full: this ends
+    }
+}
+
+constexpr uint32_t TAB_COUNT_MAX = 255u; // what a counter is read as at most (pcon's Counter<u8>)
+// One more occurrence.  A counter that has reached 255 is left alone, so it stands for min(255, occurrences) however
+// long the input: lanes that all saw 254 may each add their one, which leaves it above 255 by less than the number of
+// threads in flight (far from 2^32, and every reader takes min(255, .)).  One atomic add on the slot's own word: no
+// retry loop, nothing carried into a neighbour, and lanes of a wave that hit one slot are serialised by the memory system.
+__device__ __forceinline__ void table_count_bump(uint32_t *counter, uint32_t by = 1u)
+{
+    if (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < TAB_COUNT_MAX)
+        atomicAdd(counter, by);
+}
+__device__ __forceinline__ uint32_t table_count_read(uint32_t v) { return v < TAB_COUNT_MAX ? v : TAB_COUNT_MAX; }
 #endif
 
 } // namespace brx

@@ -127,6 +127,9 @@ int index_insert_reads(brx_set *set, const uint8_t *d_bases, const uint64_t *d_o
 // presence-only insertion over the flat base stream (brx_partbuild.hip); table == nullptr: atomicOr into `bits`
 int flat_presence_insert(const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases, int k,
                          uint32_t *bits, uint64_t *table, uint32_t line_shift, uint32_t m, unsigned long long *d_new, hipStream_t s);
+// counting into a chained table with a u32 counter per slot (brx_partbuild.hip: flat_count_kernel)
+int flat_table_count(const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases, int k, uint64_t *table,
+                     uint32_t *counts, uint32_t line_shift, uint32_t m, unsigned long long *d_new, hipStream_t s);
 // sets of this k have no bit vector
 inline bool sparse_k(int k) { return k >= 21; }
 // the set must be probed through its (chained) index: it has no bit vector, or not right now
@@ -140,7 +143,7 @@ int index_auto_m(int k, uint64_t n_keys);
 bool index_wanted(int k);
 }
 
-namespace brx { struct PartState; }
+namespace brx { struct PartState; struct TabState; }
 
 namespace brx {
 // reverse complement of staged reads (brx_strand.hip; profile timers "strand" / "strand_compact"): into the other staging buffer, lengths
@@ -163,6 +166,8 @@ struct brx_counter {
     brx::PartState *part;
     uint64_t *d_keys;
     uint64_t n_keys, cap_keys;
+    // counting-table strategy (brx_counttable.hip)
+    brx::TabState *tab = nullptr;
     hipStream_t stream; // owned, used by host-pointer entry points
     std::mutex mu;
 };

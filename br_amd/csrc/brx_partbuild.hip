@@ -621,6 +621,35 @@ __global__ __launch_bounds__(256) void flat_insert_kernel(L1Args a, uint32_t *__
     }
 }
 
+// counting into the chained table (BRX_COUNT_TABLE, brx_counttable.hip): flat_insert_kernel<true>'s walk over the tiles,
+// and every valid k-mer then adds one to the counter of the slot that holds it (n_new: keys this launch put in)
+__global__ __launch_bounds__(256) void flat_count_kernel(L1Args a, uint64_t *__restrict__ lines, uint32_t *__restrict__ counts,
+                                                         uint32_t line_shift, uint32_t m, uint32_t w, unsigned long long *__restrict__ n_new)
+{
+    __shared__ uint32_t pk[PACK_WORDS];
+    __shared__ uint32_t bnd[BND_WORDS];
+    __shared__ uint32_t sh_r0[2];
+    uint32_t added = 0;
+    uint32_t lo, hi;
+    l1_range(a.n_items, lo, hi);
+    for (uint32_t item = lo; item < hi; item++) {
+        uint32_t n_here;
+        l1_prepare(a, item, pk, bnd, sh_r0, n_here, item == lo);
+        for (uint32_t p = threadIdx.x; p < n_here; p += 256)
+            if (l1_valid(bnd, p, a.k)) {
+                bool fresh;
+                const uint64_t slot = table_find_or_claim(lines, line_shift, m, w, a.k, kmer_at(pk, p, a.k), fresh);
+                added += fresh ? 1u : 0u;
+                table_count_bump(counts + slot);
+            }
+        __syncthreads();
+    }
+    for (int d = 32; d > 0; d >>= 1)
+        added += __shfl_down(added, d);
+    if ((threadIdx.x & 63) == 0 && added)
+        atomicAdd(n_new, (unsigned long long)added);
+}
+
 // shared by the scatter kernels: block scan of cntv -> lofs/lcur (all in LDS), in two halves around one barrier so that
 // a caller with a barrier of its own there can share it
 __device__ __forceinline__ void scan_bins_begin(uint32_t B, const uint32_t *cntv, uint32_t *sh_wsum, uint32_t &mine, uint32_t &incl)
@@ -1685,6 +1714,30 @@ int flat_presence_insert(const uint8_t *d_bases, const uint64_t *d_offsets, uint
         flat_insert_kernel<true><<<grid, 256, 0, s>>>(a, nullptr, table, line_shift, m, (uint32_t)k - m + 1u, d_new);
     else
         flat_insert_kernel<false><<<grid, 256, 0, s>>>(a, bits, nullptr, 0, 0, 0, nullptr);
+    BRX_HIP(hipGetLastError());
+    return BRX_OK;
+}
+
+// counts a batch into a counting table (see flat_count_kernel); *d_new grows by the keys that were not there yet
+int flat_table_count(const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases, int k, uint64_t *table,
+                     uint32_t *counts, uint32_t line_shift, uint32_t m, unsigned long long *d_new, hipStream_t s)
+{
+    if (!total_bases || !n_reads)
+        return BRX_OK;
+    const uint64_t n_items64 = (total_bases + L1_TILE - 1) / L1_TILE;
+    if (n_items64 >= (1ull << 32)) {
+        set_error("batch of %llu bases is too large for one counting pass; split it", (unsigned long long)total_bases);
+        return BRX_ERR_UNSUPPORTED;
+    }
+    L1Args a;
+    memset(&a, 0, sizeof(a));
+    a.bases = d_bases;
+    a.offsets = d_offsets;
+    a.n_reads = n_reads;
+    a.total = total_bases;
+    a.n_items = (uint32_t)n_items64;
+    a.k = k;
+    flat_count_kernel<<<read_grid(a.n_items, 4096u), 256, 0, s>>>(a, table, counts, line_shift, m, (uint32_t)k - m + 1u, d_new);
     BRX_HIP(hipGetLastError());
     return BRX_OK;
 }

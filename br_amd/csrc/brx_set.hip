@@ -359,6 +359,15 @@ int part_finish_into(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set 
 int part_spectrum(brx_counter *c, hipStream_t s, unsigned long long *d_hist);
 int part_l1_view(brx_counter *c, void **d_keys, void **d_l1off, uint32_t *n_buckets, uint64_t *n_keys);
 int part_add_partitioned(brx_counter *c, const uint32_t *d_keys, const uint64_t *d_l1off, uint64_t n_keys);
+// counting-table strategy (brx_counttable.hip)
+int tab_begin(brx_counter *c);
+void tab_free(brx_counter *c);
+int tab_reset(brx_counter *c, hipStream_t s);
+int tab_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
+                  hipStream_t s);
+int tab_finish_into(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set *dst);
+int tab_spectrum(brx_counter *c, hipStream_t s, unsigned long long *d_hist);
+int tab_info(brx_counter *c, uint64_t *info4, hipStream_t s);
 // used by the correction chain and the host-pointer entry points
 int upload_batch(const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, uint8_t **d_bases, uint64_t *bases_cap,
                  uint64_t **d_off, uint64_t *off_cap, uint64_t *total, hipStream_t stream)
@@ -665,9 +674,9 @@ int brx_set_count_begin(uint8_t k, int device, int strategy, brx_counter_t **out
         return BRX_ERR_ARG;
     BRX_TRY(check_k(k, true));
     BRX_TRY(use_device(device));
-    if (strategy == BRX_COUNT_AUTO) // the table-free path as soon as the u8 table would not fit the caches
-        strategy = (part_supported(k) && k >= 15) ? BRX_COUNT_SORTED : BRX_COUNT_DENSE;
-    if (strategy != BRX_COUNT_DENSE && strategy != BRX_COUNT_SORTED) {
+    if (strategy == BRX_COUNT_AUTO) // the table-free path as soon as the u8 table would not fit the caches; past its 32-bit keys, the hash table
+        strategy = k >= 23 ? BRX_COUNT_TABLE : (part_supported(k) && k >= 15) ? BRX_COUNT_SORTED : BRX_COUNT_DENSE;
+    if (strategy != BRX_COUNT_DENSE && strategy != BRX_COUNT_SORTED && strategy != BRX_COUNT_TABLE) {
         set_error("unknown count strategy %d", strategy);
         return BRX_ERR_ARG;
     }
@@ -691,8 +700,8 @@ int brx_set_count_begin(uint8_t k, int device, int strategy, brx_counter_t **out
         brx_counter_free(c);
         return BRX_ERR_HIP;
     }
-    if (strategy == BRX_COUNT_SORTED) {
-        int st = part_begin(c);
+    if (strategy == BRX_COUNT_SORTED || strategy == BRX_COUNT_TABLE) {
+        int st = strategy == BRX_COUNT_TABLE ? tab_begin(c) : part_begin(c);
         if (st != BRX_OK) {
             brx_counter_free(c);
             return st;
@@ -729,6 +738,8 @@ int brx_set_count_add_batch_device(brx_counter_t *c, const uint8_t *d_bases, con
     hipStream_t s = (hipStream_t)stream;
     if (c->strategy == BRX_COUNT_SORTED)
         return part_add_batch(c, d_bases, d_offsets, n_reads, total_bases, s);
+    if (c->strategy == BRX_COUNT_TABLE)
+        return tab_add_batch(c, d_bases, d_offsets, n_reads, total_bases, s);
     {
         KernelTimer t("count_dense", s);
         kmer_scatter_kernel<0><<<grid_for(n_reads, 1, 1 << 20), 256, 0, s>>>(d_bases, d_offsets, n_reads, c->k,
@@ -774,6 +785,8 @@ int brx_counter_reset(brx_counter_t *c, void *stream)
     hipStream_t s = (hipStream_t)stream;
     if (c->strategy == BRX_COUNT_SORTED)
         return part_reset(c);
+    if (c->strategy == BRX_COUNT_TABLE)
+        return tab_reset(c, s);
     if (c->d_counts) {
         KernelTimer t("count_zero", s);
         BRX_HIP(hipMemsetAsync(c->d_counts, 0, c->count_bytes, s));
@@ -796,6 +809,8 @@ int brx_set_count_finish_into(brx_counter_t *c, uint8_t abundance, void *stream,
     hipStream_t s = (hipStream_t)stream; // nullptr = the legacy default stream, like any HIP API
     if (c->strategy == BRX_COUNT_SORTED)
         return part_finish_into(c, abundance, s, dst);
+    if (c->strategy == BRX_COUNT_TABLE)
+        return tab_finish_into(c, abundance, s, dst);
     if (dst->sparse) {
         set_error("the dense count strategy needs a bit vector; a sparse set (k=%d) has none", dst->k);
         return BRX_ERR_UNSUPPORTED;
@@ -843,9 +858,10 @@ int brx_counter_spectrum(brx_counter_t *c, uint64_t *hist256, void *stream)
     BRX_HIP(hipMalloc((void **)&d_h, 256 * 8));
     hipError_t e = hipMemsetAsync(d_h, 0, 256 * 8, s);
     const uint64_t nbytes = set_nbits(c->k); // real entries (the table may be padded to 32 B)
-    if (c->strategy == BRX_COUNT_SORTED) {
-        // no table to read: the partitioned keys are counted bucket by bucket (bins 1..255); bin 0 is the rest
-        int st = e == hipSuccess ? part_spectrum(c, s, d_h) : BRX_ERR_HIP;
+    if (c->strategy == BRX_COUNT_SORTED || c->strategy == BRX_COUNT_TABLE) {
+        // no u8 table to read: the partitioned keys are counted bucket by bucket, the hash table's slots are binned (bins
+        // 1..255); bin 0 is the rest
+        int st = e != hipSuccess ? BRX_ERR_HIP : c->strategy == BRX_COUNT_TABLE ? tab_spectrum(c, s, d_h) : part_spectrum(c, s, d_h);
         if (st == BRX_OK) {
             e = hipMemcpyAsync(hist256, d_h, 256 * 8, hipMemcpyDeviceToHost, s);
             if (e == hipSuccess)
@@ -886,6 +902,10 @@ int brx_counter_device_counts(brx_counter_t *c, void **d_counts, uint64_t *n_byt
 {
     if (!c || !d_counts || !n_bytes)
         return BRX_ERR_ARG;
+    if (c->strategy == BRX_COUNT_TABLE) {
+        set_error("device_counts: not available with the table count strategy (BRX_COUNT_TABLE)");
+        return BRX_ERR_UNSUPPORTED;
+    }
     if (c->strategy != BRX_COUNT_DENSE) {
         set_error("counter is not dense");
         return BRX_ERR_ARG;
@@ -899,6 +919,10 @@ int brx_counter_load_counts(brx_counter_t *c, uint64_t first, const uint8_t *cou
 {
     if (!c || (!counts && n))
         return BRX_ERR_ARG;
+    if (c->strategy == BRX_COUNT_TABLE) {
+        set_error("load_counts: not available with the table count strategy (BRX_COUNT_TABLE)");
+        return BRX_ERR_UNSUPPORTED;
+    }
     if (c->strategy != BRX_COUNT_DENSE) {
         set_error("load_counts needs the dense count strategy");
         return BRX_ERR_UNSUPPORTED;
@@ -917,6 +941,10 @@ int brx_counter_load_counts(brx_counter_t *c, uint64_t first, const uint8_t *cou
 
 int brx_counter_clamp(brx_counter_t *c, uint8_t cap, void *stream)
 {
+    if (c && c->strategy == BRX_COUNT_TABLE) {
+        set_error("clamp: not available with the table count strategy (BRX_COUNT_TABLE)");
+        return BRX_ERR_UNSUPPORTED;
+    }
     if (!c || c->strategy != BRX_COUNT_DENSE)
         return BRX_ERR_ARG;
     BRX_TRY(use_device(c->device));
@@ -934,6 +962,10 @@ int brx_counter_l1_view(brx_counter_t *c, void **d_keys, void **d_l1off, uint32_
 {
     if (!c || !d_keys || !d_l1off || !n_buckets || !n_keys)
         return BRX_ERR_ARG;
+    if (c->strategy == BRX_COUNT_TABLE) {
+        set_error("l1_view: not available with the table count strategy (BRX_COUNT_TABLE)");
+        return BRX_ERR_UNSUPPORTED;
+    }
     if (c->strategy != BRX_COUNT_SORTED) {
         set_error("l1_view: counter is not partitioned");
         return BRX_ERR_ARG;
@@ -945,11 +977,27 @@ int brx_counter_add_partitioned_device(brx_counter_t *c, const uint32_t *d_keys,
 {
     if (!c || (!d_keys && n_keys) || !d_l1off)
         return BRX_ERR_ARG;
+    if (c->strategy == BRX_COUNT_TABLE) {
+        set_error("add_partitioned: not available with the table count strategy (BRX_COUNT_TABLE)");
+        return BRX_ERR_UNSUPPORTED;
+    }
     if (c->strategy != BRX_COUNT_SORTED) {
         set_error("add_partitioned: counter is not partitioned");
         return BRX_ERR_ARG;
     }
     return part_add_partitioned(c, d_keys, d_l1off, n_keys);
+}
+
+int brx_counter_table_info(brx_counter_t *c, uint64_t *info4, void *stream)
+{
+    if (!c || !info4)
+        return BRX_ERR_ARG;
+    if (c->strategy != BRX_COUNT_TABLE) {
+        set_error("table_info: counter does not use the table count strategy (BRX_COUNT_TABLE)");
+        return BRX_ERR_UNSUPPORTED;
+    }
+    BRX_TRY(use_device(c->device));
+    return tab_info(c, info4, (hipStream_t)stream);
 }
 
 int brx_set_extract_keys_device(const brx_set_t *set, uint64_t first_hash, uint64_t n_hashes, uint64_t *d_out, uint64_t cap,
@@ -1018,6 +1066,8 @@ void brx_counter_free(brx_counter_t *c)
     if (use_device(c->device) == BRX_OK) {
         if (c->part)
             part_free(c);
+        if (c->tab)
+            tab_free(c);
         if (c->d_counts)
             (void)hipFree(c->d_counts);
         if (c->d_keys)

@@ -294,7 +294,8 @@ class Pcon(KmerSet):
 
 
 class Counter:
-    """pcon::counter::Counter<u8> as used by `br fasta` (src/main.rs:73-78)."""
+    """pcon::counter::Counter<u8> as used by `br fasta` (src/main.rs:73-78).  Odd k up to 31: COUNT_AUTO takes the dense
+    u8 table below 15, the partitioned counter for 15..21 and the counting hash table (COUNT_TABLE) for 23..31."""
 
     def __init__(self, k: int, device: int = 0, strategy: int = _lib.COUNT_AUTO):
         self._h = C.c_void_p()
@@ -369,7 +370,7 @@ class Counter:
 
     def spectrum(self, stream: Optional[int] = None) -> np.ndarray:
         """pcon::spectrum::Spectrum::from_count: uint64[256] histogram of the counts (255 = 255 or more).
-        Either strategy; the counter is left as it was, so `finish(threshold)` can follow."""
+        Any strategy; the counter is left as it was, so `finish(threshold)` can follow."""
         h = np.zeros(256, dtype=np.uint64)
         _lib.check(_lib.lib().brx_counter_spectrum(self._h, h.ctypes.data_as(C.POINTER(C.c_uint64)), stream))
         return h
@@ -382,6 +383,12 @@ class Counter:
 
     def add_partitioned_device(self, d_keys: int, d_l1off: int, n_keys: int) -> None:
         _lib.check(_lib.lib().brx_counter_add_partitioned_device(self._h, d_keys, d_l1off, n_keys))
+
+    def table_info(self, stream: Optional[int] = None) -> dict:
+        """the hash table of a COUNT_TABLE counter: log2 of its lines, minimizer length, distinct k-mers, peak bytes held"""
+        v = (C.c_uint64 * 4)()
+        _lib.check(_lib.lib().brx_counter_table_info(self._h, v, stream))
+        return {"log2_lines": int(v[0]), "m": int(v[1]), "keys": int(v[2]), "peak_bytes": int(v[3])}
 
     def reset(self, stream: Optional[int] = None) -> None:
         _lib.check(_lib.lib().brx_counter_reset(self._h, stream))

@@ -204,8 +204,18 @@ int brx_set_cover_split_batch(const brx_set_t *set, const uint8_t *bases, const 
  * k must be odd (Fasta::kmer_size forces it, src/cli.rs:277-279).
  * strategy: BRX_COUNT_DENSE keeps the reference's 2^(2k-1)-byte u8 table in HBM (k <= 19: 128 GiB);
  * BRX_COUNT_SORTED radix-partitions the canonical hashes and counts them bucket by bucket (same
- * set, no table; k <= 21); BRX_COUNT_AUTO = SORTED for 15 <= k <= 21, else DENSE.                 */
-enum { BRX_COUNT_AUTO = 0, BRX_COUNT_DENSE = 1, BRX_COUNT_SORTED = 2 };
+ * set, no table; k <= 21, its keys are 32 bits wide after the first digit);
+ * BRX_COUNT_TABLE counts into a hash table in HBM -- the chained 64-byte-line table sparse sets are made of, 7 keys per
+ * line, with one u32 counter per slot in an array beside the lines that stops being incremented at 255, so a count
+ * reads as min(255, occurrences) whatever the input.  Any odd k from 5 to 31.  The table is kept at most about half
+ * full: when the distinct k-mers so far plus the bases of the next batch no longer fit, a larger one is allocated and
+ * the keys are moved with their counts (add_batch_device may synchronise `stream` for that); past the largest table,
+ * 2^30 lines (64 GiB of lines + 32 GiB of counters, 7.5 G slots), add_batch returns BRX_ERR_NOMEM.  finish lists the
+ * keys with count > abundance in one pass and leaves an ordinary closed set: sparse for k >= 21, with its bit vector
+ * written for k <= 19.  Single GPU: device_counts, load_counts, clamp, l1_view, add_partitioned_device and the
+ * brx_exchange_* entries return BRX_ERR_UNSUPPORTED for such a counter.
+ * BRX_COUNT_AUTO = DENSE below 15, SORTED for 15 <= k <= 21, TABLE for 23 <= k <= 31.                              */
+enum { BRX_COUNT_AUTO = 0, BRX_COUNT_DENSE = 1, BRX_COUNT_SORTED = 2, BRX_COUNT_TABLE = 3 };
 int brx_set_count_begin(uint8_t k, int device, int strategy, brx_counter_t **out);
 int brx_set_count_add_batch(brx_counter_t *c, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads);
 int brx_set_count_add_batch_device(brx_counter_t *c, const uint8_t *d_bases, const uint64_t *d_offsets,
@@ -219,7 +229,8 @@ int brx_set_count_finish_into(brx_counter_t *c, uint8_t abundance, void *stream,
 int brx_counter_reset(brx_counter_t *c, void *stream);
 /* 256-bin histogram of the counts = pcon::spectrum::Spectrum::from_count (src/main.rs:93):
  * hist256[v] = number of canonical k-mers seen exactly v times (255 = 255 or more, 0 = never).  Either
- * strategy; the counter is left as it was, so brx_set_count_finish with the chosen threshold follows.   */
+ * strategy (TABLE: bins 1..255 from the slot counters, bin 0 = 2^(2k-1) - distinct k-mers); the counter is left as it
+ * was, so brx_set_count_finish with the chosen threshold follows.                                       */
 int brx_counter_spectrum(brx_counter_t *c, uint64_t *hist256, void *stream);
 /* dense strategy only: device view of the u8 table, for the RCCL reduction of SURVEY 8(e)   */
 int brx_counter_device_counts(brx_counter_t *c, void **d_counts, uint64_t *n_bytes);
@@ -235,6 +246,9 @@ int brx_counter_clamp(brx_counter_t *c, uint8_t cap, void *stream);
  * add_partitioned (the memory stays the caller's until the counter is finished/reset).           */
 int brx_counter_l1_view(brx_counter_t *c, void **d_keys, void **d_l1off, uint32_t *n_buckets, uint64_t *n_keys);
 int brx_counter_add_partitioned_device(brx_counter_t *c, const uint32_t *d_keys, const uint64_t *d_l1off, uint64_t n_keys);
+/* table strategy only: [0] log2(lines) of the table (0: none yet), [1] its minimizer length, [2] distinct k-mers counted
+ * (read back from the device: synchronises `stream`), [3] most bytes of table held at once (both tables during a regrow) */
+int brx_counter_table_info(brx_counter_t *c, uint64_t *info4, void *stream);
 void brx_counter_free(brx_counter_t *c);
 
 /* ---- multi-GPU: reads shard over the GPUs, the set is exchanged ONCE -----------------------------
