@@ -535,6 +535,25 @@ __global__ __launch_bounds__(256, (M == BRX_ONE ? (G == 64 ? 7 : 6)
             // trigger-free rounds of the 64-lane form (every method's reverse pass is almost only these) in a loop of
             // their own, as in one_kernel: 64 positions, one probe each, ballot, accept; a round with a trigger is
             // left to the general code below, which redoes its (pure) probes
+            // (REV_BLOCK rounds at a time where the occupancy bits can filter them: rev_block_rounds, brx_correct.hpp.  Not
+            // Greedy's kernel: its alignment already takes dynamic LDS per group, and with the queue's 8 KB beside it
+            // configs[2] measured 902 ms per step against 891)
+            while (!HAS_GREEDY && p.rev_batch && have && st == ST_SCAN && !slow && n - i >= 64u * REV_BLOCK + 1u && olen + 64u * REV_BLOCK + 2u <= cap) {
+                const uint8_t *const in_b = (const uint8_t *)uni64((uint64_t)in);
+                uint8_t *const out_b = (uint8_t *)uni64((uint64_t)(out + olen));
+                const uint32_t n_b = uni32(n), i_b = uni32(i);
+                const bool flip_b = p.flip != 0;
+                const uint32_t t = rev_block_rounds<HAS_ERRLEN>(p.idx, p.bits, k, mask, lane,
+                                                                [in_b, n_b, flip_b](uint32_t j) -> uint8_t { return in_b[flip_b ? (n_b - 1u - j) : j]; }, i_b,
+                                                                out_b, uni32(skip_until), kmer, prev);
+                olen += 64u * t;
+                i += 64u * t;
+                n_rounds += t;
+                n_probes += 64u * t;
+                steps += t;
+                if (t < (uint32_t)REV_BLOCK)
+                    break;
+            }
             while (have && st == ST_SCAN && !slow && n - i >= 65u && olen + 66u <= cap) {
                 const uint8_t c8 = ld(i + (uint32_t)lane);
                 const uint64_t km = lane_kmer64_dpp(kmer, (uint32_t)nuc2bit(c8), lane, mask);
@@ -1600,6 +1619,28 @@ __global__ __launch_bounds__(256, (G == 64 ? BRX_ONE64_WAVES : 7)) void one_kern
             // every round is "64 positions, no trigger": that round in a loop of its own, without the state dispatch,
             // the trigger machinery and the register copies at their joins.  A round that does find a trigger is left to the general
             // code below, which redoes its probes (they are pure).
+            // REV_BLOCK such rounds at a time where the set's occupancy bits can filter them (rev_block_rounds,
+            // brx_correct.hpp); the rounds left over, and the round that holds a trigger, go through the loop behind it.
+            while (p.rev_batch && have && st == ST_SCAN && !slow && n - i >= 64u * REV_BLOCK + 1u && olen + 64u * REV_BLOCK + 2u <= cap) {
+                // (the packed counters take REV_BLOCK rounds at once: make room first, so that no field passes 255 and
+                // since_flush stays below the 255 the one-round paths test for)
+                if (since_flush + REV_BLOCK >= 255u)
+                    flush();
+                const uint8_t *const in_b = (const uint8_t *)uni64((uint64_t)in);
+                uint8_t *const out_b = (uint8_t *)uni64((uint64_t)(out + olen));
+                const uint32_t n_b = uni32(n), i_b = uni32(i);
+                const bool flip_b = p.flip != 0;
+                const uint32_t t = rev_block_rounds<false>(p.idx, p.bits, k, mask, lane,
+                                                           [in_b, n_b, flip_b](uint32_t j) -> uint8_t { return in_b[flip_b ? (n_b - 1u - j) : j]; }, i_b,
+                                                           out_b, 0u, kmer, prev);
+                olen += 64u * t;
+                i += 64u * t;
+                ev += ((lane == 0) ? t : 0u) + (t << 8);
+                steps += t;
+                since_flush += t;
+                if (t < (uint32_t)REV_BLOCK)
+                    break;
+            }
             while (have && st == ST_SCAN && !slow && n - i >= 65u && olen + 66u <= cap) {
                 const uint8_t c8 = ld(i + (uint32_t)lane);
                 uint32_t sc;
@@ -1648,12 +1689,23 @@ __global__ __launch_bounds__(256, (G == 64 ? BRX_ONE64_WAVES : 7)) void one_kern
                         out[j] = ld(j);
                     olen = n;
                 } else {
-                    uint64_t km = 0;
-                    for (int j = 0; j < k; j++)
-                        km = (km << 2) | nuc2bit(ld((uint32_t)j));
-                    kmer = km;
-                    for (uint32_t j = gl; j < (uint32_t)k; j += G)
-                        out[j] = ld(j);
+                    if (G == 64) {
+                        // (one base per lane and the scan that builds the rounds' k-mers: k loads in flight per lane were
+                        // the kernel's register peak)
+                        const uint8_t cj = lane < k ? ld((uint32_t)lane) : (uint8_t)0;
+                        const uint64_t kv = lane_kmer64_dpp(0ull, (uint32_t)nuc2bit(cj), lane, mask);
+                        kmer = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(kv >> 32), k - 1) << 32) |
+                               (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)kv, k - 1);
+                        if (lane < k)
+                            out[lane] = cj;
+                    } else {
+                        uint64_t km = 0;
+                        for (int j = 0; j < k; j++)
+                            km = (km << 2) | nuc2bit(ld((uint32_t)j));
+                        kmer = km;
+                        for (uint32_t j = gl; j < (uint32_t)k; j += G)
+                            out[j] = ld(j);
+                    }
                     olen = (uint32_t)k;
                     i = (uint32_t)k;
                     do_probe = (gl == 0);
@@ -2066,7 +2118,7 @@ __global__ __launch_bounds__(256, BRX_REV_WAVES) void rev_scan_kernel(const Pass
     const uint64_t *const offsets = pp.offsets;
     const uint8_t *const in_base = pp.in;
     const uint32_t *const in_lens = pp.in_lens;
-    const bool in_staged = pp.in_staged != 0, flip = pp.flip != 0;
+    const bool in_staged = pp.in_staged != 0, flip = pp.flip != 0, rev_batch = pp.rev_batch != 0;
     uint8_t *const out_base = pp.out;
     uint32_t *const out_lens = pp.out_lens;
     constexpr bool HAS_ERRLEN = (M == BRX_GRAPH || M == BRX_GAP_SIZE);
@@ -2136,6 +2188,21 @@ __global__ __launch_bounds__(256, BRX_REV_WAVES) void rev_scan_kernel(const Pass
             n_probes++;
         }
         while (!hb && i < n) {
+            // ---- scan, REV_BLOCK full rounds at a time where the occupancy bits can filter them (rev_block_rounds) ----
+            if (rev_batch && n - i >= 64u * REV_BLOCK + 1u) {
+                const uint32_t t = rev_block_rounds<HAS_ERRLEN>(idx, bits, k, mask, lane,
+                                                                [in, n, flip](uint32_t j) -> uint8_t { return in[flip ? (n - 1u - j) : j]; }, i,
+                                                                out + i, skip_until, kmer, prev);
+                for (uint32_t q = 0; q < t; q++) { // (what the one-round form below counts: the positions it asks about)
+                    const uint32_t p0 = i + 64u * q;
+                    const uint32_t skipped = (HAS_ERRLEN && skip_until > p0) ? (skip_until - p0 < 64u ? skip_until - p0 : 64u) : 0u;
+                    n_probes += 64u - skipped;
+                }
+                n_rounds += t;
+                i += 64u * t;
+                if (t == (uint32_t)REV_BLOCK)
+                    continue;
+            }
             // ---- scan: 64 positions (mod.rs:68-104 while nothing triggers) -------------------------------------------
             const uint32_t pos = i + (uint32_t)lane;
             const bool valid = pos < n;
@@ -2574,6 +2641,14 @@ bool rev_lean_on()
     return !(e && *e == '0');
 }
 
+// BRX_REV_BATCH=0: the reverse scans' trigger-free rounds one at a time, as before rev_block_rounds (A/B runs, and the
+// fuzzer sweeps it)
+bool rev_batch_on()
+{
+    const char *e = getenv("BRX_REV_BATCH");
+    return !(e && *e == '0');
+}
+
 template <int M>
 void launch_rev_scan(const PassParams &p, uint32_t *list, uint32_t *flag, TrigRec *trig, uint32_t trig_cap, uint32_t blocks, hipStream_t s)
 {
@@ -2951,6 +3026,8 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
                 p.maxpath = maxpath;
                 BRX_HIP(hipMemsetAsync(ch->d_ctrl + CTL_WORK, 0, 8, s));
                 p.flags = 0;
+                // the reverse scans' trigger-free rounds in blocks (rev_block_rounds): the read runs back to front, not complemented
+                p.rev_batch = (dir == 1 && !revcomp && rev_batch_on() && rev_block_applies(p.idx)) ? 1 : 0;
                 p.max_search = 0;
                 p.g_dim = 0;
                 p.g_lds_bytes = 0;

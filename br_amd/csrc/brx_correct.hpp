@@ -68,6 +68,9 @@ struct PassParams {
     uint32_t trig_cap = 0;
     uint32_t *redo_list = nullptr;
     uint32_t *redo_flag = nullptr;
+    // reverse scans: trigger-free rounds REV_BLOCK at a time through the occupancy bits (rev_block_rounds); set by the host
+    // only where rev_block_applies(idx)
+    int rev_batch = 0;
 };
 
 __host__ __device__ __forceinline__ uint64_t slot_of(uint64_t o, uint64_t r, uint32_t slack)
@@ -112,7 +115,175 @@ __device__ __forceinline__ uint64_t lane_kmer64_dpp(uint64_t carry, uint32_t cod
     const uint32_t jb = 2u * ((uint32_t)(lane & 15) + 1u);
     return (((((uint64_t)b2 << 32) | b1) << jb) | v) & mask; // jb <= 32
 }
+#endif
 
+// ----------------------------------------------------------------------------------------------------------------------
+// Trigger-free scan rounds of a reverse pass, REV_BLOCK at a time (one wave per read: one_kernel<64>, correct_kernel<64>,
+// rev_scan_kernel).  Nearly every k-mer of a reversed read is absent and four index lines in five are empty, so a round
+// of 64 positions, one index_get each, makes the whole wave pay for the key, the line fetch and the slot compares of
+// the dozen lanes whose home line holds anything.  Here a round only FILTERS: the lane hashes the newest m-mer of its
+// k-mer, takes the minimum over itself and its w - 1 left neighbours (wave_shr DPP moves; the hashes in front of the
+// wave's span come from the carried k-mer, in scalar arithmetic), and loads the occupancy bit of that line.  Lanes whose bit is set queue
+// (k-mer, line, round << 6 | lane) in LDS; when the block's rounds are through -- or the queue has fewer than 64 places
+// left -- the queue is drained a wave at a time: reverse complement, key, index_probe_at, "cannot say" settled on the
+// spot as index_get does.  A solid k-mer ORs its bit into the block's answer words; the trigger test then runs over
+// those words as it does over a round's ballot.  Probes are pure, so only their order and grouping differ.
+// LDS per wave: 128 entries of 16 bytes + REV_BLOCK answer words + REV_BLOCK carried k-mers = 2 112 bytes at REV_BLOCK = 4,
+// 8 448 per block of 256: 28 waves of a CU (7 per SIMD) take 59 KB of its 160.
+// ----------------------------------------------------------------------------------------------------------------------
+#ifndef BRX_REV_BLOCK
+#define BRX_REV_BLOCK 4 // rounds per block (tools/ab_build.sh sweeps 2 / 4 / 8)
+#endif
+constexpr int REV_BLOCK = BRX_REV_BLOCK;
+constexpr uint32_t REV_MAX_W = 8;   // windows the sliding minimum is unrolled for (m = 15: k <= 22)
+constexpr uint32_t REV_QUEUE = 128; // entries of a wave's queue
+static_assert(REV_BLOCK >= 1 && REV_BLOCK <= 16, "BRX_REV_BLOCK: 1 .. 16 rounds");
+
+// the set's index answers a reverse scan in block form (the rule lane_mask_kernel has for the occupancy bits, and a
+// window count the sliding minimum is instantiated for)
+inline bool rev_block_applies(const IdxView &v)
+{
+    return v.lines != nullptr && v.line_bits != nullptr && v.line_shift >= 6u && v.w >= 1u && v.w <= REV_MAX_W;
+}
+
+#if defined(__HIPCC__)
+// hash of the canonical form of an m-mer (f: its 2m bits, nothing above): window j = 0 of minimizer_hash_w
+__device__ __forceinline__ uint32_t mmer_hash(uint32_t f, uint32_t m)
+{
+    uint32_t x = __brev(f ^ 0xAAAAAAAAu);
+    x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
+    const uint32_t r = x >> (32u - 2u * m);
+    return (f < r ? f : r) * 0x9E3779B1u;
+}
+
+// a wave-uniform value the compiler cannot see to be one (it came through a shuffle): into scalar registers
+__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t uni64(uint64_t v) { return ((uint64_t)uni32((uint32_t)(v >> 32)) << 32) | uni32((uint32_t)v); }
+
+// Up to REV_BLOCK rounds of 64 positions from logical position i on, all of them full (the caller checks n - i and the
+// room in out).  ld(j): logical base j of the read; outp: where position i's byte goes.  Returns the number of rounds
+// committed: kmer and prev then stand behind the last of them, and a return value below REV_BLOCK means that the next
+// round holds a trigger (mod.rs:73) -- nothing of it is settled here but bytes the caller's general code writes again.
+template <bool HAS_SKIP, typename LD>
+__device__ __forceinline__ uint32_t rev_block_rounds(const IdxView &idx, const uint32_t *__restrict__ bits, int k, uint64_t mask, int lane0, LD ld,
+                                                     uint32_t i, uint8_t *__restrict__ outp, uint32_t skip_until, uint64_t &kmer, bool &prev)
+{
+    __shared__ uint4 rev_q[4][REV_QUEUE];
+    __shared__ unsigned long long rev_ans[4][2 * REV_BLOCK]; // per wave: the rounds' answer words, then their carried k-mers
+    const uint32_t wv = uni32(threadIdx.x >> 6); // (scalar: the queue's address then costs no vector register)
+    uint4 *const q = rev_q[wv];
+    unsigned long long *const ans = rev_ans[wv];
+    unsigned long long *const carry = ans + REV_BLOCK;
+    const uint32_t m = idx.m, w = idx.w;
+    const uint32_t mm = m >= 16u ? 0xffffffffu : (1u << (2u * m)) - 1u;
+
+    if (lane0 < REV_BLOCK)
+        ans[lane0] = 0ull;
+
+    // One loop, one copy of each stage: a trip filters a round (k-mer, sliding minimum, occupancy bit) and queues its
+    // survivors; the drain runs when the queue has fewer than 64 places left, and until it is empty after the last round.
+    // (Nothing of a round is live across the drain but the next round's byte: the kernels that call this sit at their
+    // register limits, and the line of index_probe_at is sixteen registers.)
+    uint32_t count = 0; // entries in the queue (wave-uniform); the drain takes them from the top
+    bool any_solid = false;
+    uint64_t cur_carry = uni64(kmer);
+    uint8_t c_next = ld(i + (uint32_t)lane0);
+#pragma unroll 1
+    for (uint32_t r = 0; r < (uint32_t)REV_BLOCK; r++) {
+        {
+            // (an opaque copy of the lane id per stage: the lane constants -- addresses, shift counts, masks -- are then
+            // made where they are used instead of being kept in registers across the other stage and the caller's code)
+            int ln = lane0;
+            asm volatile("" : "+v"(ln));
+            const uint8_t c8 = c_next;
+            if (r + 1u < (uint32_t)REV_BLOCK)
+                c_next = ld(i + 64u * (r + 1u) + (uint32_t)ln);
+            const uint64_t carry_in = cur_carry;
+            const uint64_t km = lane_kmer64_dpp(cur_carry, (uint32_t)nuc2bit(c8), ln, mask);
+            outp[64u * r + (uint32_t)ln] = c8; // mod.rs:100, ahead of the answer: a round that is not committed is written again
+            if (ln == 63)
+                carry[r] = km;
+            cur_carry = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(km >> 32), 63) << 32) |
+                        (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)km, 63);
+            const uint32_t h = mmer_hash((uint32_t)km & mm, m);
+            uint32_t best = h, cur = h;
+#pragma unroll
+            for (uint32_t s = 1; s < REV_MAX_W; s++)
+                if (s < w) { // wave-uniform
+                    // lane l takes lane l - 1's value across the rows; lane 0 takes the hash s positions in front of the
+                    // span: window s - 1 of the carried k-mer (scalar arithmetic, no vector instruction)
+                    const uint32_t front = mmer_hash((uint32_t)(carry_in >> (2u * (s - 1u))) & mm, m);
+                    cur = (uint32_t)__builtin_amdgcn_update_dpp((int)front, (int)cur, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+                    best = cur < best ? cur : best;
+                }
+            const uint32_t home = index_line_of(best, idx.line_shift);
+            bool occ = (idx.line_bits[home >> 5] >> (home & 31u)) & 1u;
+            if (HAS_SKIP && i + 64u * r + (uint32_t)ln < skip_until)
+                occ = false; // (known not solid: error_len asked about it behind a trigger that failed)
+            const uint64_t em = __ballot(occ);
+            if (occ) {
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
+                q[count + rank] = make_uint4((uint32_t)km, (uint32_t)(km >> 32), home, (r << 6) | (uint32_t)ln);
+            }
+            count += (uint32_t)__builtin_popcountll(em);
+            __builtin_amdgcn_wave_barrier();
+        }
+        while (count > REV_QUEUE - 64u || (r + 1u == (uint32_t)REV_BLOCK && count)) {
+            const uint32_t cnt = count < 64u ? count : 64u;
+            bool sol = false;
+            int ln = lane0;
+            asm volatile("" : "+v"(ln));
+            if ((uint32_t)ln < cnt) {
+                const uint4 e = q[count - cnt + (uint32_t)ln];
+                const uint64_t fwd = ((uint64_t)e.y << 32) | e.x;
+                const uint64_t rc = revcomp(fwd, k);
+                const uint64_t key = (((popc64(fwd) & 1) ? rc : fwd) >> 1) + 1ull;
+                int a = index_probe_at(idx, key, e.z, 0u);
+                if (a == 2) { // "cannot say": settled here, as index_get does
+                    if (bits) {
+                        const uint64_t hh = key - 1ull; // khash(fwd, k)
+                        a = (bits[hh >> 5] >> (hh & 31u)) & 1u;
+                    } else {
+                        const uint32_t last = 0xffffffffu >> idx.line_shift;
+                        for (uint32_t hop = 1; a == 2 && hop <= last; hop++)
+                            a = index_probe_at(idx, key, e.z, hop);
+                    }
+                }
+                sol = a == 1;
+            }
+            if (__ballot(sol)) { // rare in a reverse pass
+                any_solid = true;
+                if (sol) {
+                    const uint32_t tag = q[count - cnt + (uint32_t)ln].w; // (read again: not kept across the probe)
+                    atomicOr(ans + (tag >> 6), 1ull << (tag & 63u));
+                }
+            }
+            count -= cnt;
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+
+    // ---- the trigger test over the block's answer words (mod.rs:73, 99) -------------------------------------------
+    uint32_t t = 0;
+    if (!any_solid) {
+        // no solid k-mer in the block (nearly always): only `previous` can trigger, at the block's first position
+        t = prev ? 0u : (uint32_t)REV_BLOCK;
+    } else {
+        bool pv = prev;
+        for (; t < (uint32_t)REV_BLOCK; t++) {
+            const uint64_t bs = uni64(ans[t]);
+            if (~bs & ((bs << 1) | (pv ? 1ull : 0ull)))
+                break;
+            pv = (bs >> 63) & 1ull;
+        }
+        if (t)
+            prev = pv;
+    }
+    if (t)
+        kmer = uni64(carry[t - 1u]);
+    __builtin_amdgcn_wave_barrier();
+    return t;
+}
 #endif
 
 struct LanePassInfo {

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Builds a variant of libbrx.so with extra compiler flags for a same-box A/B:
 #   tools/ab_build.sh NAME "-DBRX_XCD_ITEMS=0"   ->  br_amd/lib/ab/libbrx_NAME.so   (git-ignored, travels with gpurun)
+# (round 8: -DBRX_REV_BLOCK=2 / 4 / 8, the rounds per block of the reverse scans; -DBRX_ONE64_WAVES=6 / 7 / 8)
 # and is picked up with BRX_LIB_PATH=br_amd/lib/ab/libbrx_NAME.so python bench.py ...
 # Different GPU boxes of the pool differ by up to ~10 % on the same code, so variants are compared inside one call.
 set -e
@@ -8,7 +9,7 @@ cd "$(dirname "$0")/../br_amd/csrc"
 name=$1; shift
 bdir=build_ab_$name
 mkdir -p $bdir ../lib/ab
-srcs="brx_api brx_set brx_index brx_partbuild brx_scan brx_correct brx_onelane brx_strand brx_cover brx_pipeline brx_synth brx_exchange brx_devpool"
+srcs="brx_api brx_set brx_index brx_partbuild brx_counttable brx_scan brx_correct brx_onelane brx_strand brx_cover brx_pipeline brx_synth brx_exchange brx_devpool"
 pids=()
 for f in $srcs; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 "$@" -c $f.hip -o $bdir/$f.o &

@@ -110,6 +110,7 @@ def report_mismatch(desc, case, seed, gs, ref, names, c, ms, two_side, reads, go
         rep["reruns"]["lane_mask_off"] = differing(run_chain(gs, names, c, ms, two_side, reads, {"BRX_LANE_MASK": "0"}))
         rep["reruns"]["lane_walk_off"] = differing(run_chain(gs, names, c, ms, two_side, reads, {"BRX_LANE_WALK": "0"}))
         rep["reruns"]["rev_lean_off"] = differing(run_chain(gs, names, c, ms, two_side, reads, {"BRX_REV_LEAN": "0"}))
+        rep["reruns"]["rev_batch_off"] = differing(run_chain(gs, names, c, ms, two_side, reads, {"BRX_REV_BATCH": "0"}))
         gs2 = rebuild()
         rep["reruns"]["fresh_set_popcount"] = [int(gs2.popcount()), int(ref.popcount())]
         rep["reruns"]["same_settings_fresh_set"] = differing(run_chain(gs2, names, c, ms, two_side, reads))
@@ -185,6 +186,8 @@ while time.time() < t_end:
     # that every block loops over many reads of the job
     env["BRX_AP_GRID"] = str(xrng.choice(["", "1", "5"]))
     env["BRX_READ_GRID"] = str(xrng.choice(["", "1", "5"]))
+    # trigger-free rounds of the 64-lane reverse scans in blocks through the occupancy bits (round 8): on (default) / off
+    env["BRX_REV_BATCH"] = str(xrng.choice(["", "", "", "0"]))
     if focus == "walklane":
         names[-1] = str(frng.choice(["graph", "gap_size"]))
         env.update({"BRX_LANE": "", "BRX_LANE_WALK": "", "BRX_LANE_CHUNK": str(frng.choice(["64", "100"])),
