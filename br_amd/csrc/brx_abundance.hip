@@ -1,0 +1,346 @@
+// K-mer abundance of reads: how often the k-mers of a batch were counted.  No counterpart in the reference.
+//
+// For a read s of n bases and a counter of k-mer length k (include/brx.h, "abundance"):
+//   count[i] = the counter's value for the canonical k-mer of s[i..i+k), 0 <= i <= n-k: min(255, occurrences), 0 if never
+//              counted (every byte coded by nuc2bit, so a byte that is not ACGT is a base like any other),
+//   profile  = one byte per base, count[i] at base i, 0 at the last k-1 bases,
+//   hist[v]  = number of i with count[i] == v (256 u32 per read),
+//   stats    = kmers, absent = hist[0], above = #(count > abundance), min, lower median, max, sum.
+//
+// One lookup per k-mer of the batch, asked the way cover_kernel (brx_cover.hip) asks: the batch is cut BY POSITION into a
+// work list of tiles (read, first position) built from the offsets, a wave takes a tile of ABUND_TILE positions and walks
+// it 64 neighbouring positions per step, so that neighbours share their table lines.  The k-mers come from the DPP scan
+// of brx_correct.hpp, indexed by their LAST base e: count[e-k+1].  A tile needs no look-behind (nothing is carried from
+// position to position but the k-mer itself): it starts its scan at its first base with an empty carry, skips the k-1
+// incomplete k-mers that gives, and reads k-1 bases past its end for the k-mers that start inside it.
+//   table counter  table_lookup_slot (brx_index.hpp): the walk of index_probe_at over the counting table's lines -- whole
+//                  line in vector loads, chain followed only while the flag (and at the home line the signature bit)
+//                  says so -- then one 4-byte load of the slot's counter, read as min(255, .).
+//   dense counter  byte khash(kmer) of the u8 table.
+// A wave bins its counts into a 256-bin histogram of its own in LDS (one LDS atomic per position) and afterwards adds
+// the bins that are not zero to the read's row in global memory: integer atomic adds, so nothing depends on the launch
+// geometry or on timing.  abund_stats_kernel, a wave per read, turns the 256 bins into the statistics: a prefix sum over
+// the bins finds the median, no sort and no floating point.  The rows are the caller's d_hist, or scratch from the pool.
+#include "brx_correct.hpp"
+
+using namespace brx;
+
+namespace brx {
+uint64_t scan_tmp_bytes(uint32_t n);
+int exclusive_scan_lens(const uint32_t *d_lens, uint32_t n, uint64_t *d_tmp, uint64_t *d_out_offsets,
+                        unsigned long long *d_total, hipStream_t s);
+}
+
+namespace {
+
+constexpr uint32_t ABUND_TILE = 1024; // positions of a read per wave: 16 steps of 64, a 17th for the k-1 bases behind them
+
+enum { SRC_NONE = 0, SRC_DENSE = 1, SRC_TABLE = 2 }; // what answers: nothing counted yet, the u8 table, the counting table
+
+struct AbundArgs {
+    // the counter
+    const uint8_t *dense;   // u8 per canonical hash
+    const uint64_t *lines;  // counting table
+    const uint32_t *counts; // its counters, counts[line * 8 + slot]
+    uint32_t line_shift, m, w;
+    int k;
+    uint32_t abundance;
+    // the batch
+    uint32_t n_reads;
+    const uint8_t *bases;
+    const uint64_t *offsets;
+    // work list
+    uint32_t *tiles_of;          // tiles per read              [n_reads]
+    uint64_t *tile_base;         // exclusive scan of tiles_of  [n_reads + 1]
+    uint32_t *tile_read;         // read of a tile              [tiles]
+    unsigned long long *n_tiles; // = tile_base[n_reads]
+    // outputs, each may be null
+    uint8_t *profile;
+    uint32_t *hist; // 256 per read
+    brx_abund_stats_t *stats;
+};
+
+__global__ __launch_bounds__(256) void abund_tiles_of_kernel(AbundArgs a)
+{
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= a.n_reads)
+        return;
+    const uint64_t n = a.offsets[r + 1] - a.offsets[r];
+    a.tiles_of[r] = (uint32_t)((n + ABUND_TILE - 1u) / ABUND_TILE);
+}
+
+__global__ __launch_bounds__(256) void abund_tile_list_kernel(AbundArgs a)
+{
+    for (uint32_t r = blockIdx.x; r < a.n_reads; r += gridDim.x) {
+        const uint64_t tb = a.tile_base[r], te = a.tile_base[r + 1];
+        for (uint64_t t = tb + threadIdx.x; t < te; t += 256)
+            a.tile_read[t] = r;
+    }
+}
+
+// the counter's value for one forward k-mer
+template <int SRC>
+__device__ __forceinline__ uint32_t abund_count(const AbundArgs &a, uint64_t km)
+{
+    if (SRC == SRC_NONE)
+        return 0u;
+    if (SRC == SRC_DENSE)
+        return a.dense[khash(km, a.k)];
+    const uint64_t rc = revcomp(km, a.k);
+    const uint64_t key = (((popc64(km) & 1) ? rc : km) >> 1) + 1ull;
+    const uint32_t home = index_line_of(minimizer_of(km, rc, a.m, a.w), a.line_shift);
+    const uint64_t slot = table_lookup_slot(a.lines, a.line_shift, key, home);
+    return slot == TAB_NO_SLOT ? 0u : table_count_read(a.counts[slot]);
+}
+
+// A wave per tile.
+template <int SRC>
+__global__ __launch_bounds__(256) void abund_kernel(AbundArgs a)
+{
+    __shared__ uint32_t bins[4][256];
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned long long tile = (unsigned long long)blockIdx.x * 4ull + wv;
+    if (tile >= *a.n_tiles)
+        return;
+    const uint32_t r = a.tile_read[tile];
+    const uint64_t o0 = a.offsets[r];
+    const uint32_t n = (uint32_t)(a.offsets[r + 1] - o0);
+    const uint32_t p0 = (uint32_t)(tile - a.tile_base[r]) * ABUND_TILE;
+    const uint32_t p1 = n - p0 < ABUND_TILE ? n : p0 + ABUND_TILE;
+    const int lane = threadIdx.x & 63;
+    const uint32_t k = (uint32_t)a.k;
+    const uint64_t mask = kmask(a.k);
+    const uint8_t *in = a.bases + o0;
+    uint32_t *const h = bins[wv];
+    if (a.hist) {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            h[64 * j + lane] = 0u;
+        __builtin_amdgcn_wave_barrier();
+    }
+    // the k-mers wanted START at p0 .. istop-1 and END at p0+k-1 .. elim-1; the scan begins at base p0
+    const uint32_t nk = n >= k ? n - k + 1u : 0u;  // k-mers of the read
+    const uint32_t istop = p1 < nk ? p1 : nk;      // first start position that is not this tile's (or is no k-mer)
+    const uint32_t elim = istop > p0 ? istop + k - 1u : p0; // (<= n)
+    uint64_t carry = 0;
+    for (uint32_t eb = p0; eb < elim; eb += 64u) {
+        const uint32_t e = eb + (uint32_t)lane;
+        const uint8_t c = e < elim ? in[e] : (uint8_t)0;
+        const uint64_t km = lane_kmer64_dpp(carry, (c >> 1) & 3u, lane, mask);
+        carry = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(km >> 32), 63) << 32) |
+                (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)km, 63);
+        if (e < elim && e - p0 + 1u >= k) { // the k-mer is whole: it starts at e-k+1 >= p0
+            const uint32_t cnt = abund_count<SRC>(a, km);
+            if (a.profile)
+                a.profile[o0 + (e + 1u - k)] = (uint8_t)cnt;
+            if (a.hist)
+                atomicAdd(&h[cnt], 1u);
+        }
+    }
+    // the bases of the tile where no k-mer starts: the last k-1 of the read (all of a read shorter than k)
+    if (a.profile) {
+        const uint32_t z0 = istop > p0 ? istop : p0; // z0 .. p1-1: fewer than k <= 31 bases
+        if (z0 + (uint32_t)lane < p1)
+            a.profile[o0 + z0 + (uint32_t)lane] = 0;
+    }
+    if (a.hist) {
+        __builtin_amdgcn_wave_barrier();
+        uint32_t *row = a.hist + (uint64_t)r * 256ull;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t v = h[64 * j + lane];
+            if (v)
+                atomicAdd(row + 64 * j + lane, v);
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t wave_sum32(uint32_t v)
+{
+    for (int d = 32; d > 0; d >>= 1)
+        v += (uint32_t)__shfl_xor((int)v, d);
+    return v;
+}
+
+// A wave per read: lane l holds bins 4l .. 4l+3.
+__global__ __launch_bounds__(256) void abund_stats_kernel(AbundArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    for (uint32_t r = blockIdx.x * 4u + wv; r < a.n_reads; r += gridDim.x * 4u) {
+        const uint32_t *row = a.hist + (uint64_t)r * 256ull + 4u * lane; // (a caller's rows need no more than their own alignment)
+        const uint32_t b[4] = {row[0], row[1], row[2], row[3]};
+        const uint32_t mine = b[0] + b[1] + b[2] + b[3]; // (a read holds fewer than 2^32 k-mers)
+        // inclusive prefix sum of `mine` over the lanes
+        uint32_t incl = mine;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
+            if ((int)lane >= d)
+                incl += up;
+        }
+        const uint32_t kmers = (uint32_t)__shfl((int)incl, 63);
+        uint32_t above = 0;
+        unsigned long long sum = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            const uint32_t v = 4u * lane + j;
+            above += v > a.abundance ? b[j] : 0u;
+            sum += (unsigned long long)v * b[j];
+        }
+        above = wave_sum32(above);
+        for (int d = 32; d > 0; d >>= 1)
+            sum += (unsigned long long)__shfl_xor((long long)sum, d);
+        uint32_t vmin = 0, vmax = 0, vmed = 0;
+        if (kmers) { // wave-uniform
+            const uint64_t has = __ballot(mine != 0u);
+            const uint32_t lo = (uint32_t)__ffsll((unsigned long long)has) - 1u, hi = 63u - (uint32_t)__clzll((long long)has);
+            const uint32_t first = b[0] ? 0u : (b[1] ? 1u : (b[2] ? 2u : 3u)), last = b[3] ? 3u : (b[2] ? 2u : (b[1] ? 1u : 0u));
+            vmin = (uint32_t)__shfl((int)(4u * lane + first), (int)lo);
+            vmax = (uint32_t)__shfl((int)(4u * lane + last), (int)hi);
+            // element (kmers-1)/2 of the sorted counts: the smallest v whose bins 0..v hold more than that many
+            const uint32_t target = (kmers - 1u) / 2u;
+            uint32_t run = incl - mine, med = 0;
+            bool found = false;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) {
+                run += b[j];
+                if (!found && run > target) {
+                    found = true;
+                    med = 4u * lane + j;
+                }
+            }
+            const uint64_t fm = __ballot(found);
+            vmed = (uint32_t)__shfl((int)med, (int)((uint32_t)__ffsll((unsigned long long)fm) - 1u));
+        }
+        if (lane == 0u) {
+            brx_abund_stats_t st;
+            st.kmers = kmers;
+            st.absent = kmers ? b[0] : 0u;
+            st.above = above;
+            st.min = vmin;
+            st.median = vmed;
+            st.max = vmax;
+            st.sum = sum;
+            a.stats[r] = st;
+        }
+    }
+}
+
+template <int SRC>
+__global__ __launch_bounds__(256) void abund_get_kernel(AbundArgs a, const uint64_t *__restrict__ kmers, uint32_t n, uint8_t *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n)
+        out[i] = (uint8_t)abund_count<SRC>(a, kmers[i] & kmask(a.k));
+}
+
+// how the kernels reach the counter; the table's pointers are read here, i.e. inside the caller's lock
+int abund_view(const brx_counter *c, const char *what, AbundArgs &a, int &src)
+{
+    a.k = c->k;
+    if (c->strategy == BRX_COUNT_DENSE) {
+        a.dense = reinterpret_cast<const uint8_t *>(c->d_counts);
+        src = SRC_DENSE;
+        return BRX_OK;
+    }
+    if (c->strategy == BRX_COUNT_TABLE) {
+        uint32_t log_lines = 0;
+        tab_view(c, &a.lines, &a.counts, &log_lines, &a.m);
+        src = a.lines ? SRC_TABLE : SRC_NONE;
+        if (a.lines) {
+            a.line_shift = 32u - log_lines;
+            a.w = (uint32_t)c->k - a.m + 1u;
+        }
+        return BRX_OK;
+    }
+    set_error("%s: the counter (strategy %d) holds no counts to look up", what, c->strategy); // (the entries refuse it before)
+    return BRX_ERR_UNSUPPORTED;
+}
+
+int abund_enqueue(const brx_counter *c, AbundArgs &a, uint64_t total_bases, DevScratch &sc, hipStream_t s)
+{
+    int src = SRC_NONE;
+    BRX_TRY(abund_view(c, "abundance", a, src));
+    const uint32_t n_reads = a.n_reads;
+    const uint64_t tile_bound = total_bases / ABUND_TILE + n_reads;
+    if (tile_bound / 4ull + 1ull > 0x7fffffffull) {
+        set_error("abundance: batch of %llu bases in %u reads is too large for one call", (unsigned long long)total_bases, n_reads);
+        return BRX_ERR_ARG;
+    }
+    uint64_t *tmp = nullptr;
+    BRX_TRY(sc.get(&a.tiles_of, n_reads));
+    BRX_TRY(sc.get(&a.tile_base, (uint64_t)n_reads + 1));
+    BRX_TRY(sc.get(&a.tile_read, tile_bound));
+    BRX_TRY(sc.get(&a.n_tiles, 1));
+    BRX_TRY(sc.get(&tmp, scan_tmp_bytes(n_reads) / 8 + 1));
+    if (a.stats && !a.hist)
+        BRX_TRY(sc.get(&a.hist, (uint64_t)n_reads * 256ull));
+    if (a.hist)
+        BRX_HIP(hipMemsetAsync(a.hist, 0, (uint64_t)n_reads * 1024ull, s));
+    {
+        KernelTimer t("abund_tiles", s);
+        abund_tiles_of_kernel<<<(n_reads + 255u) / 256u, 256, 0, s>>>(a);
+        BRX_TRY(exclusive_scan_lens(a.tiles_of, n_reads, tmp, a.tile_base, a.n_tiles, s));
+        abund_tile_list_kernel<<<read_grid(n_reads, 2048u), 256, 0, s>>>(a);
+    }
+    {
+        KernelTimer t("abund", s);
+        const uint32_t grid = (uint32_t)((tile_bound + 3ull) / 4ull);
+        if (src == SRC_TABLE)
+            abund_kernel<SRC_TABLE><<<grid, 256, 0, s>>>(a);
+        else if (src == SRC_DENSE)
+            abund_kernel<SRC_DENSE><<<grid, 256, 0, s>>>(a);
+        else
+            abund_kernel<SRC_NONE><<<grid, 256, 0, s>>>(a);
+    }
+    if (a.stats) {
+        KernelTimer t("abund_stats", s);
+        abund_stats_kernel<<<read_grid(((uint64_t)n_reads + 3ull) / 4ull, 4096u), 256, 0, s>>>(a);
+    }
+    BRX_HIP(hipGetLastError());
+    return BRX_OK;
+}
+
+} // namespace
+
+namespace brx {
+
+int abund_batch(const brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
+                uint8_t abundance, uint8_t *d_profile, uint32_t *d_hist, brx_abund_stats_t *d_stats, hipStream_t s)
+{
+    DevScratch sc;
+    AbundArgs a{};
+    a.abundance = abundance;
+    a.n_reads = n_reads;
+    a.bases = d_bases;
+    a.offsets = d_offsets;
+    a.profile = d_profile;
+    a.hist = d_hist;
+    a.stats = d_stats;
+    int st = abund_enqueue(c, a, total_bases, sc, s);
+    // the scratch goes back to the pool when this returns: nothing of the call may still be running then
+    const hipError_t e = hipStreamSynchronize(s);
+    if (st == BRX_OK && e != hipSuccess) {
+        set_error("abundance: %s", hipGetErrorString(e));
+        st = BRX_ERR_HIP;
+    }
+    return st;
+}
+
+int abund_get_counts(const brx_counter *c, const uint64_t *d_kmers, uint32_t n, uint8_t *d_out, hipStream_t s)
+{
+    AbundArgs a{};
+    int src = SRC_NONE;
+    BRX_TRY(abund_view(c, "get_counts", a, src));
+    const uint32_t grid = (n + 255u) / 256u;
+    if (src == SRC_TABLE)
+        abund_get_kernel<SRC_TABLE><<<grid, 256, 0, s>>>(a, d_kmers, n, d_out);
+    else if (src == SRC_DENSE)
+        abund_get_kernel<SRC_DENSE><<<grid, 256, 0, s>>>(a, d_kmers, n, d_out);
+    else
+        abund_get_kernel<SRC_NONE><<<grid, 256, 0, s>>>(a, d_kmers, n, d_out);
+    BRX_HIP(hipGetLastError());
+    return BRX_OK;
+}
+
+} // namespace brx

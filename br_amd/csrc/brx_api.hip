@@ -1,4 +1,4 @@
-// Diagnostics, device selection and the per-kernel event timers of libbrx.so.
+// Diagnostics, device selection and the per-kernel event timers of libbrx.so; the C entries of the abundance calls.
 #include "brx_internal.hpp"
 
 #include <stdio.h>
@@ -309,6 +309,145 @@ int brx_profile_names(char *buf, size_t cap)
     }
     snprintf(buf, cap, "%s", s.c_str());
     return BRX_OK;
+}
+
+// ---- abundance (include/brx.h "abundance"; the kernels are in brx_abundance.hip) ---------------------------------------
+static int abund_check(const char *what, const brx_counter_t *c, const void *bases, const uint64_t *offsets, uint32_t n_reads,
+                       uint64_t total_bases)
+{
+    if (!c) {
+        set_error("%s: null counter", what);
+        return BRX_ERR_ARG;
+    }
+    if (c->strategy == BRX_COUNT_SORTED) {
+        set_error("%s: a partitioned counter (BRX_COUNT_SORTED) holds sorted keys, no counts to look up; count with BRX_COUNT_TABLE "
+                  "for an abundance profile at k=%d", what, c->k);
+        return BRX_ERR_UNSUPPORTED;
+    }
+    if ((n_reads && !offsets) || (total_bases && !bases)) {
+        set_error("%s: null bases / offsets for %u reads, %llu bases", what, n_reads, (unsigned long long)total_bases);
+        return BRX_ERR_ARG;
+    }
+    if (total_bases && !n_reads) {
+        set_error("%s: %llu bases in no reads", what, (unsigned long long)total_bases);
+        return BRX_ERR_ARG;
+    }
+    return BRX_OK;
+}
+
+// the body of both batch entries; the caller holds c->mu
+static int abund_batch_locked(brx_counter_t *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
+                              uint8_t abundance, uint8_t *d_profile, uint32_t *d_hist, brx_abund_stats_t *d_stats, hipStream_t s)
+{
+    if (!n_reads || (!d_profile && !d_hist && !d_stats))
+        return BRX_OK;
+    if (!total_bases) { // reads without bases: no k-mers, and no kernel
+        if (d_hist)
+            BRX_HIP(hipMemsetAsync(d_hist, 0, (uint64_t)n_reads * 1024ull, s));
+        if (d_stats)
+            BRX_HIP(hipMemsetAsync(d_stats, 0, (uint64_t)n_reads * sizeof(brx_abund_stats_t), s));
+        BRX_HIP(hipStreamSynchronize(s));
+        return BRX_OK;
+    }
+    return abund_batch(c, d_bases, d_offsets, n_reads, total_bases, abundance, d_profile, d_hist, d_stats, s);
+}
+
+int brx_counter_abundance_batch_device(brx_counter_t *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads,
+                                       uint64_t total_bases, uint8_t abundance, uint8_t *d_profile, uint32_t *d_hist,
+                                       brx_abund_stats_t *d_stats, void *stream)
+{
+    BRX_TRY(abund_check("brx_counter_abundance_batch_device", c, d_bases, d_offsets, n_reads, total_bases));
+    BRX_TRY(use_device(c->device));
+    std::lock_guard<std::mutex> g(c->mu);
+    return abund_batch_locked(c, d_bases, d_offsets, n_reads, total_bases, abundance, d_profile, d_hist, d_stats, (hipStream_t)stream);
+}
+
+int brx_counter_abundance_batch(brx_counter_t *c, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                                uint8_t abundance, uint8_t *profile, uint32_t *hist, brx_abund_stats_t *stats)
+{
+    const char *me = "brx_counter_abundance_batch";
+    if (n_reads && !offsets) {
+        set_error("%s: null offsets", me);
+        return BRX_ERR_ARG;
+    }
+    const uint64_t total = n_reads ? offsets[n_reads] : 0;
+    BRX_TRY(abund_check(me, c, bases, offsets, n_reads, total));
+    for (uint32_t r = 0; r < n_reads; r++)
+        if (offsets[r + 1] < offsets[r] || offsets[r + 1] - offsets[r] > 0xfffffff0ull || (r == 0 && offsets[0] != 0)) {
+            set_error("%s: offsets must start at 0 and not decrease; a read holds fewer than 2^32 - 16 bases (read %u)", me, r);
+            return BRX_ERR_ARG;
+        }
+    BRX_TRY(use_device(c->device));
+    if (!n_reads || (!profile && !hist && !stats))
+        return BRX_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    DevScratch sc;
+    uint8_t *d_bases = nullptr, *d_profile = nullptr;
+    uint64_t *d_off = nullptr;
+    uint32_t *d_hist = nullptr;
+    brx_abund_stats_t *d_stats = nullptr;
+    BRX_TRY(sc.get(&d_bases, total));
+    BRX_TRY(sc.get(&d_off, (uint64_t)n_reads + 1));
+    if (profile)
+        BRX_TRY(sc.get(&d_profile, total));
+    if (hist)
+        BRX_TRY(sc.get(&d_hist, (uint64_t)n_reads * 256ull));
+    if (stats)
+        BRX_TRY(sc.get(&d_stats, n_reads));
+    hipStream_t s = c->stream;
+    auto run = [&]() -> int {
+        if (total)
+            BRX_HIP(hipMemcpyAsync(d_bases, bases, total, hipMemcpyHostToDevice, s));
+        BRX_HIP(hipMemcpyAsync(d_off, offsets, ((uint64_t)n_reads + 1) * 8, hipMemcpyHostToDevice, s));
+        BRX_TRY(abund_batch_locked(c, d_bases, d_off, n_reads, total, abundance, d_profile, d_hist, d_stats, s));
+        if (profile && total)
+            BRX_HIP(hipMemcpyAsync(profile, d_profile, total, hipMemcpyDeviceToHost, s));
+        if (hist)
+            BRX_HIP(hipMemcpyAsync(hist, d_hist, (uint64_t)n_reads * 1024ull, hipMemcpyDeviceToHost, s));
+        if (stats)
+            BRX_HIP(hipMemcpyAsync(stats, d_stats, (uint64_t)n_reads * sizeof(brx_abund_stats_t), hipMemcpyDeviceToHost, s));
+        return BRX_OK;
+    };
+    const int st = run();
+    const hipError_t e = hipStreamSynchronize(s); // the blocks are freed below: nothing may still be running
+    if (st == BRX_OK && e != hipSuccess) {
+        set_error("%s: %s", me, hipGetErrorString(e));
+        return BRX_ERR_HIP;
+    }
+    return st;
+}
+
+int brx_counter_get_counts(brx_counter_t *c, const uint64_t *forward_kmers, uint32_t n, uint8_t *out)
+{
+    const char *me = "brx_counter_get_counts";
+    BRX_TRY(abund_check(me, c, nullptr, nullptr, 0, 0));
+    if ((!forward_kmers || !out) && n) {
+        set_error("%s: null k-mers / out", me);
+        return BRX_ERR_ARG;
+    }
+    BRX_TRY(use_device(c->device));
+    if (!n)
+        return BRX_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    DevScratch sc;
+    uint64_t *d_k = nullptr;
+    uint8_t *d_o = nullptr;
+    BRX_TRY(sc.get(&d_k, n));
+    BRX_TRY(sc.get(&d_o, n));
+    hipStream_t s = c->stream;
+    auto run = [&]() -> int {
+        BRX_HIP(hipMemcpyAsync(d_k, forward_kmers, (uint64_t)n * 8, hipMemcpyHostToDevice, s));
+        BRX_TRY(abund_get_counts(c, d_k, n, d_o, s));
+        BRX_HIP(hipMemcpyAsync(out, d_o, n, hipMemcpyDeviceToHost, s));
+        return BRX_OK;
+    };
+    const int st = run();
+    const hipError_t e = hipStreamSynchronize(s);
+    if (st == BRX_OK && e != hipSuccess) {
+        set_error("%s: %s", me, hipGetErrorString(e));
+        return BRX_ERR_HIP;
+    }
+    return st;
 }
 
 void brx_buf_free(void *p) { brx::host_buf_release(p); }

@@ -319,6 +319,16 @@ int tab_spectrum(brx_counter *c, hipStream_t s, unsigned long long *d_hist)
     return BRX_OK;
 }
 
+// what a read-only lookup needs (brx_abundance.hip); lines == nullptr: nothing counted yet
+void tab_view(const brx_counter *c, const uint64_t **lines, const uint32_t **counts, uint32_t *log_lines, uint32_t *m)
+{
+    const TabState *t = c->tab;
+    *lines = t->d_lines;
+    *counts = t->d_counts;
+    *log_lines = t->log_lines;
+    *m = t->m;
+}
+
 int tab_info(brx_counter *c, uint64_t *info4, hipStream_t s)
 {
     TabState *t = c->tab;

@@ -286,6 +286,31 @@ __device__ __forceinline__ uint64_t table_find_or_claim(uint64_t *lines, uint32_
     }
 }
 
+// Read-only twin of table_find_or_claim (brx_abundance.hip): the index of the slot that holds `key`, or TAB_NO_SLOT.  The
+// walk of index_probe_at: the whole line in four 16-byte loads, the seven slots compared with `|`; a miss goes on to the
+// next line only while the line is flagged, and at the home line only if one of the keys it turned away had this key's
+// signature.  Never more lines than the table has, so a damaged table cannot keep a wave here for ever.  Plain loads:
+// nothing counts while this runs (the counter's lock and the stream's order see to that).
+constexpr uint64_t TAB_NO_SLOT = ~0ull;
+__device__ __forceinline__ uint64_t table_lookup_slot(const uint64_t *__restrict__ lines, uint32_t line_shift, uint64_t key, uint32_t home)
+{
+    const uint32_t line_mask = 0xffffffffu >> line_shift;
+    for (uint32_t hop = 0;; hop++) {
+        const uint32_t line = (home + hop) & line_mask;
+        const ulonglong2 *L = reinterpret_cast<const ulonglong2 *>(lines + (uint64_t)line * 8ull);
+        const ulonglong2 q0 = L[0], q1 = L[1], q2 = L[2], q3 = L[3];
+        const uint32_t hit = (uint32_t)(q0.x == key) | ((uint32_t)(q0.y == key) << 1) | ((uint32_t)(q1.x == key) << 2) |
+                             ((uint32_t)(q1.y == key) << 3) | ((uint32_t)(q2.x == key) << 4) | ((uint32_t)(q2.y == key) << 5) |
+                             ((uint32_t)(q3.x == key) << 6);
+        if (hit)
+            return (uint64_t)line * 8ull + (uint64_t)(__ffs((int)hit) - 1);
+        const uint32_t hdr_hi = (uint32_t)(q3.y >> 32);
+        const bool more = (hdr_hi >> 31) && (hop != 0u || ((hdr_hi >> idx_sig_index(key)) & 1u));
+        if (!more || hop == line_mask)
+            return TAB_NO_SLOT;
+    }
+}
+
 constexpr uint32_t TAB_COUNT_MAX = 255u; // what a counter is read as at most (pcon's Counter<u8>)
 // One more occurrence.  A counter that has reached 255 is left alone, so it stands for min(255, occurrences) however
 // long the input: lanes that all saw 254 may each add their one, which leaves it above 255 by less than the number of

@@ -172,6 +172,16 @@ struct brx_counter {
     std::mutex mu;
 };
 
+namespace brx {
+// counting table of a BRX_COUNT_TABLE counter as a read-only lookup sees it (brx_counttable.hip)
+void tab_view(const brx_counter *c, const uint64_t **lines, const uint32_t **counts, uint32_t *log_lines, uint32_t *m);
+// k-mer abundance of reads (brx_abundance.hip); the callers (brx_api.hip) hold the counter's lock.  abund_batch enqueues on
+// `s` and returns after its kernels have completed
+int abund_batch(const brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
+                uint8_t abundance, uint8_t *d_profile, uint32_t *d_hist, brx_abund_stats_t *d_stats, hipStream_t s);
+int abund_get_counts(const brx_counter *c, const uint64_t *d_kmers, uint32_t n, uint8_t *d_out, hipStream_t s);
+}
+
 struct brx_chain {
     const brx_set *set;
     int device;
@@ -223,3 +233,24 @@ struct brx_chain {
 // The library's device memory comes from the block pool (brx_devpool.hip, which does not include this header).
 #define hipMalloc(ptr, bytes) brx::dev_alloc((void **)(ptr), (bytes))
 #define hipFree(ptr) brx::dev_free((void *)(ptr))
+
+namespace brx {
+// device blocks of one call, from the block pool; released when the call returns
+struct DevScratch {
+    std::vector<void *> blocks;
+    ~DevScratch()
+    {
+        for (void *p : blocks)
+            (void)hipFree(p);
+    }
+    template <typename T>
+    int get(T **out, uint64_t n)
+    {
+        void *p = nullptr;
+        BRX_HIP(hipMalloc(&p, (n ? n : 1) * sizeof(T)));
+        blocks.push_back(p);
+        *out = (T *)p;
+        return BRX_OK;
+    }
+};
+}

@@ -393,6 +393,46 @@ class Counter:
     def reset(self, stream: Optional[int] = None) -> None:
         _lib.check(_lib.lib().brx_counter_reset(self._h, stream))
 
+    # ---- abundance (include/brx.h "abundance", br_amd/abundance.py: no counterpart in the reference) ----
+    def abundance_batch(self, bases: np.ndarray, offsets: np.ndarray, abundance: int = 0, profile: bool = True,
+                        hist: bool = False):
+        """(profile uint8[total] | None, hist uint32[n, 256] | None, stats abundance.STATS_DTYPE[n]) of a bases / offsets
+        batch: the count of the k-mer that starts at every base, on the GPU (brx_counter_abundance_batch).  Dense and
+        table counters; the counter is left as it was."""
+        from . import abundance as ab
+        _check_u8(abundance, "abundance")
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        pr = np.zeros(bases.size, dtype=np.uint8) if profile else None
+        hi = np.zeros((n, 256), dtype=np.uint32) if hist else None
+        st = np.zeros(n, dtype=ab.STATS_DTYPE)
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        _lib.check(_lib.lib().brx_counter_abundance_batch(self._h, bases.ctypes.data, offsets.ctypes.data, n, abundance,
+                                                          ptr(pr), ptr(hi), ptr(st)))
+        return pr, hi, st
+
+    def abundance_batch_device(self, d_bases: int, d_offsets: int, n_reads: int, total_bases: int, abundance: int = 0,
+                               d_profile: Optional[int] = None, d_hist: Optional[int] = None, d_stats: Optional[int] = None,
+                               stream: Optional[int] = None) -> None:
+        _check_u8(abundance, "abundance")
+        _lib.check(_lib.lib().brx_counter_abundance_batch_device(self._h, d_bases, d_offsets, n_reads, total_bases, abundance,
+                                                                 d_profile, d_hist, d_stats, stream))
+
+    def abundance_reads(self, reads: Sequence[bytes], abundance: int = 0):
+        """(list of per-read uint8 arrays of length kmers, stats array) of `reads`"""
+        from . import abundance as ab
+        bases, offs = pack_reads(reads)
+        pr, _, st = self.abundance_batch(bases, offs, abundance)
+        return ab.unpack_profile(pr, offs, self.k), st
+
+    def get_counts(self, kmers: Sequence[int]) -> np.ndarray:
+        """uint8 count of every forward k-mer (of its canonical form): Pcon.get_many's twin on a counter"""
+        km = np.ascontiguousarray(np.asarray(kmers, dtype=np.uint64))
+        out = np.zeros(km.size, dtype=np.uint8)
+        _lib.check(_lib.lib().brx_counter_get_counts(self._h, km.ctypes.data, km.size, out.ctypes.data))
+        return out
+
     def finish_into(self, abundance: int, dst: "Pcon", stream: Optional[int] = None) -> None:
         _check_u8(abundance, "abundance")
         _lib.check(_lib.lib().brx_set_count_finish_into(self._h, abundance, stream, dst._h))

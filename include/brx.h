@@ -251,6 +251,43 @@ int brx_counter_add_partitioned_device(brx_counter_t *c, const uint32_t *d_keys,
 int brx_counter_table_info(brx_counter_t *c, uint64_t *info4, void *stream);
 void brx_counter_free(brx_counter_t *c);
 
+/* ---- abundance: how often the k-mers of a read were counted.  No counterpart in the reference ---------------------
+ * For a read s of n bytes and a counter of k-mer length k:
+ *   count[i], 0 <= i <= n-k, is the counter's value for the canonical k-mer of s[i..i+k): min(255, occurrences counted so
+ *     far), 0 if the k-mer was never counted.  Every byte is coded as nuc2bit codes it -- a byte that is not ACGT is a
+ *     base like any other, lower case equals upper case; n < k gives no k-mers;
+ *   the PROFILE is one byte per base, laid out like `bases`: byte i of a read is count[i], the last k-1 bytes of a read
+ *     (all bytes of a read shorter than k) are 0;
+ *   the HISTOGRAM is 256 u32 per read: hist[v] = number of i with count[i] == v;
+ *   the STATISTICS are brx_abund_stats_t, all fields 0 when kmers == 0.
+ * Integer arithmetic throughout: no result depends on the launch geometry or on timing.  One lookup per k-mer of the
+ * batch, 64 neighbouring positions per wave step, the batch cut by position like a cover call.  Dense (BRX_COUNT_DENSE)
+ * and table (BRX_COUNT_TABLE) counters are served; a partitioned one (BRX_COUNT_SORTED) holds sorted keys, no counts
+ * that could be looked up, and returns BRX_ERR_UNSUPPORTED.  A table counter that has counted nothing answers zeros.
+ * The calls take the counter's lock, see everything added before them (also after the table has regrown) and leave
+ * the counter as it was: brx_counter_spectrum and brx_set_count_finish with any threshold still follow.
+ * A read holds fewer than 2^32 - 16 bases.                                                                             */
+typedef struct brx_abund_stats {
+    uint32_t kmers;  /* max(n-k+1, 0)                                                            */
+    uint32_t absent; /* hist[0]                                                                  */
+    uint32_t above;  /* number of i with count[i] > abundance (strict, as in brx_set_count_finish) */
+    uint32_t min;    /* of count[]                                                               */
+    uint32_t median; /* the lower median: element (kmers-1)/2 of the sorted counts               */
+    uint32_t max;
+    uint64_t sum;    /* of count[]                                                               */
+} brx_abund_stats_t;
+/* d_profile: one byte per base; d_hist: n_reads rows of 256 u32; d_stats: n_reads entries.  Any of the three may be
+ * NULL.  The work is enqueued on `stream`; the call returns after its kernels have completed (its scratch goes back to
+ * the pool).  n_reads == 0 or total_bases == 0 launches nothing.                                                        */
+int brx_counter_abundance_batch_device(brx_counter_t *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads,
+                                       uint64_t total_bases, uint8_t abundance, uint8_t *d_profile, uint32_t *d_hist,
+                                       brx_abund_stats_t *d_stats, void *stream);
+/* same on host buffers (offsets[0] == 0)                                                                                */
+int brx_counter_abundance_batch(brx_counter_t *c, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                                uint8_t abundance, uint8_t *profile, uint32_t *hist, brx_abund_stats_t *stats);
+/* brx_set_get_batch's twin: out[i] = the count of the canonical form of forward_kmers[i] (low 2k bits)                  */
+int brx_counter_get_counts(brx_counter_t *c, const uint64_t *forward_kmers, uint32_t n, uint8_t *out);
+
 /* ---- multi-GPU: reads shard over the GPUs, the set is exchanged ONCE -----------------------------
  * The reference is one process with rayon threads over shared memory (src/main.rs:30-33, src/lib.rs:72-139); on N
  * GPUs every rank counts and later corrects its own block of the reads, and the single exchange step is the k-mer
