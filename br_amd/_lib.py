@@ -101,6 +101,9 @@ SIGNATURES = {
     "brx_counter_abundance_batch_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint8, _vp, _vp, _vp, _vp]),
     "brx_counter_abundance_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint8, _vp, _vp, _vp]),
     "brx_counter_get_counts": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
+    "brx_counter_lookup_prepare": (C.c_int, [_vp, _vp]),
+    "brx_counter_lookup_state": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "brx_counter_lookup_drop": (C.c_int, [_vp]),
     "brx_comm_unique_id": (C.c_int, [_vp]),
     "brx_comm_init": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _pp]),
     "brx_comm_init_all": (C.c_int, [C.c_int, C.POINTER(C.c_int), _pp]),

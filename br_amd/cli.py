@@ -205,7 +205,9 @@ def threshold_and_finish(cnt: Counter, args, keep: Optional[dict] = None) -> Pco
 
 def build_set(args, keep: Optional[dict] = None) -> Pcon:
     """keep (a dict, --abundance-report): the counter is left in it, and `fasta` counts into the hash table, whose counts
-    can be looked up at every k (the partitioned counter of 15 <= k <= 21 holds sorted keys)"""
+    can be looked up at every k.  (The partitioned counter of 15 <= k <= 21 answers too once Counter.prepare_lookup has
+    built its count view, but count + view + lookup measured slower there than the table's count + lookup: DESIGN.md
+    section 10.11, tools/partition_lookup_bench.py)"""
     dev = args.device
     if args.subcommand == "fasta":
         k = fasta_kmer_size(args.kmer_size)

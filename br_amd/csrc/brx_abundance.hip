@@ -17,6 +17,9 @@
 //                  line in vector loads, chain followed only while the flag (and at the home line the signature bit)
 //                  says so -- then one 4-byte load of the slot's counter, read as min(255, .).
 //   dense counter  byte khash(kmer) of the u8 table.
+//   partitioned    the count view that brx_counter_lookup_prepare built (brx_partbuild.hip: final_view_kernel): the last
+//                  level's bucket h >> 12 holds its distinct keys h & 4095 sorted, at most 4096 of them, then padding;
+//                  two neighbouring offsets, a binary search of at most 12 steps, the count byte beside the key.
 // A wave bins its counts into a 256-bin histogram of its own in LDS (one LDS atomic per position) and afterwards adds
 // the bins that are not zero to the read's row in global memory: integer atomic adds, so nothing depends on the launch
 // geometry or on timing.  abund_stats_kernel, a wave per read, turns the 256 bins into the statistics: a prefix sum over
@@ -35,7 +38,7 @@ namespace {
 
 constexpr uint32_t ABUND_TILE = 1024; // positions of a read per wave: 16 steps of 64, a 17th for the k-1 bases behind them
 
-enum { SRC_NONE = 0, SRC_DENSE = 1, SRC_TABLE = 2 }; // what answers: nothing counted yet, the u8 table, the counting table
+enum { SRC_NONE = 0, SRC_DENSE = 1, SRC_TABLE = 2, SRC_PART = 3 }; // what answers: nothing counted yet, the u8 table, the counting table, a partitioned counter's view
 
 struct AbundArgs {
     // the counter
@@ -43,6 +46,9 @@ struct AbundArgs {
     const uint64_t *lines;  // counting table
     const uint32_t *counts; // its counters, counts[line * 8 + slot]
     uint32_t line_shift, m, w;
+    const uint16_t *vkeys;  // count view of a partitioned counter: sorted low 12 bits per bucket, 0xFFFF behind them
+    const uint8_t *vcounts; // min(255, count) beside every key
+    const uint64_t *voff;   // bucket b = vkeys[voff[b] .. voff[b + 1])
     int k;
     uint32_t abundance;
     // the batch
@@ -86,6 +92,21 @@ __device__ __forceinline__ uint32_t abund_count(const AbundArgs &a, uint64_t km)
         return 0u;
     if (SRC == SRC_DENSE)
         return a.dense[khash(km, a.k)];
+    if (SRC == SRC_PART) {
+        const uint64_t h = khash(km, a.k);
+        const uint32_t key = (uint32_t)h & 4095u;
+        const uint64_t s = a.voff[h >> 12], e = a.voff[(h >> 12) + 1];
+        uint64_t lo = s, hi = e - s > 4096ull ? s + 4096ull : e; // distinct keys first: never more than 4096 of them
+        while (lo < hi) { // first entry >= key (the padding is larger than every key)
+            const uint64_t mid = lo + ((hi - lo) >> 1);
+            if (a.vkeys[mid] < key)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        // (lo == s + 4096 only if all 4096 keys are there and smaller, which key <= 4095 rules out)
+        return lo < e && a.vkeys[lo] == key ? a.vcounts[lo] : 0u;
+    }
     const uint64_t rc = revcomp(km, a.k);
     const uint64_t key = (((popc64(km) & 1) ? rc : km) >> 1) + 1ull;
     const uint32_t home = index_line_of(minimizer_of(km, rc, a.m, a.w), a.line_shift);
@@ -253,7 +274,13 @@ int abund_view(const brx_counter *c, const char *what, AbundArgs &a, int &src)
         }
         return BRX_OK;
     }
-    set_error("%s: the counter (strategy %d) holds no counts to look up", what, c->strategy); // (the entries refuse it before)
+    if (c->strategy == BRX_COUNT_SORTED && part_lookup_view(c, &a.vkeys, &a.vcounts, &a.voff)) {
+        src = a.vkeys ? SRC_PART : SRC_NONE;
+        return BRX_OK;
+    }
+    if (c->strategy == BRX_COUNT_SORTED)
+        return abund_refuse_partitioned(what, c->k); // (the view went between the entry's check and its lock)
+    set_error("%s: the counter (strategy %d) holds no counts to look up", what, c->strategy);
     return BRX_ERR_UNSUPPORTED;
 }
 
@@ -288,6 +315,8 @@ int abund_enqueue(const brx_counter *c, AbundArgs &a, uint64_t total_bases, DevS
         const uint32_t grid = (uint32_t)((tile_bound + 3ull) / 4ull);
         if (src == SRC_TABLE)
             abund_kernel<SRC_TABLE><<<grid, 256, 0, s>>>(a);
+        else if (src == SRC_PART)
+            abund_kernel<SRC_PART><<<grid, 256, 0, s>>>(a);
         else if (src == SRC_DENSE)
             abund_kernel<SRC_DENSE><<<grid, 256, 0, s>>>(a);
         else
@@ -304,6 +333,13 @@ int abund_enqueue(const brx_counter *c, AbundArgs &a, uint64_t total_bases, DevS
 } // namespace
 
 namespace brx {
+
+int abund_refuse_partitioned(const char *what, int k)
+{
+    set_error("%s: a partitioned counter (BRX_COUNT_SORTED) holds sorted keys, no counts to look up; count with BRX_COUNT_TABLE "
+              "for an abundance profile at k=%d, or build its count view first with brx_counter_lookup_prepare", what, k);
+    return BRX_ERR_UNSUPPORTED;
+}
 
 int abund_batch(const brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
                 uint8_t abundance, uint8_t *d_profile, uint32_t *d_hist, brx_abund_stats_t *d_stats, hipStream_t s)
@@ -335,6 +371,8 @@ int abund_get_counts(const brx_counter *c, const uint64_t *d_kmers, uint32_t n, 
     const uint32_t grid = (n + 255u) / 256u;
     if (src == SRC_TABLE)
         abund_get_kernel<SRC_TABLE><<<grid, 256, 0, s>>>(a, d_kmers, n, d_out);
+    else if (src == SRC_PART)
+        abund_get_kernel<SRC_PART><<<grid, 256, 0, s>>>(a, d_kmers, n, d_out);
     else if (src == SRC_DENSE)
         abund_get_kernel<SRC_DENSE><<<grid, 256, 0, s>>>(a, d_kmers, n, d_out);
     else

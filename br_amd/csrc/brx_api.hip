@@ -319,11 +319,8 @@ static int abund_check(const char *what, const brx_counter_t *c, const void *bas
         set_error("%s: null counter", what);
         return BRX_ERR_ARG;
     }
-    if (c->strategy == BRX_COUNT_SORTED) {
-        set_error("%s: a partitioned counter (BRX_COUNT_SORTED) holds sorted keys, no counts to look up; count with BRX_COUNT_TABLE "
-                  "for an abundance profile at k=%d", what, c->k);
-        return BRX_ERR_UNSUPPORTED;
-    }
+    if (c->strategy == BRX_COUNT_SORTED && !part_lookup_ready(c))
+        return abund_refuse_partitioned(what, c->k);
     if ((n_reads && !offsets) || (total_bases && !bases)) {
         set_error("%s: null bases / offsets for %u reads, %llu bases", what, n_reads, (unsigned long long)total_bases);
         return BRX_ERR_ARG;
@@ -448,6 +445,44 @@ int brx_counter_get_counts(brx_counter_t *c, const uint64_t *forward_kmers, uint
         return BRX_ERR_HIP;
     }
     return st;
+}
+
+int brx_counter_lookup_prepare(brx_counter_t *c, void *stream)
+{
+    if (!c) {
+        set_error("brx_counter_lookup_prepare: null counter");
+        return BRX_ERR_ARG;
+    }
+    if (c->strategy != BRX_COUNT_SORTED)
+        return BRX_OK; // dense / table: the counts are where a lookup reads them
+    BRX_TRY(use_device(c->device));
+    std::lock_guard<std::mutex> g(c->mu);
+    return part_lookup_prepare(c, (hipStream_t)stream);
+}
+
+int brx_counter_lookup_state(brx_counter_t *c, int *state)
+{
+    if (!c || !state) {
+        set_error("brx_counter_lookup_state: null counter / state");
+        return BRX_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(c->mu);
+    *state = c->strategy != BRX_COUNT_SORTED || part_lookup_ready(c) ? 1 : 0;
+    return BRX_OK;
+}
+
+int brx_counter_lookup_drop(brx_counter_t *c)
+{
+    if (!c) {
+        set_error("brx_counter_lookup_drop: null counter");
+        return BRX_ERR_ARG;
+    }
+    if (c->strategy != BRX_COUNT_SORTED)
+        return BRX_OK;
+    BRX_TRY(use_device(c->device));
+    std::lock_guard<std::mutex> g(c->mu);
+    part_lookup_drop(c);
+    return BRX_OK;
 }
 
 void brx_buf_free(void *p) { brx::host_buf_release(p); }

@@ -175,11 +175,19 @@ struct brx_counter {
 namespace brx {
 // counting table of a BRX_COUNT_TABLE counter as a read-only lookup sees it (brx_counttable.hip)
 void tab_view(const brx_counter *c, const uint64_t **lines, const uint32_t **counts, uint32_t *log_lines, uint32_t *m);
+// count view of a BRX_COUNT_SORTED counter (brx_partbuild.hip); the callers hold the counter's lock.  part_lookup_view:
+// false = no valid view; true with *keys == nullptr = nothing was counted
+int part_lookup_prepare(brx_counter *c, hipStream_t s);
+void part_lookup_drop(brx_counter *c);
+bool part_lookup_ready(const brx_counter *c);
+bool part_lookup_view(const brx_counter *c, const uint16_t **keys, const uint8_t **counts, const uint64_t **off);
 // k-mer abundance of reads (brx_abundance.hip); the callers (brx_api.hip) hold the counter's lock.  abund_batch enqueues on
 // `s` and returns after its kernels have completed
 int abund_batch(const brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
                 uint8_t abundance, uint8_t *d_profile, uint32_t *d_hist, brx_abund_stats_t *d_stats, hipStream_t s);
 int abund_get_counts(const brx_counter *c, const uint64_t *d_kmers, uint32_t n, uint8_t *d_out, hipStream_t s);
+// sets the error of a partitioned counter that has no count view, returns BRX_ERR_UNSUPPORTED
+int abund_refuse_partitioned(const char *what, int k);
 }
 
 struct brx_chain {

@@ -30,6 +30,7 @@
 
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 
 namespace brx {
 uint64_t scan_tmp_bytes(uint32_t n);
@@ -1602,6 +1603,185 @@ __global__ __launch_bounds__(64 * SP_WAVES) void final_spectrum_kernel(const uin
             atomicAdd(&hist[q], sp_hist[q]);
 }
 
+// ---- count view of the last-level buckets: what an abundance lookup reads (brx_abundance.hip, SRC_PART) -----------------
+// Turns every last-level bucket IN PLACE into a lookup structure: the bucket's distinct keys (the low F_BITS bits of the
+// hashes counted) in rising order at the front of its own range of `keys`, the rest of the range filled with VIEW_PAD (a
+// real key never exceeds F_SIZE - 1), and min(255, count) in `cnt` at the same index (0 beside the padding).  A bucket
+// then holds at most F_SIZE sorted entries whatever the coverage, and the count of hash h is found by a binary search
+// for h & (F_SIZE - 1) between off[h >> F_BITS] and off[(h >> F_BITS) + 1].
+// A wave takes a contiguous run of buckets the way final_count_kernel does -- 64 offsets in one load, the keys of as many
+// buckets as fit STAGE_KEYS staged in LDS with coalesced loads, rewritten there and written back whole -- because at
+// k = 21 there are 2^29 buckets of a few keys each and a memory round trip per bucket would be all the kernel does.
+//   up to 64 keys   a key per lane: rank among the distinct keys and multiplicity from one readlane + ballot per
+//                   distinct key
+//   more            counted in the wave's F_SIZE u32 bins (no 16-bit halves that could carry) with a bit per bin that is
+//                   not zero; a lane owns 64 neighbouring bins, a prefix sum of its bits gives their place in hash order
+// Either way the wave has read ALL of a bucket's keys before it writes any, and buckets are disjoint: in place is safe.
+constexpr int VW_WAVES = 4;
+constexpr uint32_t VIEW_PAD = 0xFFFFu;
+constexpr uint64_t VW_PER_WAVE = 63ull * 16ull; // consecutive buckets a wave takes per trip of its block: 16 offset loads
+__global__ __launch_bounds__(64 * VW_WAVES) void final_view_kernel(uint16_t *keys, const uint64_t *__restrict__ off, uint64_t n_buckets,
+                                                                   uint8_t *__restrict__ cnt_out)
+{
+    __shared__ uint32_t bins_all[VW_WAVES][F_SIZE];
+    __shared__ __attribute__((aligned(8))) uint16_t stage_all[VW_WAVES][STAGE_KEYS + 8];
+    __shared__ __attribute__((aligned(4))) uint8_t scnt_all[VW_WAVES][STAGE_KEYS + 8];
+    __shared__ uint32_t bmp_all[VW_WAVES][BIT_WORDS]; // which bins of the wave are not zero
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint32_t *bins = bins_all[wave];
+    uint16_t *stage = stage_all[wave];
+    uint8_t *scnt = scnt_all[wave];
+    uint32_t *bmp = bmp_all[wave];
+    for (uint32_t q = lane; q < F_SIZE; q += 64)
+        bins[q] = 0;
+    bmp[2 * lane] = 0;
+    bmp[2 * lane + 1] = 0;
+    asm volatile("" ::: "memory");
+
+    // blocks loop over chunks of buckets; inside a chunk consecutive buckets go to one wave, so its key stream is contiguous
+    const uint64_t n_chunks = (n_buckets + VW_PER_WAVE * VW_WAVES - 1) / (VW_PER_WAVE * VW_WAVES);
+    for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const uint64_t b_lo = (chunk * VW_WAVES + (uint64_t)wave) * VW_PER_WAVE;
+        const uint64_t b_hi = b_lo + VW_PER_WAVE < n_buckets ? b_lo + VW_PER_WAVE : n_buckets;
+        uint64_t g0 = b_lo;
+        while (g0 < b_hi) {
+            const int gmax = (int)((b_hi - g0 < 63) ? b_hi - g0 : 63);
+            const uint64_t oi = g0 + (uint64_t)lane;
+            const uint64_t offv = off[oi <= n_buckets ? oi : n_buckets];
+            const uint64_t gs = __shfl(offv, 0);
+            // largest prefix of buckets whose keys fit the staging buffer (lane l: does bucket l-1 end inside?)
+            const bool fits = lane >= 1 && lane <= gmax && (offv - gs) <= (uint64_t)STAGE_KEYS;
+            const uint64_t fm = __ballot(fits) >> 1; // bit j: buckets 0..j fit
+            int gcount = (fm == ~0ull >> 1) ? 63 : __builtin_ctzll(~fm);
+            if (gcount > gmax)
+                gcount = gmax;
+            const bool staged = gcount > 0;
+            if (!staged)
+                gcount = 1; // a single bucket larger than the staging buffer: counted from, and written to, global memory
+            const uint64_t ge = __shfl(offv, gcount);
+            if (ge == gs) { // nothing but empty buckets (most groups of a small input at large k)
+                g0 += (uint64_t)gcount;
+                continue;
+            }
+            const uint64_t base4 = gs & ~3ull; // 8-byte aligned start of the staged window
+            const uint32_t nquads = (uint32_t)((ge - base4 + 3) / 4);
+            if (staged) {
+                // (the window may begin with up to 3 keys of the bucket before and end with 3 of the one behind, which
+                // another wave may be rewriting: nobody looks at them, and they are not written back)
+                const uint2 *src = reinterpret_cast<const uint2 *>(keys + base4);
+                uint2 *dstq = reinterpret_cast<uint2 *>(stage);
+                for (uint32_t q = lane; q < nquads; q += 64)
+                    dstq[q] = src[q];
+                asm volatile("" ::: "memory");
+            }
+            const uint32_t off_lo = (uint32_t)offv, off_hi = (uint32_t)(offv >> 32);
+            for (int j = 0; j < gcount; j++) {
+                // (readlane returns a signed int: without the casts an offset with bit 31 set sign-extends)
+                const uint64_t s = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(off_hi, j) << 32) |
+                                   (uint64_t)(uint32_t)__builtin_amdgcn_readlane(off_lo, j);
+                const uint64_t e = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(off_hi, j + 1) << 32) |
+                                   (uint64_t)(uint32_t)__builtin_amdgcn_readlane(off_lo, j + 1);
+                const uint64_t n = e - s;
+                if (n == 0)
+                    continue;
+                const uint32_t sidx = (uint32_t)(s - base4); // of the bucket's first key in the staged window
+                if (staged && n <= 64) {
+                    const bool act = (uint64_t)lane < n;
+                    const uint32_t key = act ? (uint32_t)stage[sidx + lane] : VIEW_PAD;
+                    uint32_t less = 0, mult = 0, distinct = 0;
+                    bool lead = false;
+                    // one trip per DISTINCT key (at 50x a solid k-mer is there ~35 times): the lowest lane not yet
+                    // accounted for names the key, a ballot finds its copies and takes them out
+                    for (uint64_t rem = __ballot(act); rem; distinct++) {
+                        const int i = __builtin_ctzll(rem); // wave-uniform
+                        const uint32_t ki = (uint32_t)__builtin_amdgcn_readlane((int)key, i);
+                        const uint64_t eq = __ballot(act && key == ki);
+                        rem &= ~eq;
+                        if (ki < key)
+                            less++;
+                        if (key == ki) {
+                            mult = (uint32_t)__builtin_popcountll(eq);
+                            lead = lane == i;
+                        }
+                    }
+                    asm volatile("" ::: "memory");
+                    if (act && lead) {
+                        stage[sidx + less] = (uint16_t)key;
+                        scnt[sidx + less] = (uint8_t)(mult > 255u ? 255u : mult);
+                    }
+                    if (act && (uint32_t)lane >= distinct) {
+                        stage[sidx + lane] = (uint16_t)VIEW_PAD;
+                        scnt[sidx + lane] = 0;
+                    }
+                    asm volatile("" ::: "memory");
+                    continue;
+                }
+                for (uint64_t i = lane; i < n; i += 64) {
+                    const uint32_t kk = (staged ? (uint32_t)stage[sidx + (uint32_t)i] : (uint32_t)keys[s + i]) & (F_SIZE - 1u);
+                    atomicAdd(&bins[kk], 1u);
+                    atomicOr(&bmp[kk >> 5], 1u << (kk & 31u));
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // LDS operations of one wave complete in order
+                // lane l owns hashes 64l .. 64l+63: the bits of its two bitmap words are its distinct keys, a prefix sum
+                // over the lanes says where they go, and only bins that were counted are visited
+                uint64_t mine = ((uint64_t)bmp[2 * lane + 1] << 32) | (uint64_t)bmp[2 * lane];
+                bmp[2 * lane] = 0;
+                bmp[2 * lane + 1] = 0;
+                const uint32_t nmine = (uint32_t)__builtin_popcountll(mine);
+                uint32_t incl = nmine;
+                for (int d = 1; d < 64; d <<= 1) {
+                    const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
+                    if (lane >= d)
+                        incl += up;
+                }
+                const uint32_t pos = (uint32_t)__shfl((int)incl, 63); // distinct keys (<= n)
+                for (uint32_t p = incl - nmine; mine; mine &= mine - 1ull, p++) {
+                    const uint32_t h = 64u * (uint32_t)lane + (uint32_t)__builtin_ctzll(mine);
+                    const uint32_t v = bins[h];
+                    bins[h] = 0;
+                    const uint8_t c8 = (uint8_t)(v > 255u ? 255u : v);
+                    if (staged) {
+                        stage[sidx + p] = (uint16_t)h;
+                        scnt[sidx + p] = c8;
+                    } else {
+                        keys[s + p] = (uint16_t)h;
+                        cnt_out[s + p] = c8;
+                    }
+                }
+                for (uint64_t i = (uint64_t)pos + lane; i < n; i += 64) {
+                    if (staged) {
+                        stage[sidx + (uint32_t)i] = (uint16_t)VIEW_PAD;
+                        scnt[sidx + (uint32_t)i] = 0;
+                    } else {
+                        keys[s + i] = (uint16_t)VIEW_PAD;
+                        cnt_out[s + i] = 0;
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            }
+            if (staged) {
+                // the window back to memory: whole quads where all four keys are this group's, key by key at its two ends
+                asm volatile("" ::: "memory");
+                for (uint32_t q = lane; q < nquads; q += 64) {
+                    const uint64_t at = base4 + 4ull * q;
+                    if (at >= gs && at + 4 <= ge) {
+                        *reinterpret_cast<uint2 *>(keys + at) = *reinterpret_cast<const uint2 *>(stage + 4u * q);
+                        *reinterpret_cast<uint32_t *>(cnt_out + at) = *reinterpret_cast<const uint32_t *>(scnt + 4u * q);
+                    } else {
+                        for (uint32_t t = 0; t < 4; t++)
+                            if (at + t >= gs && at + t < ge) {
+                                keys[at + t] = stage[4u * q + t];
+                                cnt_out[at + t] = scnt[4u * q + t];
+                            }
+                    }
+                }
+                asm volatile("" ::: "memory");
+            }
+            g0 += (uint64_t)gcount;
+        }
+    }
+}
+
 // concatenates, per level-1 bucket, the segments of every batch (only needed for > 1 batch)
 __global__ __launch_bounds__(256) void merge_segments_kernel(const uint32_t *__restrict__ src,
                                                              const uint64_t *__restrict__ src_off,
@@ -1670,6 +1850,11 @@ struct PartState {
     uint64_t *d_l1off_all = nullptr;
     uint32_t *d_cnts = nullptr;        // B1 running counts (merge)
     uint64_t *d_shift = nullptr;       // B1 (merge)
+    // count view for lookups (part_lookup_prepare): d_keys_fin rewritten bucket by bucket, d_coff[nlev - 1] delimits them
+    std::atomic<bool> view_valid{false}; // (read without the counter's lock by the entries' first check) cleared by everything that touches the batches or the workspace above
+    bool view_empty = false;           // ... of a counter without keys: answers 0 everywhere, nothing to read
+    uint8_t *d_view_cnt = nullptr;     // min(255, count) beside every key of d_keys_fin
+    uint64_t view_cnt_cap = 0;
 };
 
 static int ensure_dev(void **p, uint64_t *cap, uint64_t need_bytes)
@@ -1821,7 +2006,8 @@ void part_free(brx_counter *c)
                     (void *)st->d_pos, (void *)st->d_scan_tmp, (void *)st->d_scalars, (void *)st->d_coff[0],
                     (void *)st->d_coff[1], (void *)st->d_coff[2], (void *)st->d_coff[3], (void *)st->d_keys_mid,
                     (void *)st->d_keys_mid2, (void *)st->d_keys_fin,
-                    (void *)st->d_merged, (void *)st->d_l1off_all, (void *)st->d_cnts, (void *)st->d_shift})
+                    (void *)st->d_merged, (void *)st->d_l1off_all, (void *)st->d_cnts, (void *)st->d_shift,
+                    (void *)st->d_view_cnt})
         if (p)
             (void)hipFree(p);
     delete st;
@@ -1831,6 +2017,7 @@ void part_free(brx_counter *c)
 int part_reset(brx_counter *c)
 {
     PartState *st = c->part;
+    st->view_valid = false;
     for (auto &b : st->batches)
         if (!b.borrowed)
             st->spare.push_back(b);
@@ -1842,6 +2029,7 @@ int part_reset(brx_counter *c)
 int part_l1_view(brx_counter *c, void **d_keys, void **d_l1off, uint32_t *n_buckets, uint64_t *n_keys)
 {
     PartState *st = c->part;
+    st->view_valid = false; // (the caller is about to move keys in or out of this counter)
     *n_buckets = (uint32_t)st->pl.nchild[0];
     if (st->batches.empty()) { // nothing counted (an empty shard): no keys, and the caller takes every offset as 0
         *d_keys = nullptr;
@@ -1864,6 +2052,7 @@ int part_l1_view(brx_counter *c, void **d_keys, void **d_l1off, uint32_t *n_buck
 int part_add_partitioned(brx_counter *c, const uint32_t *d_keys, const uint64_t *d_l1off, uint64_t n_keys)
 {
     PartState *st = c->part;
+    st->view_valid = false;
     if (n_keys == 0)
         return BRX_OK;
     PartBatch b;
@@ -1909,6 +2098,7 @@ int part_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_off
 {
     PartState *st = c->part;
     const Plan &pl = st->pl;
+    st->view_valid = false;
     if (total_bases == 0 || n_reads == 0)
         return BRX_OK;
     const uint64_t max_keys = total_bases; // upper bound of the number of k-mers of this batch
@@ -2066,9 +2256,13 @@ static int run_level(PartState *st, int l, const uint32_t *keys_in, const uint64
 
 // d_hist != nullptr: no set is produced (dst is not touched); the keys go through every level and the final buckets
 // are binned into the 256-entry count spectrum (bins 1..255)
-static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set *dst, unsigned long long *d_hist)
+// view: no set either; the same levels, then the final buckets become the count view (final_view_kernel)
+static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set *dst, unsigned long long *d_hist,
+                            bool view = false)
 {
     PartState *st = c->part;
+    st->view_valid = false; // the levels below overwrite what a view is made of
+    const bool no_set = d_hist || view;
     uint64_t total = 0;
     for (auto &b : st->batches)
         total += b.n;
@@ -2080,7 +2274,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
     const char *e_wide = getenv("BRX_WIDE_L2");
     const uint64_t wide_from = e_wide && *e_wide ? strtoull(e_wide, nullptr, 10) : 16384ull;
     const bool lazy_on = [] { const char *e = getenv("BRX_LAZY_BITS"); return !(e && *e == '0'); }(); // (per call too)
-    st->use_wide = wide_from != 0 && !d_hist && dst && (dst->sparse || (index_wanted(c->k) && lazy_on)) &&
+    st->use_wide = wide_from != 0 && !no_set && dst && (dst->sparse || (index_wanted(c->k) && lazy_on)) &&
                    st->pl_wide.bits[1] != st->pl.bits[1] &&
                    (wide_from == 1 || (st->pl.nlev == 3 ? total / st->pl.nchild[1] > wide_from
                                                         // four levels: as soon as the wider buckets fill a workgroup
@@ -2091,7 +2285,11 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
     const uint32_t *keys1 = nullptr;
     const uint64_t *l1off = nullptr;
     if (st->batches.empty() || total == 0) {
-        if (d_hist)
+        if (view) {
+            st->view_empty = true; // nothing counted: every lookup answers 0
+            st->view_valid = true;
+        }
+        if (no_set)
             return BRX_OK; // nothing counted: bins 1..255 stay 0
         if (dst->sparse) {
             if (!dst->d_keylist_n)
@@ -2133,7 +2331,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
     // solid-key list for the probe index: a solid hash was seen more than `abundance` times, so there are at
     // most total / (abundance + 1) of them; real data is far below that, and a list that turns out too short
     // is simply not used (the index is then built from the bit vector)
-    const bool emit = !d_hist && (dst->sparse || index_wanted(c->k));
+    const bool emit = !no_set && (dst->sparse || index_wanted(c->k));
     // lazy bit vector: when the solid hashes are listed anyway, the 2^(2k-4)-byte vector (16 GiB of slices at k = 19)
     // is written only if somebody asks for it later (ensure_bits); BRX_LAZY_BITS=0 writes it here as before
     const bool lazy = emit && !dst->sparse && lazy_on;
@@ -2175,7 +2373,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
     const uint64_t nb_hf = pl.nlev >= 2 ? pl.nchild[pl.nlev - 2] : 0;
     // (up to 2^17 keys per bucket: the table then takes a bucket in a few passes over its key range, see hash_final_kernel)
     static const uint64_t hf_max_avg = [] { const char *e = getenv("BRX_HASH_FINAL_MAX"); return e && *e ? strtoull(e, nullptr, 10) : 131072ull; }();
-    const bool hash_final = !d_hist && hf_on && (dst->sparse || lazy) && pl.nlev >= 3 && R_hf <= 20 && total / nb_hf <= hf_max_avg;
+    const bool hash_final = !no_set && hf_on && (dst->sparse || lazy) && pl.nlev >= 3 && R_hf <= 20 && total / nb_hf <= hf_max_avg;
     for (int l = 1; l < pl.nlev; l++) {
         if (hash_final && l == pl.nlev - 1)
             break;
@@ -2237,6 +2435,23 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
         return BRX_OK;
     }
     const uint64_t *fin_off = st->d_coff[pl.nlev - 1];
+    if (view) {
+        uint64_t capb = st->view_cnt_cap;
+        BRX_TRY(ensure_dev((void **)&st->d_view_cnt, &capb, total + 64));
+        st->view_cnt_cap = capb;
+        {
+            KernelTimer t("part_view", s);
+            const uint64_t nb = pl.nchild[pl.nlev - 1];
+            const uint64_t chunks = (nb + VW_PER_WAVE * VW_WAVES - 1) / (VW_PER_WAVE * VW_WAVES);
+            final_view_kernel<<<read_grid(chunks, 2048u), 64 * VW_WAVES, 0, s>>>(st->d_keys_fin, fin_off, nb, st->d_view_cnt);
+        }
+        BRX_HIP(hipGetLastError());
+        trace_stage(s, "count view");
+        BRX_HIP(hipStreamSynchronize(s));
+        st->view_empty = false;
+        st->view_valid = true;
+        return BRX_OK;
+    }
     if (d_hist) {
         KernelTimer t("part_spectrum", s);
         const uint64_t nb = pl.nchild[pl.nlev - 1];
@@ -2287,6 +2502,40 @@ int part_finish_into(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set 
 int part_spectrum(brx_counter *c, hipStream_t s, unsigned long long *d_hist)
 {
     return part_finish_impl(c, 255u, s, nullptr, d_hist);
+}
+
+// The count view of everything counted so far, for abundance lookups: levels 2..n as for the spectrum, then every final
+// bucket sorted and counted in place.  Valid -- after this has returned, the stream synchronised -- until the counter is
+// next asked for anything that touches its batches or the partition workspace; each of those clears view_valid first.
+int part_lookup_prepare(brx_counter *c, hipStream_t s)
+{
+    if (c->part->view_valid)
+        return BRX_OK; // nothing has touched the counter since the view was built
+    return part_finish_impl(c, 255u, s, nullptr, nullptr, true);
+}
+
+void part_lookup_drop(brx_counter *c)
+{
+    PartState *st = c->part;
+    st->view_valid = false;
+    if (st->d_view_cnt)
+        (void)hipFree(st->d_view_cnt);
+    st->d_view_cnt = nullptr;
+    st->view_cnt_cap = 0;
+}
+
+bool part_lookup_ready(const brx_counter *c) { return c->part && c->part->view_valid; }
+
+// what a lookup reads; false: no valid view.  *keys == nullptr with true: nothing was counted, every count is 0
+bool part_lookup_view(const brx_counter *c, const uint16_t **keys, const uint8_t **counts, const uint64_t **off)
+{
+    const PartState *st = c->part;
+    if (!st || !st->view_valid)
+        return false;
+    *keys = st->view_empty ? nullptr : st->d_keys_fin;
+    *counts = st->view_empty ? nullptr : st->d_view_cnt;
+    *off = st->view_empty ? nullptr : st->d_coff[st->pl.nlev - 1];
+    return true;
 }
 
 } // namespace brx

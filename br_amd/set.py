@@ -398,7 +398,7 @@ class Counter:
                         hist: bool = False):
         """(profile uint8[total] | None, hist uint32[n, 256] | None, stats abundance.STATS_DTYPE[n]) of a bases / offsets
         batch: the count of the k-mer that starts at every base, on the GPU (brx_counter_abundance_batch).  Dense and
-        table counters; the counter is left as it was."""
+        table counters, and a partitioned one after prepare_lookup(); the counter is left as it was."""
         from . import abundance as ab
         _check_u8(abundance, "abundance")
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
@@ -432,6 +432,23 @@ class Counter:
         out = np.zeros(km.size, dtype=np.uint8)
         _lib.check(_lib.lib().brx_counter_get_counts(self._h, km.ctypes.data, km.size, out.ctypes.data))
         return out
+
+    def prepare_lookup(self, stream: Optional[int] = None) -> None:
+        """build the count view of a partitioned counter (brx_counter_lookup_prepare), so that the abundance calls and
+        get_counts answer from it; nothing to do for a dense or a table counter.  The view holds until the counter is
+        next added to, finished, reset or asked for its spectrum: prepare after those"""
+        _lib.check(_lib.lib().brx_counter_lookup_prepare(self._h, stream))
+
+    @property
+    def lookup_ready(self) -> bool:
+        """whether the abundance calls and get_counts would answer (always for dense and table counters)"""
+        st = C.c_int(0)
+        _lib.check(_lib.lib().brx_counter_lookup_state(self._h, C.byref(st)))
+        return bool(st.value)
+
+    def drop_lookup(self) -> None:
+        """free the count view of a partitioned counter (harmless for the others)"""
+        _lib.check(_lib.lib().brx_counter_lookup_drop(self._h))
 
     def finish_into(self, abundance: int, dst: "Pcon", stream: Optional[int] = None) -> None:
         _check_u8(abundance, "abundance")

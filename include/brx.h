@@ -262,8 +262,9 @@ void brx_counter_free(brx_counter_t *c);
  *   the STATISTICS are brx_abund_stats_t, all fields 0 when kmers == 0.
  * Integer arithmetic throughout: no result depends on the launch geometry or on timing.  One lookup per k-mer of the
  * batch, 64 neighbouring positions per wave step, the batch cut by position like a cover call.  Dense (BRX_COUNT_DENSE)
- * and table (BRX_COUNT_TABLE) counters are served; a partitioned one (BRX_COUNT_SORTED) holds sorted keys, no counts
- * that could be looked up, and returns BRX_ERR_UNSUPPORTED.  A table counter that has counted nothing answers zeros.
+ * and table (BRX_COUNT_TABLE) counters are served as they are; a partitioned one (BRX_COUNT_SORTED) holds sorted keys, no
+ * counts that could be looked up, and returns BRX_ERR_UNSUPPORTED until brx_counter_lookup_prepare has built its count
+ * view (below).  A counter that has counted nothing answers zeros.
  * The calls take the counter's lock, see everything added before them (also after the table has regrown) and leave
  * the counter as it was: brx_counter_spectrum and brx_set_count_finish with any threshold still follow.
  * A read holds fewer than 2^32 - 16 bases.                                                                             */
@@ -287,6 +288,22 @@ int brx_counter_abundance_batch(brx_counter_t *c, const uint8_t *bases, const ui
                                 uint8_t abundance, uint8_t *profile, uint32_t *hist, brx_abund_stats_t *stats);
 /* brx_set_get_batch's twin: out[i] = the count of the canonical form of forward_kmers[i] (low 2k bits)                  */
 int brx_counter_get_counts(brx_counter_t *c, const uint64_t *forward_kmers, uint32_t n, uint8_t *out);
+/* The count view of a partitioned counter.  prepare sends everything counted so far -- every batch, segments registered
+ * with add_partitioned_device included -- through the radix levels the spectrum takes, then rewrites every last-level
+ * bucket (4096 consecutive hashes) in place: its distinct keys sorted, min(255, count) in a byte array beside them (one
+ * byte per counted k-mer, the only memory the view adds).  A lookup is then two neighbouring bucket offsets and a binary
+ * search of at most 12 steps.  prepare returns after `stream` has been synchronised; on a dense or a table counter it
+ * does nothing and returns BRX_OK.  The view holds until the counter is next used for anything that touches its batches or
+ * the partition workspace: add_batch[_device], add_partitioned_device, finish / finish_into, spectrum, reset, l1_view
+ * and the brx_exchange_* entries each drop it first, and abundance / get_counts refuse again until the next prepare
+ * (prepare after the threshold is chosen and the set finished).  The counter itself is left as it was: spectrum and
+ * finish with any threshold still follow and give what they gave before.
+ * state: *state = 1 if abundance / get_counts would answer (always for dense / table), 0 if they would refuse.
+ * drop: frees the view's count array; state 0 for a partitioned counter, nothing to do for the others.
+ * All three take the counter's lock.                                                                                    */
+int brx_counter_lookup_prepare(brx_counter_t *c, void *stream);
+int brx_counter_lookup_state(brx_counter_t *c, int *state);
+int brx_counter_lookup_drop(brx_counter_t *c);
 
 /* ---- multi-GPU: reads shard over the GPUs, the set is exchanged ONCE -----------------------------
  * The reference is one process with rayon threads over shared memory (src/main.rs:30-33, src/lib.rs:72-139); on N
