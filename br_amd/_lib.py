@@ -97,6 +97,7 @@ SIGNATURES = {
     "brx_counter_l1_view": (C.c_int, [_vp, _pp, _pp, C.POINTER(C.c_uint32), _u64p]),
     "brx_counter_add_partitioned_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
     "brx_counter_table_info": (C.c_int, [_vp, _u64p, _vp]),
+    "brx_counter_merge_state": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "brx_counter_free": (None, [_vp]),
     "brx_counter_abundance_batch_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint8, _vp, _vp, _vp, _vp]),
     "brx_counter_abundance_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint8, _vp, _vp, _vp]),
@@ -111,6 +112,10 @@ SIGNATURES = {
     "brx_exchange_build_partitioned": (C.c_int, [_vp, _vp, C.c_uint8, _vp, _vp]),
     "brx_exchange_reduce_counts": (C.c_int, [_vp, _vp, C.c_uint8, _vp]),
     "brx_exchange_plan": (C.c_int, [_u64p, C.c_int, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), _u64p, _u64p, _u64p, _u64p]),
+    "brx_exchange_table_owner": (C.c_int, [_vp, C.c_uint64, C.c_int, _vp]),
+    "brx_exchange_table_merge": (C.c_int, [_vp, _vp, _vp]),
+    "brx_exchange_spectrum": (C.c_int, [_vp, _vp, _u64p, _vp]),
+    "brx_exchange_table_finish": (C.c_int, [_vp, _vp, C.c_uint8, _vp, _vp]),
     "brx_comm_last_stats": (C.c_int, [_vp, _u64p]),
     "brx_comm_free": (None, [_vp]),
     "brx_chain_new": (C.c_int, [_vp, C.POINTER(Method), C.c_uint32, C.c_bool, _pp]),

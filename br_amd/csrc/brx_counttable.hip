@@ -34,6 +34,9 @@ struct TabState {
     uint64_t pending = 0;          // bases counted since: at most that many more keys
     uint64_t bases_total = 0;      // bases counted in all: at most that many occurrences
     uint64_t peak_bytes = 0;       // lines + counters held at once (both tables during a regrow)
+    // after brx_exchange_table_merge: the table holds the k-mers this rank owns, with the counts of the whole job; nothing
+    // more can be counted into it until the counter is reset (merged_world 0: an ordinary counter)
+    int merged_world = 0, merged_rank = 0;
 };
 
 } // namespace brx
@@ -101,6 +104,97 @@ __global__ __launch_bounds__(256) void table_spectrum_kernel(const uint64_t *__r
     __syncthreads();
     if (h[threadIdx.x])
         atomicAdd(hist + threadIdx.x, h[threadIdx.x]);
+}
+
+// ---- the table side of the multi-GPU merge (brx_exchange_table_merge) ---------------------------------------------------
+// Both owner kernels stream the slots as table_select_kernel does: 64 consecutive slots per wave trip, entry 7 of a line
+// skipped, every lane of the wave in every trip (n_slots and the stride are multiples of 256).  A trip walks the owners
+// present among its 64 slots -- the first lane not served yet names one, a ballot finds the lanes that share it -- and
+// that leader alone adds the popcount: one atomic per wave and owner present, never one per entry.
+
+// entries per owner into hist[world]
+__global__ __launch_bounds__(256) void table_owner_hist_kernel(const uint64_t *__restrict__ lines, uint64_t n_slots, uint32_t world,
+                                                               unsigned long long *__restrict__ hist)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_slots; i += stride) {
+        const uint64_t v = (i & 7ull) == 7ull ? 0ull : lines[i];
+        const uint32_t own = v ? table_owner_of(v - 1ull, world) : 0xffffffffu;
+        unsigned long long todo = __ballot(v != 0ull);
+        while (todo) { // wave-uniform
+            const uint32_t leader = (uint32_t)__ffsll(todo) - 1u;
+            const uint32_t o = __shfl(own, leader);
+            const unsigned long long same = __ballot(own == o);
+            if (lane == leader && o < world)
+                atomicAdd(hist + o, (unsigned long long)__popcll(same));
+            todo &= ~same;
+        }
+    }
+}
+
+// every entry into its owner's region of (keys, cnts): region r is [off[r], off[r + 1]), cursor[r] starts at off[r]
+__global__ __launch_bounds__(256) void table_owner_split_kernel(const uint64_t *__restrict__ lines, const uint32_t *__restrict__ counts,
+                                                                uint64_t n_slots, uint32_t world, const uint64_t *__restrict__ off,
+                                                                unsigned long long *__restrict__ cursor, uint64_t *__restrict__ keys,
+                                                                uint8_t *__restrict__ cnts)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_slots; i += stride) {
+        const uint64_t v = (i & 7ull) == 7ull ? 0ull : lines[i];
+        const uint32_t own = v ? table_owner_of(v - 1ull, world) : 0xffffffffu;
+        const uint32_t cnt = v ? table_count_read(counts[i]) : 0u;
+        unsigned long long todo = __ballot(v != 0ull);
+        while (todo) { // wave-uniform
+            const uint32_t leader = (uint32_t)__ffsll(todo) - 1u;
+            const uint32_t o = __shfl(own, leader);
+            const unsigned long long same = __ballot(own == o);
+            unsigned long long first = 0;
+            if (lane == leader && o < world)
+                first = atomicAdd(cursor + o, (unsigned long long)__popcll(same));
+            first = __shfl(first, leader);
+            if (own == o && o < world) {
+                const uint64_t pos = first + (uint64_t)__popcll(same & ((1ull << lane) - 1ull));
+                if (pos < off[o + 1u]) { // (the histogram pass sized the region: always, unless the table changed in between)
+                    keys[pos] = v - 1ull;
+                    cnts[pos] = (uint8_t)cnt;
+                }
+            }
+            todo &= ~same;
+        }
+    }
+}
+
+// the rehash kernel with (key, count) arrays as its source: a key may come once per source rank, its counts add up to
+// 255.  n_new: keys this launch put in; n_sum: the counts it added (a bound on the occurrences behind the table)
+__global__ __launch_bounds__(256) void table_merge_kernel(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ cnts, uint64_t n, int k,
+                                                          uint64_t key_limit, uint64_t *__restrict__ lines, uint32_t *__restrict__ counts,
+                                                          uint32_t line_shift, uint32_t m, uint32_t w, unsigned long long *__restrict__ n_new,
+                                                          unsigned long long *__restrict__ n_sum)
+{
+    uint32_t added = 0;
+    unsigned long long sum = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t h = keys[i];
+        const uint32_t by = cnts[i];
+        if (h < key_limit && by) { // (anything else is not an entry of a table of this k)
+            bool fresh;
+            const uint64_t slot = table_find_or_claim(lines, line_shift, m, w, k, (h << 1) | (uint64_t)(popc64(h) & 1), fresh);
+            table_count_bump(counts + slot, by);
+            added += fresh ? 1u : 0u;
+            sum += by;
+        }
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        added += __shfl_down(added, d);
+        sum += __shfl_down(sum, d);
+    }
+    if ((threadIdx.x & 63) == 0 && sum) {
+        atomicAdd(n_new, (unsigned long long)added);
+        atomicAdd(n_sum, sum);
+    }
 }
 
 uint32_t slot_grid(uint64_t n_slots) { return read_grid((n_slots + 255ull) / 256ull, 256u * 16u); }
@@ -236,12 +330,18 @@ int tab_reset(brx_counter *c, hipStream_t s)
     }
     BRX_HIP(hipMemsetAsync(t->d_nkeys, 0, 8, s));
     t->keys_known = t->pending = t->bases_total = 0;
+    t->merged_world = t->merged_rank = 0;
     return BRX_OK;
 }
 
 int tab_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases, hipStream_t s)
 {
     TabState *t = c->tab;
+    if (t->merged_world) {
+        set_error("counting table: the counter was merged over %d ranks and holds the job's counts of the k-mers rank %d owns; "
+                  "brx_counter_reset it before counting again", t->merged_world, t->merged_rank);
+        return BRX_ERR_ARG;
+    }
     if (!n_reads || !total_bases)
         return BRX_OK;
     // every k-mer of the batch could be new
@@ -304,6 +404,109 @@ int tab_finish_into(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set *
     dst->keylist_valid = list; // (nothing counted: the empty list)
     trace_stage(s, "table select");
     return BRX_OK;
+}
+
+int tab_split_by_owner(brx_counter *c, int world, hipStream_t s, uint64_t **d_keys, uint8_t **d_cnts, uint64_t *per_owner)
+{
+    TabState *t = c->tab;
+    *d_keys = nullptr;
+    *d_cnts = nullptr;
+    for (int r = 0; r < world; r++)
+        per_owner[r] = 0;
+    if (t->pending)
+        BRX_TRY(read_keys(t, s));
+    const uint64_t n = t->d_lines ? t->keys_known : 0ull;
+    if (n) {
+        const uint64_t n_slots = 8ull << t->log_lines;
+        DevScratch ws;
+        unsigned long long *d_hist = nullptr, *d_cursor = nullptr;
+        uint64_t *d_off = nullptr;
+        BRX_TRY(ws.get(&d_hist, (uint64_t)world));
+        BRX_TRY(ws.get(&d_cursor, (uint64_t)world));
+        BRX_TRY(ws.get(&d_off, (uint64_t)world + 1ull));
+        std::vector<uint64_t> off((size_t)world + 1, 0);
+        BRX_HIP(hipMemsetAsync(d_hist, 0, (size_t)world * 8, s));
+        {
+            KernelTimer kt("tab_split", s);
+            table_owner_hist_kernel<<<slot_grid(n_slots), 256, 0, s>>>(t->d_lines, n_slots, (uint32_t)world, d_hist);
+        }
+        BRX_HIP(hipGetLastError());
+        BRX_HIP(hipMemcpyAsync(per_owner, d_hist, (size_t)world * 8, hipMemcpyDeviceToHost, s));
+        BRX_HIP(hipStreamSynchronize(s));
+        for (int r = 0; r < world; r++)
+            off[r + 1] = off[r] + per_owner[r];
+        if (off[world] != n) {
+            set_error("counting table split: %llu entries found, %llu k-mers counted", (unsigned long long)off[world], (unsigned long long)n);
+            return BRX_ERR_HIP;
+        }
+        hipError_t e = hipMalloc((void **)d_keys, n * 8);
+        if (e == hipSuccess)
+            e = hipMalloc((void **)d_cnts, n);
+        if (e != hipSuccess) {
+            set_error("hipMalloc(%llu B, the table's %llu entries grouped by owner): %s", (unsigned long long)(n * 9), (unsigned long long)n,
+                      hipGetErrorString(e));
+            return BRX_ERR_NOMEM;
+        }
+        if ((96ull << t->log_lines) + n * 9 > t->peak_bytes)
+            t->peak_bytes = (96ull << t->log_lines) + n * 9;
+        BRX_HIP(hipMemcpyAsync(d_off, off.data(), ((size_t)world + 1) * 8, hipMemcpyHostToDevice, s));
+        BRX_HIP(hipMemcpyAsync(d_cursor, d_off, (size_t)world * 8, hipMemcpyDeviceToDevice, s));
+        {
+            KernelTimer kt("tab_split", s);
+            table_owner_split_kernel<<<slot_grid(n_slots), 256, 0, s>>>(t->d_lines, t->d_counts, n_slots, (uint32_t)world, d_off, d_cursor,
+                                                                       *d_keys, *d_cnts);
+        }
+        BRX_HIP(hipGetLastError());
+        BRX_HIP(hipStreamSynchronize(s)); // (`off` is a local; the table is freed below)
+    }
+    free_table(t); // every entry is in the arrays now: never two tables at once
+    BRX_HIP(hipMemsetAsync(t->d_nkeys, 0, 8, s));
+    t->keys_known = t->pending = t->bases_total = 0;
+    return BRX_OK;
+}
+
+int tab_load_pairs(brx_counter *c, const uint64_t *d_keys, const uint8_t *d_cnts, uint64_t n, hipStream_t s)
+{
+    TabState *t = c->tab;
+    if (t->d_lines || t->keys_known || t->pending) {
+        set_error("counting table: pairs are loaded into an empty counter");
+        return BRX_ERR_ARG;
+    }
+    if (!n)
+        return BRX_OK;
+    BRX_TRY(regrow(c, n, s)); // every pair could be a key of its own
+    DevScratch ws;
+    unsigned long long *d_sum = nullptr;
+    BRX_TRY(ws.get(&d_sum, 1));
+    BRX_HIP(hipMemsetAsync(d_sum, 0, 8, s));
+    {
+        KernelTimer kt("tab_merge", s);
+        table_merge_kernel<<<read_grid((n + 255ull) / 256ull, 256u * 16u), 256, 0, s>>>(d_keys, d_cnts, n, c->k, set_nbits(c->k), t->d_lines,
+                                                                                       t->d_counts, 32u - t->log_lines, t->m,
+                                                                                       (uint32_t)c->k - t->m + 1u, t->d_nkeys, d_sum);
+        BRX_HIP(hipGetLastError());
+    }
+    unsigned long long sum = 0;
+    BRX_HIP(hipMemcpyAsync(&sum, d_sum, 8, hipMemcpyDeviceToHost, s));
+    BRX_TRY(read_keys(t, s));
+    t->bases_total = sum; // a key listed by finish has a count above `abundance`: tab_finish_into's bound on the list holds
+    return BRX_OK;
+}
+
+void tab_set_merged(brx_counter *c, int world, int rank)
+{
+    c->tab->merged_world = world;
+    c->tab->merged_rank = rank;
+}
+
+bool tab_merged(const brx_counter *c, int *world, int *rank)
+{
+    const TabState *t = c->tab;
+    if (world)
+        *world = t ? t->merged_world : 0;
+    if (rank)
+        *rank = t ? t->merged_rank : 0;
+    return t && t->merged_world != 0;
 }
 
 // bins 1..255 of the count spectrum into d_hist (256 x u64, zeroed by the caller); the counter is left as it was

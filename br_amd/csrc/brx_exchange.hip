@@ -8,7 +8,10 @@
 //       finishes its digit range, and the solid hashes come back to everybody (all-gather-v of u64 lists);
 //   dense strategy                  the reference's own u8 table is all-reduced (north_star's form): counts are
 //       clamped to min(c, a+1) first so that an u8 SUM over `world` ranks cannot wrap while world*(a+1) <= 255;
-//       beyond that the table is reduced in int32 slices.
+//       beyond that the table is reduced in int32 slices;
+//   table strategy (k = 23..31)     the entries of the counting tables travel as (u64 key, u8 count) pairs to the rank that
+//       owns the k-mer (a hash of it), the owner sums with saturation into a fresh table and finishes its share, and the
+//       solid hashes come back to everybody as above (brx_exchange_table_merge / _spectrum / _table_finish, at the end).
 //
 // librccl is NOT a link-time dependency: it is dlopen'ed by soname on first use, so that a process which
 // already carries a copy (PyTorch bundles one under the same soname) shares it, and hosts that never go
@@ -132,7 +135,8 @@ struct brx_comm {
     // workspace kept between jobs
     uint32_t *d_recv = nullptr;    // keys received from every rank for the owned digit range
     uint64_t recv_cap = 0;         // bytes
-    uint64_t *d_tables = nullptr;  // world x (B1+1) gathered level-1 offset tables, then the owner's segment tables
+    uint64_t *d_tables = nullptr;  // world x (B1+1) gathered level-1 offset tables, then the owner's segment tables (table merge:
+                                   // world x world send counts; its spectrum: world x 256 bins)
     uint64_t tables_cap = 0;
     uint64_t *d_gather = nullptr;  // every rank's solid-hash list, rank after rank
     uint64_t gather_cap = 0;
@@ -171,12 +175,15 @@ int grow(void **p, uint64_t *cap, uint64_t need, const char *what)
     return BRX_OK;
 }
 
-// every rank's `send` (send_counts[r] elements for rank r, back to back) to its owner; `recv` likewise.
-// One group of ncclSend / ncclRecv per round, messages capped at a2a_chunk_elems().  A failing call never leaves
-// the thread's group open: the first error is kept, the group is closed, then the error is returned.
-int all_to_all_v(brx_comm *cm, const uint32_t *send, const uint64_t *send_counts, uint32_t *recv, const uint64_t *recv_counts,
-                 uint64_t job_biggest, hipStream_t s)
+// every rank's `send` (send_counts[r] elements of `esize` bytes for rank r, back to back) to its owner; `recv` likewise.
+// One group of ncclSend / ncclRecv per round, messages capped at a2a_chunk_elems() x 4 bytes (the cap counts u32 keys).
+// A failing call never leaves the thread's group open: the first error is kept, the group is closed, then the error is
+// returned.
+int all_to_all_v(brx_comm *cm, const void *send_v, const uint64_t *send_counts, void *recv_v, const uint64_t *recv_counts,
+                 uint64_t job_biggest, uint64_t esize, ncclDataType_t dt, hipStream_t s)
 {
+    const char *send = (const char *)send_v;
+    char *recv = (char *)recv_v;
     // tests on one GPU: route the own share through ncclSend/ncclRecv to self instead of a device copy
     const char *ess = getenv("BRX_EXCHANGE_SELF_SEND");
     const bool self_send = ess && *ess == '1';
@@ -188,7 +195,8 @@ int all_to_all_v(brx_comm *cm, const uint32_t *send, const uint64_t *send_counts
     }
     // every rank must run the same number of rounds: the largest message of the JOB decides (every rank holds every
     // offset table, so all of them compute the same `job_biggest`)
-    const uint64_t chunk = a2a_chunk_elems() ? a2a_chunk_elems() : (job_biggest ? job_biggest : 1);
+    const uint64_t cap = a2a_chunk_elems() * 4ull / esize; // elements of this size in a message of the cap
+    const uint64_t chunk = a2a_chunk_elems() ? (cap ? cap : 1) : (job_biggest ? job_biggest : 1);
     const uint64_t rounds = (job_biggest + chunk - 1) / chunk;
     cm->rounds_a2a = rounds;
     for (uint64_t c = 0; c < rounds; c++) {
@@ -200,13 +208,14 @@ int all_to_all_v(brx_comm *cm, const uint32_t *send, const uint64_t *send_counts
             const uint64_t rlo = std::min(c * chunk, recv_counts[r]), rhi = std::min((c + 1) * chunk, recv_counts[r]);
             if (r == cm->rank && !self_send) { // own share: a device copy, not a message
                 if (shi > slo)
-                    hfirst = hipMemcpyAsync(recv + ro[r] + rlo, send + so[r] + slo, (shi - slo) * 4, hipMemcpyDeviceToDevice, s);
+                    hfirst = hipMemcpyAsync(recv + (ro[r] + rlo) * esize, send + (so[r] + slo) * esize, (shi - slo) * esize,
+                                            hipMemcpyDeviceToDevice, s);
                 continue;
             }
             if (shi > slo)
-                first = g_rccl.Send(send + so[r] + slo, shi - slo, ncclUint32, r, cm->comm, s);
+                first = g_rccl.Send(send + (so[r] + slo) * esize, shi - slo, dt, r, cm->comm, s);
             if (rhi > rlo && first == ncclSuccess)
-                first = g_rccl.Recv(recv + ro[r] + rlo, rhi - rlo, ncclUint32, r, cm->comm, s);
+                first = g_rccl.Recv(recv + (ro[r] + rlo) * esize, rhi - rlo, dt, r, cm->comm, s);
         }
         const ncclResult_t ge = g_rccl.GroupEnd();
         if (hfirst != hipSuccess) {
@@ -459,6 +468,56 @@ int gather_lists(brx_comm *cm, const std::vector<uint64_t> &n_of, const std::vec
     return BRX_OK;
 }
 
+// Steps 5 and 6 of an exchange, shared by the partitioned build and the table finish: `d_list` holds the n_mine solid
+// hashes this owner found (`local`: how that went; `what`: the owner's work, for the message).
+//   5. the owners' solid hashes to everybody; the size exchange carries the status of the owner's step
+//   6. the whole job's set on this rank: OR the lists into a current bit vector, and hand the complete list to
+//      the probe index (for lazy and sparse sets the chained index built from it IS the set).  No collective
+//      follows, so a failure here is this rank's alone.
+int replicate_solid(brx_comm *cm, brx_set_t *dst, const void *d_list, uint64_t n_mine, int local, const char *what, hipStream_t s,
+                    uint64_t *n_all_out)
+{
+    const int W = cm->world, me = cm->rank;
+    uint64_t pair[2] = {n_mine, (uint64_t)(int64_t)local};
+    std::vector<uint64_t> got((size_t)W * 2);
+    BRX_HIP(hipMemcpy(cm->d_counts + 2 * me, pair, 16, hipMemcpyHostToDevice)); // (a stack variable: not an async copy)
+    BRX_NCCL(g_rccl.AllGather(cm->d_counts + 2 * me, cm->d_counts, 2, ncclUint64, cm->comm, s)); // in place
+    BRX_HIP(hipMemcpyAsync(got.data(), cm->d_counts, (size_t)W * 16, hipMemcpyDeviceToHost, s));
+    BRX_HIP(hipStreamSynchronize(s));
+    if (local != BRX_OK) {
+        cm->agreed_failure = true; // (the size exchange carried it to everybody)
+        return local;
+    }
+    std::vector<uint64_t> n_of(W), off(W + 1, 0);
+    for (int r = 0; r < W; r++) {
+        if ((int64_t)got[2 * r + 1] != BRX_OK) {
+            set_error("exchange: rank %d failed to %s (%s)", r, what, brx_strerror((int)(int64_t)got[2 * r + 1]));
+            cm->agreed_failure = true;
+            return (int)(int64_t)got[2 * r + 1];
+        }
+        n_of[r] = got[2 * r];
+        off[r + 1] = off[r] + n_of[r];
+    }
+    const uint64_t n_all = off[W];
+    local = grow((void **)&cm->d_gather, &cm->gather_cap, (n_all + 1) * 8, "gathered solid k-mers");
+    BRX_TRY(agree(cm, local, s));
+    if (n_mine)
+        BRX_HIP(hipMemcpyAsync(cm->d_gather + off[me], d_list, n_mine * 8, hipMemcpyDeviceToDevice, s));
+    if (W > 1)
+        BRX_TRY(gather_lists(cm, n_of, off, s));
+    if (!dst->sparse && !dst->bits_stale && W > 1) {
+        if (off[me])
+            BRX_TRY(brx_set_or_keys_device(dst, cm->d_gather, off[me], s));
+        if (n_all > off[me + 1])
+            BRX_TRY(brx_set_or_keys_device(dst, cm->d_gather + off[me + 1], n_all - off[me + 1], s));
+    }
+    if (index_wanted(dst->k) || no_bits(dst))
+        BRX_TRY(brx_set_index_build_from_keys_device(dst, cm->d_gather, n_all, 0, 0, s));
+    BRX_HIP(hipStreamSynchronize(s));
+    *n_all_out = n_all;
+    return BRX_OK;
+}
+
 // a failure only this rank saw: the peers must not be left in their next collective (see brx_comm::agreed_failure)
 void abort_after_local_failure(brx_comm *cm)
 {
@@ -475,6 +534,28 @@ struct ExchangeJob {
     uint64_t *d_extracted = nullptr; // owned: freed by the caller whatever happens
     bool counter_borrows = false;    // the counter refers to cm->d_recv: reset it before returning
 };
+
+// the solid hashes the owner's finish left in `dst`: its key list (an owner's finish saw only owned k-mers, so the list
+// IS this rank's share of the set), else taken from the bit vector
+int owned_list(brx_set_t *dst, ExchangeJob &job, void **d_list, uint64_t *n_mine, hipStream_t s)
+{
+    BRX_TRY(brx_set_keylist_device(dst, d_list, n_mine, s));
+    if (!*d_list) {
+        // no list (it did not fit, or BRX_LAZY_BITS=0 builds that keep none): take it from the bit vector
+        if (dst->sparse || dst->bits_stale) {
+            set_error("exchange: the owner's set has neither a key list nor a bit vector");
+            return BRX_ERR_NOMEM;
+        }
+        BRX_HIP(hipStreamSynchronize(s));
+        uint64_t pc = 0;
+        BRX_TRY(brx_set_popcount(dst, &pc));
+        BRX_HIP(hipMalloc((void **)&job.d_extracted, (pc + 64) * 8));
+        BRX_TRY(brx_set_extract_keys_device(dst, 0, dst->nwords * 32, job.d_extracted, pc + 64, n_mine, s));
+        *d_list = job.d_extracted;
+    }
+    BRX_HIP(hipStreamSynchronize(s));
+    return BRX_OK;
+}
 
 // steps 4a: the owner's finish of the segments it received (all local work, one status)
 int finish_owned(brx_comm *cm, brx_counter_t *c, uint8_t abundance, brx_set_t *dst, const std::vector<uint64_t> &seg,
@@ -493,24 +574,7 @@ int finish_owned(brx_comm *cm, brx_counter_t *c, uint8_t abundance, brx_set_t *d
         pos += recv_counts[r];
     }
     BRX_TRY(brx_set_count_finish_into(c, abundance, s, dst));
-    // The partitioned finish lists the solid hashes on the side (only owned buckets were counted, so the list IS this
-    // rank's share of the set).
-    BRX_TRY(brx_set_keylist_device(dst, d_list, n_mine, s));
-    if (!*d_list) {
-        // no list (it did not fit, or BRX_LAZY_BITS=0 builds that keep none): take it from the bit vector
-        if (dst->sparse || dst->bits_stale) {
-            set_error("exchange: the owner's set has neither a key list nor a bit vector");
-            return BRX_ERR_NOMEM;
-        }
-        BRX_HIP(hipStreamSynchronize(s));
-        uint64_t pc = 0;
-        BRX_TRY(brx_set_popcount(dst, &pc));
-        BRX_HIP(hipMalloc((void **)&job.d_extracted, (pc + 64) * 8));
-        BRX_TRY(brx_set_extract_keys_device(dst, 0, dst->nwords * 32, job.d_extracted, pc + 64, n_mine, s));
-        *d_list = job.d_extracted;
-    }
-    BRX_HIP(hipStreamSynchronize(s));
-    return BRX_OK;
+    return owned_list(dst, job, d_list, n_mine, s);
 }
 
 int exchange_body(brx_comm *cm, brx_counter_t *c, uint8_t abundance, brx_set_t *dst, hipStream_t s, ExchangeJob &job)
@@ -553,7 +617,7 @@ int exchange_body(brx_comm *cm, brx_counter_t *c, uint8_t abundance, brx_set_t *
         local = grow((void **)&cm->d_recv, &cm->recv_cap, (n_recv + 1) * 4, "received keys");
     BRX_TRY(agree(cm, local, s));
     const double t_a2a = now_ms();
-    BRX_TRY(all_to_all_v(cm, (const uint32_t *)pk, send_counts.data(), cm->d_recv, recv_counts.data(), biggest, s));
+    BRX_TRY(all_to_all_v(cm, pk, send_counts.data(), cm->d_recv, recv_counts.data(), biggest, 4, ncclUint32, s));
     BRX_HIP(hipStreamSynchronize(s)); // the local level-1 buffer has been read: the counter may forget it now
     const double t_a2a_done = now_ms();
 
@@ -563,47 +627,9 @@ int exchange_body(brx_comm *cm, brx_counter_t *c, uint8_t abundance, brx_set_t *
     uint64_t n_mine = 0;
     local = finish_owned(cm, c, abundance, dst, seg, recv_counts.data(), T, job, &d_list, &n_mine, s);
 
-    // 5. the owners' solid hashes to everybody; the size exchange carries the status of step 4
-    uint64_t pair[2] = {n_mine, (uint64_t)(int64_t)local};
-    std::vector<uint64_t> got((size_t)W * 2);
-    BRX_HIP(hipMemcpy(cm->d_counts + 2 * me, pair, 16, hipMemcpyHostToDevice)); // (a stack variable: not an async copy)
-    BRX_NCCL(g_rccl.AllGather(cm->d_counts + 2 * me, cm->d_counts, 2, ncclUint64, cm->comm, s)); // in place
-    BRX_HIP(hipMemcpyAsync(got.data(), cm->d_counts, (size_t)W * 16, hipMemcpyDeviceToHost, s));
-    BRX_HIP(hipStreamSynchronize(s));
-    if (local != BRX_OK) {
-        cm->agreed_failure = true; // (the size exchange carried it to everybody)
-        return local;
-    }
-    std::vector<uint64_t> n_of(W), off(W + 1, 0);
-    for (int r = 0; r < W; r++) {
-        if ((int64_t)got[2 * r + 1] != BRX_OK) {
-            set_error("exchange: rank %d failed to finish its digit range (%s)", r, brx_strerror((int)(int64_t)got[2 * r + 1]));
-            cm->agreed_failure = true;
-            return (int)(int64_t)got[2 * r + 1];
-        }
-        n_of[r] = got[2 * r];
-        off[r + 1] = off[r] + n_of[r];
-    }
-    const uint64_t n_all = off[W];
-    local = grow((void **)&cm->d_gather, &cm->gather_cap, (n_all + 1) * 8, "gathered solid k-mers");
-    BRX_TRY(agree(cm, local, s));
-    if (n_mine)
-        BRX_HIP(hipMemcpyAsync(cm->d_gather + off[me], d_list, n_mine * 8, hipMemcpyDeviceToDevice, s));
-    if (W > 1)
-        BRX_TRY(gather_lists(cm, n_of, off, s));
-
-    // 6. the whole job's set on this rank: OR the lists into a current bit vector, and hand the complete list to
-    //    the probe index (for lazy and sparse sets the chained index built from it IS the set).  No collective
-    //    follows, so a failure here is this rank's alone.
-    if (!dst->sparse && !dst->bits_stale && W > 1) {
-        if (off[me])
-            BRX_TRY(brx_set_or_keys_device(dst, cm->d_gather, off[me], s));
-        if (n_all > off[me + 1])
-            BRX_TRY(brx_set_or_keys_device(dst, cm->d_gather + off[me + 1], n_all - off[me + 1], s));
-    }
-    if (index_wanted(dst->k) || no_bits(dst))
-        BRX_TRY(brx_set_index_build_from_keys_device(dst, cm->d_gather, n_all, 0, 0, s));
-    BRX_HIP(hipStreamSynchronize(s));
+    // 5., 6. the owners' solid hashes to everybody, the whole job's set on this rank
+    uint64_t n_all = 0;
+    BRX_TRY(replicate_solid(cm, dst, d_list, n_mine, local, "finish its digit range", s, &n_all));
     cm->stats[0] = (nk - send_counts[me]) * 4;             // key bytes sent over the links
     cm->stats[1] = (n_recv - recv_counts[me]) * 4;         // key bytes received
     cm->stats[2] = n_recv;                                 // keys this owner counted
@@ -631,7 +657,8 @@ int brx_exchange_build_partitioned(brx_comm_t *cm, brx_counter_t *c, uint8_t abu
                   dst->device, dst->k);
         local = BRX_ERR_ARG;
     } else if (c->strategy == BRX_COUNT_TABLE) {
-        set_error("exchange: not available with the table count strategy (BRX_COUNT_TABLE); sets of k >= 23 are built on one GPU");
+        set_error("exchange: not available with the table count strategy (BRX_COUNT_TABLE); such counters cross the GPUs through "
+                  "brx_exchange_table_merge / _table_finish");
         local = BRX_ERR_UNSUPPORTED;
     }
     BRX_TRY(use_device(cm->device));
@@ -717,6 +744,270 @@ static int reduce_counts_body(brx_comm_t *cm, brx_counter_t *c, uint8_t abundanc
     }
     BRX_HIP(hipStreamSynchronize(s));
     return BRX_OK;
+}
+
+} // extern "C"
+
+// ---- counting tables across ranks (BRX_COUNT_TABLE, any odd k up to 31) -------------------------------------------------
+// The partitioned exchange's idea on (key, count) pairs: every k-mer has ONE owner (table_owner_of), the ranks send the
+// entries of their tables there, the owner sums with saturation and keeps a table of the k-mers it owns -- a merged
+// counter, which answers for the whole job: its spectrum summed over the ranks is the job's, its finish followed by the
+// replication of the solid lists (replicate_solid) gives every rank the job's set.
+namespace {
+
+struct TableJob { // device arrays of one merge, freed by the caller whatever happens
+    uint64_t *d_skeys = nullptr, *d_rkeys = nullptr;
+    uint8_t *d_scnts = nullptr, *d_rcnts = nullptr;
+    void drop_send()
+    {
+        if (d_skeys)
+            (void)hipFree(d_skeys);
+        if (d_scnts)
+            (void)hipFree(d_scnts);
+        d_skeys = nullptr;
+        d_scnts = nullptr;
+    }
+    void drop_recv()
+    {
+        if (d_rkeys)
+            (void)hipFree(d_rkeys);
+        if (d_rcnts)
+            (void)hipFree(d_rcnts);
+        d_rkeys = nullptr;
+        d_rcnts = nullptr;
+    }
+};
+
+// what the three table entries ask of their arguments; `want_merged`: the counter must have been merged over this
+// communicator (spectrum, finish) / must not have been merged (merge)
+int table_args(const brx_comm *cm, const brx_counter_t *c, bool want_merged, const char *what)
+{
+    if (c->device != cm->device) {
+        set_error("%s: communicator on device %d, counter on %d", what, cm->device, c->device);
+        return BRX_ERR_ARG;
+    }
+    if (c->strategy != BRX_COUNT_TABLE) {
+        set_error("%s: the counter does not use the table count strategy (BRX_COUNT_TABLE)", what);
+        return BRX_ERR_UNSUPPORTED;
+    }
+    int w = 0, r = 0;
+    const bool merged = tab_merged(c, &w, &r);
+    if (want_merged && (!merged || w != cm->world || r != cm->rank)) {
+        if (merged)
+            set_error("%s: the counter was merged as rank %d of %d, the communicator is rank %d of %d", what, r, w, cm->rank, cm->world);
+        else
+            set_error("%s: the counter has not been merged (brx_exchange_table_merge comes first)", what);
+        return BRX_ERR_ARG;
+    }
+    if (!want_merged && merged) {
+        set_error("%s: the counter has been merged already; brx_counter_reset it before counting again", what);
+        return BRX_ERR_ARG;
+    }
+    return BRX_OK;
+}
+
+int table_merge_body(brx_comm *cm, brx_counter_t *c, hipStream_t s, TableJob &job)
+{
+    const int W = cm->world, me = cm->rank;
+    const double t_begin = now_ms();
+
+    // 1.-3. every entry of the table, own share included, into (keys, counts) grouped by owner; the table is freed
+    std::vector<uint64_t> send_counts(W, 0), recv_counts(W, 0), all((size_t)W * W, 0);
+    int local = tab_split_by_owner(c, W, s, &job.d_skeys, &job.d_scnts, send_counts.data());
+    if (local == BRX_OK)
+        local = grow((void **)&cm->d_tables, &cm->tables_cap, (uint64_t)W * W * 8, "send counts of every rank");
+    BRX_TRY(agree(cm, local, s));
+
+    // 4. everybody's send counts to everybody: every message size and the job's largest message follow
+    BRX_HIP(hipMemcpy(cm->d_tables + (size_t)me * W, send_counts.data(), (size_t)W * 8, hipMemcpyHostToDevice));
+    BRX_NCCL(g_rccl.AllGather(cm->d_tables + (size_t)me * W, cm->d_tables, W, ncclUint64, cm->comm, s)); // in place
+    BRX_HIP(hipMemcpyAsync(all.data(), cm->d_tables, (size_t)W * W * 8, hipMemcpyDeviceToHost, s));
+    BRX_HIP(hipStreamSynchronize(s));
+    uint64_t n_send = 0, n_recv = 0, biggest = 0;
+    for (int r = 0; r < W; r++) {
+        recv_counts[r] = all[(size_t)r * W + me];
+        n_recv += recv_counts[r];
+        n_send += send_counts[r];
+        for (int q = 0; q < W; q++)
+            biggest = std::max(biggest, all[(size_t)r * W + q]);
+    }
+
+    // 5. (key, count) pairs to their owners: two arrays, 9 bytes per entry
+    hipError_t e = hipMalloc((void **)&job.d_rkeys, (n_recv + 1) * 8);
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&job.d_rcnts, n_recv + 1);
+    if (e != hipSuccess) {
+        set_error("hipMalloc(%llu B, received table entries): %s", (unsigned long long)((n_recv + 1) * 9), hipGetErrorString(e));
+        local = BRX_ERR_NOMEM;
+    }
+    BRX_TRY(agree(cm, local, s));
+    const double t_a2a = now_ms();
+    BRX_TRY(all_to_all_v(cm, job.d_skeys, send_counts.data(), job.d_rkeys, recv_counts.data(), biggest, 8, ncclUint64, s));
+    BRX_TRY(all_to_all_v(cm, job.d_scnts, send_counts.data(), job.d_rcnts, recv_counts.data(), biggest, 1, ncclUint8, s));
+    BRX_HIP(hipStreamSynchronize(s));
+    const double t_a2a_done = now_ms();
+    job.drop_send();
+
+    // 6. the owner's table: a key comes at most once per source, its counts add up to 255.  The last status exchange
+    //    tells every rank whether the JOB has merged counters.
+    local = tab_load_pairs(c, job.d_rkeys, job.d_rcnts, n_recv, s);
+    job.drop_recv();
+    BRX_TRY(agree(cm, local, s));
+    tab_set_merged(c, W, me);
+    cm->stats[0] = (n_send - send_counts[me]) * 9;         // entry bytes sent over the links
+    cm->stats[1] = (n_recv - recv_counts[me]) * 9;         // entry bytes received
+    cm->stats[2] = n_recv;                                 // entries merged here
+    cm->stats[3] = cm->stats[4] = 0;                       // (brx_exchange_table_finish)
+    cm->stats[5] = (uint64_t)((t_a2a_done - t_a2a) * 1e3); // all-to-all, microseconds of host wall time
+    cm->stats[6] = (uint64_t)((now_ms() - t_begin) * 1e3); // whole call
+    cm->stats[7] = biggest;                                // largest single message, in entries
+    return BRX_OK;
+}
+
+int table_spectrum_body(brx_comm *cm, brx_counter_t *c, uint64_t *hist256, int local, hipStream_t s)
+{
+    const int W = cm->world, me = cm->rank;
+    if (local == BRX_OK)
+        local = grow((void **)&cm->d_tables, &cm->tables_cap, (uint64_t)W * 256 * 8, "spectrum of every rank");
+    uint64_t *mine = cm->d_tables + (size_t)me * 256;
+    if (local == BRX_OK && hipMemsetAsync(mine, 0, 256 * 8, s) != hipSuccess) {
+        set_error("exchange_spectrum: hipMemsetAsync failed");
+        local = BRX_ERR_HIP;
+    }
+    if (local == BRX_OK)
+        local = tab_spectrum(c, s, (unsigned long long *)mine);
+    BRX_TRY(agree(cm, local, s));
+    // (an all-gather and a host sum, not an all-reduce: 256 numbers, and exact whatever the transport reduces)
+    BRX_NCCL(g_rccl.AllGather(mine, cm->d_tables, 256, ncclUint64, cm->comm, s)); // in place
+    std::vector<uint64_t> all((size_t)W * 256);
+    BRX_HIP(hipMemcpyAsync(all.data(), cm->d_tables, (size_t)W * 256 * 8, hipMemcpyDeviceToHost, s));
+    BRX_HIP(hipStreamSynchronize(s));
+    uint64_t seen = 0;
+    for (int v = 1; v < 256; v++) {
+        hist256[v] = 0;
+        for (int r = 0; r < W; r++)
+            hist256[v] += all[(size_t)r * 256 + v];
+        seen += hist256[v];
+    }
+    hist256[0] = set_nbits(c->k) - seen; // every k-mer has one owner: the bins of the ranks count disjoint k-mers
+    return BRX_OK;
+}
+
+int table_finish_body(brx_comm *cm, brx_counter_t *c, uint8_t abundance, brx_set_t *dst, hipStream_t s, ExchangeJob &job)
+{
+    // this owner's solid k-mers (and their bits, for a set with a bit vector): all local work, one status
+    void *d_list = nullptr;
+    uint64_t n_mine = 0, n_all = 0;
+    int local = brx_set_count_finish_into(c, abundance, s, dst);
+    // (an owner whose table is empty leaves the valid, empty list without ever allocating one: nothing to take)
+    if (local == BRX_OK && !(dst->keylist_valid && !dst->d_keylist))
+        local = owned_list(dst, job, &d_list, &n_mine, s);
+    BRX_TRY(replicate_solid(cm, dst, d_list, n_mine, local, "list its solid k-mers", s, &n_all));
+    cm->stats[3] = n_mine; // solid k-mers this rank owns
+    cm->stats[4] = n_all;  // solid k-mers of the job (the other slots keep what the merge left)
+    return BRX_OK;
+}
+
+// the way into a collective entry: the lock is the caller's; BRX_OK = go on
+int enter_collective(brx_comm *cm)
+{
+    if (cm->dead) {
+        set_error("exchange: this communicator was aborted after a failure on this rank; make a new one");
+        return BRX_ERR_UNSUPPORTED;
+    }
+    cm->agreed_failure = false;
+    return BRX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int brx_exchange_table_owner(const uint64_t *hashes, uint64_t n, int world, uint32_t *owner_out)
+{
+    if (world < 1 || (n && (!hashes || !owner_out))) {
+        set_error("exchange_table_owner: bad argument (world %d)", world);
+        return BRX_ERR_ARG;
+    }
+    for (uint64_t i = 0; i < n; i++)
+        owner_out[i] = table_owner_of(hashes[i], (uint32_t)world);
+    return BRX_OK;
+}
+
+int brx_exchange_table_merge(brx_comm_t *cm, brx_counter_t *c, void *stream)
+{
+    if (!cm || !c) {
+        set_error("null argument");
+        return BRX_ERR_ARG;
+    }
+    BRX_TRY(use_device(cm->device));
+    std::lock_guard<std::mutex> g(cm->mu);
+    std::lock_guard<std::mutex> gc(c->mu);
+    BRX_TRY(enter_collective(cm));
+    hipStream_t s = (hipStream_t)stream;
+    // (argument faults are this rank's alone, yet the peers must not be left waiting -- nor take their tables apart for a
+    // merge that will not happen: an agreement of its own, before anything is touched)
+    BRX_TRY(agree(cm, table_args(cm, c, false, "exchange_table_merge"), s));
+    TableJob job;
+    const int rc = table_merge_body(cm, c, s, job);
+    if (rc != BRX_OK)
+        abort_after_local_failure(cm);
+    job.drop_send();
+    job.drop_recv();
+    if (rc != BRX_OK) { // the table was taken apart: what is left is an empty counter
+        const std::string msg = brx_last_error();
+        (void)hipStreamSynchronize(s);
+        (void)tab_reset(c, s);
+        set_error("%s", msg.c_str());
+    }
+    return rc;
+}
+
+int brx_exchange_spectrum(brx_comm_t *cm, brx_counter_t *c, uint64_t *hist256, void *stream)
+{
+    if (!cm || !c || !hist256) {
+        set_error("null argument");
+        return BRX_ERR_ARG;
+    }
+    BRX_TRY(use_device(cm->device));
+    std::lock_guard<std::mutex> g(cm->mu);
+    std::lock_guard<std::mutex> gc(c->mu);
+    BRX_TRY(enter_collective(cm));
+    const int rc = table_spectrum_body(cm, c, hist256, table_args(cm, c, true, "exchange_spectrum"), (hipStream_t)stream);
+    if (rc != BRX_OK)
+        abort_after_local_failure(cm);
+    return rc;
+}
+
+int brx_exchange_table_finish(brx_comm_t *cm, brx_counter_t *c, uint8_t abundance, brx_set_t *dst, void *stream)
+{
+    if (!cm || !c || !dst) {
+        set_error("null argument");
+        return BRX_ERR_ARG;
+    }
+    BRX_TRY(use_device(cm->device));
+    std::lock_guard<std::mutex> g(cm->mu);
+    std::lock_guard<std::mutex> gc(c->mu);
+    BRX_TRY(enter_collective(cm));
+    hipStream_t s = (hipStream_t)stream;
+    int local = table_args(cm, c, true, "exchange_table_finish");
+    if (local == BRX_OK && (dst->device != cm->device || dst->k != c->k)) {
+        set_error("exchange_table_finish: counter of k=%d on device %d, set of k=%d on device %d", c->k, c->device, dst->k, dst->device);
+        local = BRX_ERR_ARG;
+    }
+    BRX_TRY(agree(cm, local, s));
+    ExchangeJob job;
+    const int rc = table_finish_body(cm, c, abundance, dst, s, job);
+    if (rc != BRX_OK)
+        abort_after_local_failure(cm);
+    if (job.d_extracted) {
+        const std::string msg = rc != BRX_OK ? brx_last_error() : "";
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(job.d_extracted);
+        if (rc != BRX_OK)
+            set_error("%s", msg.c_str());
+    }
+    return rc;
 }
 
 } // extern "C"

@@ -175,6 +175,24 @@ struct brx_counter {
 namespace brx {
 // counting table of a BRX_COUNT_TABLE counter as a read-only lookup sees it (brx_counttable.hip)
 void tab_view(const brx_counter *c, const uint64_t **lines, const uint32_t **counts, uint32_t *log_lines, uint32_t *m);
+// The rank of a multi-GPU job that sums the counts of a k-mer (brx_exchange_table_merge): a multiplicative hash of the
+// k-mer's bit index (canonical >> 1) spread over `world` by the top-bits product, so neighbouring hashes part.  ONE
+// definition for the split kernel and for brx_exchange_table_owner; br_amd/dist.py table_owner states it in numpy.
+__host__ __device__ inline uint32_t table_owner_of(uint64_t hash, uint32_t world)
+{
+    return (uint32_t)((((hash * 0x9E3779B97F4A7C15ull) >> 32) * (uint64_t)world) >> 32);
+}
+// The table side of that merge (brx_counttable.hip).  split: every entry of the table into two arrays the call allocates
+// (keys u64 = bit indices, counts u8 = min(255, count)), grouped by owner, per_owner[r] entries for rank r in rank order;
+// the table is freed, the arrays are the caller's (hipFree; both nullptr when nothing was counted).  load_pairs: a fresh
+// table for `n` (key, count) pairs, counts of one key summed up to 255 -- the counter must hold no table (after split).
+// Both synchronise `s`.  set_merged / merged: the mark a merged counter carries until it is reset (world 0: not merged).
+int tab_split_by_owner(brx_counter *c, int world, hipStream_t s, uint64_t **d_keys, uint8_t **d_cnts, uint64_t *per_owner);
+int tab_load_pairs(brx_counter *c, const uint64_t *d_keys, const uint8_t *d_cnts, uint64_t n, hipStream_t s);
+void tab_set_merged(brx_counter *c, int world, int rank);
+bool tab_merged(const brx_counter *c, int *world, int *rank);
+int tab_reset(brx_counter *c, hipStream_t s);
+int tab_spectrum(brx_counter *c, hipStream_t s, unsigned long long *d_hist);
 // count view of a BRX_COUNT_SORTED counter (brx_partbuild.hip); the callers hold the counter's lock.  part_lookup_view:
 // false = no valid view; true with *keys == nullptr = nothing was counted
 int part_lookup_prepare(brx_counter *c, hipStream_t s);

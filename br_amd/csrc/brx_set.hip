@@ -1000,6 +1000,20 @@ int brx_counter_table_info(brx_counter_t *c, uint64_t *info4, void *stream)
     return tab_info(c, info4, (hipStream_t)stream);
 }
 
+int brx_counter_merge_state(brx_counter_t *c, int *world, int *rank)
+{
+    if (!c || !world)
+        return BRX_ERR_ARG;
+    *world = 0;
+    if (rank)
+        *rank = 0;
+    if (c->strategy == BRX_COUNT_TABLE) {
+        std::lock_guard<std::mutex> g(c->mu);
+        (void)tab_merged(c, world, rank);
+    }
+    return BRX_OK;
+}
+
 int brx_set_extract_keys_device(const brx_set_t *set, uint64_t first_hash, uint64_t n_hashes, uint64_t *d_out, uint64_t cap,
                                 uint64_t *n_out, void *stream)
 {

@@ -171,6 +171,35 @@ class AbiExchange:
         from . import _lib
         _lib.check(_lib.lib().brx_exchange_reduce_counts(self._h, counter._h, abundance, stream))
 
+    # ---- counted sets at k = 23..31 across ranks: counting tables merged by owner (include/brx.h) ----
+    def merge_table(self, counter, stream: Optional[int] = None) -> None:
+        """`counter` (COUNT_TABLE) has counted this rank's reads, in any number of batches; on return it is MERGED: it holds
+        the k-mers this rank owns (`table_owner`), each with min(255, its count over all ranks).  A failed merge leaves
+        an empty counter."""
+        from . import _lib
+        _lib.check(_lib.lib().brx_exchange_table_merge(self._h, counter._h, stream))
+
+    def spectrum(self, counter, stream: Optional[int] = None):
+        """uint64[256], the same on every rank: the spectrum one process would have computed over all the reads (what
+        br_amd.spectrum's threshold selectors take).  `counter` must be merged."""
+        import ctypes as C
+        import numpy as np
+        from . import _lib
+        h = np.zeros(256, dtype=np.uint64)
+        _lib.check(_lib.lib().brx_exchange_spectrum(self._h, counter._h, h.ctypes.data_as(C.POINTER(C.c_uint64)), stream))
+        return h
+
+    def finish_table(self, counter, solid, abundance: int, stream: Optional[int] = None) -> None:
+        """the solid set (count > abundance) of ALL ranks' reads into `solid`, from merged counters; the counter stays
+        merged: another spectrum or another threshold may follow"""
+        from . import _lib
+        _lib.check(_lib.lib().brx_exchange_table_finish(self._h, counter._h, abundance, solid._h, stream))
+
+    def build_table(self, counter, solid, abundance: int, stream: Optional[int] = None) -> None:
+        """merge_table + finish_table, for a host that knows its threshold"""
+        self.merge_table(counter, stream)
+        self.finish_table(counter, solid, abundance, stream)
+
     def last_stats(self) -> dict:
         import ctypes as C
         from . import _lib
@@ -191,6 +220,17 @@ class AbiExchange:
             self.close()
         except Exception:
             pass
+
+
+def table_owner(hashes, world: int):
+    """The rank that sums the counts of a k-mer in AbiExchange.merge_table (brx_exchange_table_owner, the same arithmetic):
+    `hashes` are bit indices (canonical k-mer >> 1); uint32 owners, every one < world."""
+    import numpy as np
+    if world < 1:
+        raise ValueError("world must be at least 1")
+    h = np.asarray(hashes, dtype=np.uint64)
+    hi = (h * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(32)           # (uint64 products wrap: mod 2^64)
+    return ((hi * np.uint64(world)) >> np.uint64(32)).astype(np.uint32)
 
 
 def shard_range(n_items: int, world: int, rank: int):

@@ -390,6 +390,13 @@ class Counter:
         _lib.check(_lib.lib().brx_counter_table_info(self._h, v, stream))
         return {"log2_lines": int(v[0]), "m": int(v[1]), "keys": int(v[2]), "peak_bytes": int(v[3])}
 
+    def merge_state(self) -> Tuple[int, int]:
+        """(world, rank) a table counter was merged over by AbiExchange.merge_table; world 0: not merged.  A merged counter
+        holds the k-mers its rank owns with the counts of the whole job, and takes no more reads until `reset()`"""
+        w, r = C.c_int(0), C.c_int(0)
+        _lib.check(_lib.lib().brx_counter_merge_state(self._h, C.byref(w), C.byref(r)))
+        return w.value, r.value
+
     def reset(self, stream: Optional[int] = None) -> None:
         _lib.check(_lib.lib().brx_counter_reset(self._h, stream))
 

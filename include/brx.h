@@ -212,8 +212,12 @@ int brx_set_cover_split_batch(const brx_set_t *set, const uint8_t *bases, const 
  * the keys are moved with their counts (add_batch_device may synchronise `stream` for that); past the largest table,
  * 2^30 lines (64 GiB of lines + 32 GiB of counters, 7.5 G slots), add_batch returns BRX_ERR_NOMEM.  finish lists the
  * keys with count > abundance in one pass and leaves an ordinary closed set: sparse for k >= 21, with its bit vector
- * written for k <= 19.  Single GPU: device_counts, load_counts, clamp, l1_view, add_partitioned_device and the
- * brx_exchange_* entries return BRX_ERR_UNSUPPORTED for such a counter.
+ * written for k <= 19.  device_counts, load_counts, clamp, l1_view, add_partitioned_device, brx_exchange_build_partitioned
+ * and brx_exchange_reduce_counts return BRX_ERR_UNSUPPORTED for such a counter; across GPUs it goes through
+ * brx_exchange_table_merge / _spectrum / _table_finish (below, "multi-GPU").  A MERGED counter holds the k-mers its rank
+ * owns with the counts of the whole job: add_batch[_device] and a second merge return BRX_ERR_ARG until brx_counter_reset
+ * reopens it; brx_counter_abundance_* and get_counts answer for the owned k-mers and 0 for all others (there is no
+ * abundance query across ranks); spectrum, finish and table_info describe the owned share.
  * BRX_COUNT_AUTO = DENSE below 15, SORTED for 15 <= k <= 21, TABLE for 23 <= k <= 31.                              */
 enum { BRX_COUNT_AUTO = 0, BRX_COUNT_DENSE = 1, BRX_COUNT_SORTED = 2, BRX_COUNT_TABLE = 3 };
 int brx_set_count_begin(uint8_t k, int device, int strategy, brx_counter_t **out);
@@ -249,6 +253,9 @@ int brx_counter_add_partitioned_device(brx_counter_t *c, const uint32_t *d_keys,
 /* table strategy only: [0] log2(lines) of the table (0: none yet), [1] its minimizer length, [2] distinct k-mers counted
  * (read back from the device: synchronises `stream`), [3] most bytes of table held at once (both tables during a regrow) */
 int brx_counter_table_info(brx_counter_t *c, uint64_t *info4, void *stream);
+/* *world, *rank (rank may be NULL) the counter was merged over by brx_exchange_table_merge; *world = 0 for a counter that is
+ * not merged (never merged, reset since, or of another strategy)                                                        */
+int brx_counter_merge_state(brx_counter_t *c, int *world, int *rank);
 void brx_counter_free(brx_counter_t *c);
 
 /* ---- abundance: how often the k-mers of a read were counted.  No counterpart in the reference ---------------------
@@ -340,8 +347,33 @@ int brx_exchange_reduce_counts(brx_comm_t *comm, brx_counter_t *c, uint8_t abund
  * any world size; there is no reference counterpart (one process, src/main.rs:30-33).                            */
 int brx_exchange_plan(const uint64_t *tables, int world, uint32_t n_buckets, int rank, uint32_t *bound, uint64_t *send_counts,
                       uint64_t *recv_counts, uint64_t *seg /* may be NULL */, uint64_t *largest_message /* may be NULL */);
+/* ---- counted sets across GPUs at any odd k up to 31: counting tables merged by owner -----------------------------------
+ * Every rank counts its shard into a BRX_COUNT_TABLE counter (any number of batches, none included), then all ranks make
+ * the three calls below together, in this order; spectrum and finish may be repeated (another threshold) on the merged
+ * counter.  Argument faults and local failures travel through a status exchange, so that all ranks return together.
+ *
+ * owner: the rank that sums a k-mer's counts.  hash = canonical k-mer >> 1 (the bit index every key list carries);
+ *   owner = ((((hash * 0x9E3779B97F4A7C15) mod 2^64) >> 32) * world) >> 32.  A pure function (no GPU, no communicator);
+ *   BRX_ERR_ARG for world < 1 or NULL pointers.                                                                         */
+int brx_exchange_table_owner(const uint64_t *hashes, uint64_t n, int world, uint32_t *owner_out);
+/* merge: every entry of the rank's table goes to its owner as a (u64 key, u8 count) pair -- 9 bytes per distinct k-mer,
+ * (world-1)/world of them over the links, in rounds whose messages stay under BRX_A2A_CHUNK x 4 bytes -- and the owner
+ * builds a fresh table with the sums.  On return `c` is MERGED: it holds exactly the k-mers this rank owns, each with
+ * min(255, sum over all ranks of the rank's count) (exact: min(255, sum of min(255, c_i)) = min(255, sum of c_i)).  The old
+ * table is freed before the new one is made: the peak is old table + 9 B per entry, then send + receive arrays + new table.
+ * If anything fails once the table has been taken apart the error is returned and `c` is left EMPTY (as after reset).     */
+int brx_exchange_table_merge(brx_comm_t *comm, brx_counter_t *c, void *stream);
+/* the job's spectrum from merged counters: every rank gets the same 256 numbers, what brx_counter_spectrum gives one
+ * process that counted all the reads (the ranks' bins 1..255 all-gathered and summed, bin 0 = 2^(2k-1) - the rest)      */
+int brx_exchange_spectrum(brx_comm_t *comm, brx_counter_t *c, uint64_t *hist256, void *stream);
+/* the job's solid set (count > abundance) from merged counters into `dst` on every rank: the owner lists its solid k-mers
+ * (and writes their bits when k <= 19), the lists go to everybody and are ORed into the bit vector / built into the probe
+ * index, as build_partitioned does.  `c` stays merged and untouched.                                                    */
+int brx_exchange_table_finish(brx_comm_t *comm, brx_counter_t *c, uint8_t abundance, brx_set_t *dst, void *stream);
 /* last build_partitioned: [0] key bytes sent, [1] received, [2] keys counted by this owner, [3] its solid k-mers,
- * [4] solid k-mers of the job, [5] all-to-all us, [6] whole call us, [7] largest single message (keys)          */
+ * [4] solid k-mers of the job, [5] all-to-all us, [6] whole call us, [7] largest single message (keys).
+ * After table_merge: [0] entry bytes sent over links, [1] received, [2] entries merged here, [3] = [4] = 0, [5] all-to-all
+ * us, [6] whole call us, [7] largest single message (entries); table_finish then sets [3] and [4] and leaves the rest.    */
 int brx_comm_last_stats(const brx_comm_t *comm, uint64_t *stats8);
 void brx_comm_free(brx_comm_t *comm);
 
