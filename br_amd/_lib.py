@@ -16,6 +16,7 @@ BRX_ERR_ARG = -1
 BRX_ERR_OVERFLOW = -7
 BRX_ERR_NODEVICE = -4
 BRX_ERR_UNSUPPORTED = -6
+BRX_ERR_FORMAT = -5
 
 METHOD_IDS = {"one": 0, "two": 1, "graph": 2, "greedy": 3, "gap_size": 4, "gap-size": 4}
 COUNT_AUTO, COUNT_DENSE, COUNT_SORTED, COUNT_TABLE = 0, 1, 2, 3
@@ -105,6 +106,12 @@ SIGNATURES = {
     "brx_counter_lookup_prepare": (C.c_int, [_vp, _vp]),
     "brx_counter_lookup_state": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "brx_counter_lookup_drop": (C.c_int, [_vp]),
+    "brx_sort_keys_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp]),
+    "brx_counter_save_fd": (C.c_int, [_vp, C.c_uint8, C.c_int, _u64p]),
+    "brx_counter_load_fd": (C.c_int, [_vp, C.c_int, _u64p]),
+    "brx_counter_floor": (C.c_int, [_vp, _u8p]),
+    "brx_set_save_fd": (C.c_int, [_vp, C.c_int, _u64p]),
+    "brx_set_load_fd": (C.c_int, [C.c_int, C.c_int, _pp, _u64p]),
     "brx_comm_unique_id": (C.c_int, [_vp]),
     "brx_comm_init": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _pp]),
     "brx_comm_init_all": (C.c_int, [C.c_int, C.POINTER(C.c_int), _pp]),

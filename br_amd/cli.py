@@ -24,6 +24,15 @@ Not in the reference, like `--device` (include/brx.h "coverage"; a base is cover
                                counted -- k-mers / absent / above the threshold / min / median / max / mean per read
                                (br_amd/abundance.py).  `fasta` then counts into the hash table (BRX_COUNT_TABLE) whatever
                                the k: the same set, a slower build
+    --save-set PATH            with any sub-command: write the set in use as a key file (br_amd/keyfile.py: sorted keys in
+                               blocks of 256, any odd k from 5 to 31) before the correction starts; `solid -i PATH -f keys`
+                               loads it again, no -k needed
+    --save-counts PATH         with `fasta` or `count`: write the k-mer counts as a key file with a count byte per key;
+                               `count -i PATH` loads it again (the magic is sniffed after decompression; anything else is
+                               still read as a pcon count table) and -a or a threshold selector follow as usual.  `fasta`
+                               then counts into the hash table whatever the k, as with --abundance-report: the same set
+    --save-min-count N         keep only the k-mers counted at least N times (default 1) in --save-counts.  A counter loaded
+                               from such a file no longer knows the rarer k-mers: thresholds below N - 1 are refused
     --second-pass MODE         reverse (default: the reference's second scan, reads reversed and not complemented),
                                revcomp (the second scan on the reverse complement: br_amd/strand.py) or none (= -s)
 """
@@ -37,7 +46,7 @@ import lzma
 import sys
 from typing import BinaryIO, List, Optional
 
-from . import _lib, abundance, fasta, spectrum, strand
+from . import _lib, abundance, fasta, keyfile, spectrum, strand
 from .correct import build_methods
 from .driver import run_correction
 from .set import Counter, Pcon
@@ -92,6 +101,18 @@ def abundance_reports(args):
     return paths
 
 
+def save_counts_of(args):
+    """the --save-counts path (or None): only where a counter is built"""
+    if args.save_counts is None:
+        if args.save_min_count is not None:
+            raise SystemExit("Error: --save-min-count goes with --save-counts")
+        return None
+    if args.subcommand not in ("fasta", "count"):
+        raise SystemExit("Error: --save-counts writes the k-mer counter, and `%s` builds its set without a counter: "
+                         "use it with `fasta` or `count` (--save-set writes the set)" % args.subcommand)
+    return args.save_counts
+
+
 def second_pass_of(args) -> str:
     """the second-pass mode of the parsed flags: --second-pass wins where given, -s means none, both must agree"""
     if args.two_side and args.second_pass not in (None, "none"):
@@ -144,6 +165,14 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--second-pass", choices=["reverse", "revcomp", "none"], default=None,
                    help="second scan of every read: reverse (default, the reference's), revcomp (on the reverse complement) "
                         "or none (what -s means) (not in the reference)")
+    p.add_argument("--save-set", default=None, metavar="PATH",
+                   help="write the set in use as a key file before the correction starts; `solid -i PATH -f keys` loads it "
+                        "(not in the reference)")
+    p.add_argument("--save-counts", default=None, metavar="PATH",
+                   help="write the k-mer counts as a key file; with `fasta` or `count` only; `count -i PATH` loads it.  `fasta` "
+                        "then counts into the hash table (BRX_COUNT_TABLE) whatever the k (not in the reference)")
+    p.add_argument("--save-min-count", type=u8, default=None, metavar="N",
+                   help="keep only the k-mers counted at least N times in --save-counts (default 1)")
     sub = p.add_subparsers(dest="subcommand", required=True)
 
     def abundance_methods(sp):
@@ -163,7 +192,7 @@ def parser() -> argparse.ArgumentParser:
     abundance_methods(f)
     s = sub.add_parser("solid", help="With Solid")
     s.add_argument("-i", "--input", dest="sub_input", required=True)
-    s.add_argument("-f", "--format", choices=["solid", "fasta", "fastq", "csv"], required=True)
+    s.add_argument("-f", "--format", choices=["solid", "fasta", "fastq", "csv", "keys"], required=True)
     s.add_argument("-k", "--kmer-size", type=int, default=None)
     lk = sub.add_parser("large-kmer", help="Large Kmer mode")
     lk.add_argument("-i", "--input", dest="sub_input", required=True)
@@ -198,13 +227,17 @@ def threshold_and_finish(cnt: Counter, args, keep: Optional[dict] = None) -> Pco
         thr = spectrum.get_threshold(cnt.spectrum(), args.abundance_selection, getattr(args, "percent", 0.0))
         if thr is None:
             raise SystemExit("Error: Can't compute minimal abundance")                  # error.rs ComputeAbundanceThreshold
+    if thr < cnt.floor - 1:
+        raise SystemExit("Error: the counts were saved with --save-min-count %d: k-mers seen fewer times are not in the file, so the "
+                         "set of abundance %d would miss members; the lowest threshold it supports is %d"
+                         % (cnt.floor, thr, cnt.floor - 1))
     if keep is not None:
         keep.update(counter=cnt, threshold=thr)
     return cnt.finish(thr)
 
 
 def build_set(args, keep: Optional[dict] = None) -> Pcon:
-    """keep (a dict, --abundance-report): the counter is left in it, and `fasta` counts into the hash table, whose counts
+    """keep (a dict, --abundance-report / --save-counts): the counter is left in it, and `fasta` counts into the hash table, whose counts
     can be looked up at every k.  (The partitioned counter of 15 <= k <= 21 answers too once Counter.prepare_lookup has
     built its count view, but count + view + lookup measured slower there than the table's count + lookup: DESIGN.md
     section 10.11, tools/partition_lookup_bench.py)"""
@@ -223,13 +256,26 @@ def build_set(args, keep: Optional[dict] = None) -> Pcon:
         if args.format == "solid":
             with open_input(args.sub_input) as f:
                 return Pcon.from_pcon_solid(f.read(), dev)
+        if args.format == "keys":  # a key file carries its k
+            with open_input(args.sub_input) as f:
+                try:
+                    return Pcon.from_keyfile(f, dev)
+                except _lib.BrxError as e:
+                    raise SystemExit(f"Error: {args.sub_input}: {e}")
         if args.kmer_size is None:
             raise SystemExit("Error: Solid input fasta require kmer size")            # error.rs SolidRequireKmerSize
         return presence_set(args.sub_input, args.format, args.kmer_size, dev)
     if args.subcommand == "count":
         # src/main.rs:59-70: Counter::from_stream, then the same threshold -> Solid::from_count as `fasta`
+        # a key file (--save-counts) is told from a pcon table by its magic, after decompression
         with open_input(args.sub_inputs) as f:
-            cnt = Counter.from_count_stream(f, dev)
+            if keyfile.is_keyfile(f.peek(8)[:8]):
+                try:
+                    cnt = Counter.from_keyfile(f, dev)
+                except _lib.BrxError as e:
+                    raise SystemExit(f"Error: {args.sub_inputs}: {e}")
+            else:
+                cnt = Counter.from_count_stream(f, dev)
         return threshold_and_finish(cnt, args, keep)
     # large-kmer -f fasta: set::Hash::from_fasta (src/set/hash.rs:40-60, src/main.rs:147-163) = every canonical k-mer of
     # every record, no counting.  Same membership as a presence-only Pcon; for k >= 21 the set is sparse (a chained
@@ -281,16 +327,26 @@ def main(argv: Optional[List[str]] = None) -> int:
     mode, split_min, report_paths = output_form(args)
     second_pass = second_pass_of(args)
     abund_paths = abundance_reports(args)
-    if abund_paths is None:
+    counts_path = save_counts_of(args)
+    if abund_paths is None and counts_path is None:
         kmer_set = build_set(args)
     else:
         # the threshold is known, nothing is corrected yet: the reads to be corrected, asked about their k-mers' counts
         kept: dict = {}
         kmer_set = build_set(args, kept)
-        for src, dst in zip(args.inputs, abund_paths):
+        if counts_path is not None:
+            try:
+                with open(counts_path, "wb") as f:
+                    kept["counter"].save(f, 1 if args.save_min_count is None else args.save_min_count)
+            except _lib.BrxError as e:
+                raise SystemExit(f"Error: --save-counts: {e}")
+        for src, dst in zip(args.inputs, abund_paths or []):
             with open_input(src) as f, open(dst, "wb") as rep:
                 write_abundance_report(kept["counter"], kept["threshold"], f, rep, args.record_buffer or 8192)
         kept.clear()  # (the counter's memory goes back before the correction starts)
+    if args.save_set is not None:
+        with open(args.save_set, "wb") as f:
+            kmer_set.save_keys(f)
     names = args.corrections or METHOD_NAMES                          # src/cli.rs:121-131: all five by default
     confirm = 5 if args.confirm is None else args.confirm            # src/cli.rs:135-137
     max_search = 7 if args.max_search is None else args.max_search   # src/cli.rs:140-142

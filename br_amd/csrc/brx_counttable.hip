@@ -37,6 +37,9 @@ struct TabState {
     // after brx_exchange_table_merge: the table holds the k-mers this rank owns, with the counts of the whole job; nothing
     // more can be counted into it until the counter is reset (merged_world 0: an ordinary counter)
     int merged_world = 0, merged_rank = 0;
+    // after brx_counter_load_fd of a file that kept only counts >= floor: the k-mers seen fewer times are unknown, so
+    // nothing can be added and no set with a threshold below floor - 1 can be finished until the counter is reset
+    uint8_t floor = 1;
 };
 
 } // namespace brx
@@ -331,6 +334,7 @@ int tab_reset(brx_counter *c, hipStream_t s)
     BRX_HIP(hipMemsetAsync(t->d_nkeys, 0, 8, s));
     t->keys_known = t->pending = t->bases_total = 0;
     t->merged_world = t->merged_rank = 0;
+    t->floor = 1;
     return BRX_OK;
 }
 
@@ -340,6 +344,11 @@ int tab_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offs
     if (t->merged_world) {
         set_error("counting table: the counter was merged over %d ranks and holds the job's counts of the k-mers rank %d owns; "
                   "brx_counter_reset it before counting again", t->merged_world, t->merged_rank);
+        return BRX_ERR_ARG;
+    }
+    if (t->floor > 1) {
+        set_error("counting table: the counter was loaded from a key file that kept only counts from %d up; brx_counter_reset it "
+                  "before counting again", (int)t->floor);
         return BRX_ERR_ARG;
     }
     if (!n_reads || !total_bases)
@@ -364,6 +373,11 @@ int tab_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offs
 int tab_finish_into(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set *dst)
 {
     TabState *t = c->tab;
+    if (t->floor > 1 && abundance + 1u < t->floor) {
+        set_error("counting table: the counter was loaded from a key file that kept only counts from %d up: a set of the k-mers seen more "
+                  "than %u times would miss members (thresholds from %d up can be finished)", (int)t->floor, abundance, (int)t->floor - 1);
+        return BRX_ERR_ARG;
+    }
     if (t->pending)
         BRX_TRY(read_keys(t, s));
     if (!dst->d_keylist_n)
@@ -492,6 +506,39 @@ int tab_load_pairs(brx_counter *c, const uint64_t *d_keys, const uint8_t *d_cnts
     t->bases_total = sum; // a key listed by finish has a count above `abundance`: tab_finish_into's bound on the list holds
     return BRX_OK;
 }
+
+// tab_load_pairs for a counter that may hold k-mers already (brx_counter_load_fd): the table is regrown for the k-mers
+// known plus n, then every pair is found or claimed and its count added up to 255
+int tab_merge_pairs(brx_counter *c, const uint64_t *d_keys, const uint8_t *d_cnts, uint64_t n, hipStream_t s)
+{
+    TabState *t = c->tab;
+    if (!n)
+        return BRX_OK;
+    if (t->pending)
+        BRX_TRY(read_keys(t, s));
+    if (!t->d_lines || !fits_half(t->log_lines, t->keys_known + n))
+        BRX_TRY(regrow(c, t->keys_known + n, s)); // every pair could be a key of its own
+    DevScratch ws;
+    unsigned long long *d_sum = nullptr;
+    BRX_TRY(ws.get(&d_sum, 1));
+    BRX_HIP(hipMemsetAsync(d_sum, 0, 8, s));
+    {
+        KernelTimer kt("tab_merge", s);
+        table_merge_kernel<<<read_grid((n + 255ull) / 256ull, 256u * 16u), 256, 0, s>>>(d_keys, d_cnts, n, c->k, set_nbits(c->k), t->d_lines,
+                                                                                       t->d_counts, 32u - t->log_lines, t->m,
+                                                                                       (uint32_t)c->k - t->m + 1u, t->d_nkeys, d_sum);
+        BRX_HIP(hipGetLastError());
+    }
+    unsigned long long sum = 0;
+    BRX_HIP(hipMemcpyAsync(&sum, d_sum, 8, hipMemcpyDeviceToHost, s));
+    BRX_TRY(read_keys(t, s));
+    t->bases_total += sum; // (the counts in the table add up to no more: tab_finish_into's bound on the list holds)
+    return BRX_OK;
+}
+
+uint8_t tab_floor(const brx_counter *c) { return c->tab ? c->tab->floor : 1; }
+
+void tab_set_floor(brx_counter *c, uint8_t floor) { c->tab->floor = floor ? floor : 1; }
 
 void tab_set_merged(brx_counter *c, int world, int rank)
 {

@@ -189,6 +189,15 @@ __host__ __device__ inline uint32_t table_owner_of(uint64_t hash, uint32_t world
 // Both synchronise `s`.  set_merged / merged: the mark a merged counter carries until it is reset (world 0: not merged).
 int tab_split_by_owner(brx_counter *c, int world, hipStream_t s, uint64_t **d_keys, uint8_t **d_cnts, uint64_t *per_owner);
 int tab_load_pairs(brx_counter *c, const uint64_t *d_keys, const uint8_t *d_cnts, uint64_t n, hipStream_t s);
+// Key files (brx_keyfile.hip).  merge_pairs: load_pairs for a counter that may hold k-mers already -- the table is regrown for
+// the k-mers known plus n, counts add up to 255; synchronises `s`.  floor: f > 1 after a count file that kept only counts
+// >= f was loaded (finish below f - 1 and add_batch refuse until the counter is reset), 1 otherwise.  tab_info: what
+// brx_counter_table_info reports.  set_alloc_unwritten (brx_set.hip): a set of this k with nothing written yet.
+int tab_merge_pairs(brx_counter *c, const uint64_t *d_keys, const uint8_t *d_cnts, uint64_t n, hipStream_t s);
+uint8_t tab_floor(const brx_counter *c);
+void tab_set_floor(brx_counter *c, uint8_t floor);
+int tab_info(brx_counter *c, uint64_t *info4, hipStream_t s);
+int set_alloc_unwritten(int k, int device, brx_set **out);
 void tab_set_merged(brx_counter *c, int world, int rank);
 bool tab_merged(const brx_counter *c, int *world, int *rank);
 int tab_reset(brx_counter *c, hipStream_t s);

@@ -368,6 +368,8 @@ int tab_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offs
 int tab_finish_into(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set *dst);
 int tab_spectrum(brx_counter *c, hipStream_t s, unsigned long long *d_hist);
 int tab_info(brx_counter *c, uint64_t *info4, hipStream_t s);
+// a set of this k with nothing written yet (brx_set_load_fd fills it from a key list)
+int set_alloc_unwritten(int k, int device, brx_set **out) { return alloc_set(k, device, false, out); }
 // used by the correction chain and the host-pointer entry points
 int upload_batch(const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, uint8_t **d_bases, uint64_t *bases_cap,
                  uint64_t **d_off, uint64_t *off_cap, uint64_t *total, hipStream_t stream)

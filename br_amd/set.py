@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import gzip
+import io
 from typing import Iterable, Optional, Sequence, Tuple
 
 import numpy as np
@@ -34,6 +35,18 @@ def seq2bit(seq: bytes) -> int:
     for c in seq:
         k = (k << 2) | ((c >> 1) & 3)
     return k
+
+
+def _keyfile_stats(st) -> dict:
+    """stats8 of the key-file entries (include/brx.h "key files")"""
+    return {"keys": int(st[0]), "bytes": int(st[1]), "blocks": int(st[2]), "max_width": int(st[3]), "ns_list_sort": int(st[4]),
+            "ns_pack": int(st[5]), "ns_fd": int(st[6]), "ns_wall": int(st[7])}
+
+
+def sort_keys_device(d_keys: int, d_payload: Optional[int], n: int, key_bits: int, stream: Optional[int] = None) -> None:
+    """stable radix sort of n u64 keys on the device by their low key_bits bits, a payload byte per key moving along
+    (brx_sort_keys_device)"""
+    _lib.check(_lib.lib().brx_sort_keys_device(d_keys, d_payload, n, key_bits, stream))
 
 
 class KmerSet:
@@ -119,6 +132,28 @@ class Pcon(KmerSet):
         if chunk:
             c.add_reads(chunk)
         return c.finish(abundance)
+
+    @classmethod
+    def from_keyfile(cls, f, device: int = 0) -> "Pcon":
+        """the set of a key file (br_amd/keyfile.py; binary file object, any compression already undone): k from the header,
+        every key listed a member -- the counts of a count file are ignored (brx_set_load_fd)"""
+        from . import hostio
+        h = C.c_void_p()
+        st = (C.c_uint64 * 8)()
+        with hostio.input_fd(f) as fd:
+            _lib.check(_lib.lib().brx_set_load_fd(fd, device, C.byref(h), st))
+        s = cls(h.value, device)
+        s.keyfile_stats = _keyfile_stats(st)
+        return s
+
+    def save_keys(self, f) -> dict:
+        """write the set as a key file to the binary file object `f`: sorted keys, whatever holds the set (brx_set_save_fd);
+        the set is left as it was, a lazy bit vector stays lazy"""
+        from . import hostio
+        st = (C.c_uint64 * 8)()
+        with hostio.output_fd(f) as fd:
+            _lib.check(_lib.lib().brx_set_save_fd(self._h, fd, st))
+        return _keyfile_stats(st)
 
     # ---- KmerSet ----------------------------------------------------------------------
     def get(self, kmer: int) -> bool:
@@ -345,6 +380,53 @@ class Counter:
     def load_counts(self, first: int, counts: bytes) -> None:
         """overwrite counters [first, first + len(counts)) of a dense counter (`br count`: a table counted elsewhere)"""
         _lib.check(_lib.lib().brx_counter_load_counts(self._h, first, bytes(counts), len(counts)))
+
+    # ---- key files (include/brx.h "key files", br_amd/keyfile.py) -----------------------------------------------------
+    def save(self, f, min_count: int = 1) -> dict:
+        """write the k-mers counted at least min_count times, with min(255, count), as a key file to the binary file object
+        `f` (brx_counter_save_fd: table strategy).  The counter is left as it was"""
+        from . import hostio
+        _check_u8(min_count, "min_count")
+        st = (C.c_uint64 * 8)()
+        with hostio.output_fd(f) as fd:
+            _lib.check(_lib.lib().brx_counter_save_fd(self._h, min_count, fd, st))
+        return _keyfile_stats(st)
+
+    def load(self, f) -> dict:
+        """ADD the counts of a count file (binary file object) to this counter: counts of one k-mer sum and saturate at 255
+        (brx_counter_load_fd).  A file saved with min_count > 1 loads into an empty counter only and floors it"""
+        from . import hostio
+        st = (C.c_uint64 * 8)()
+        with hostio.input_fd(f) as fd:
+            _lib.check(_lib.lib().brx_counter_load_fd(self._h, fd, st))
+        return _keyfile_stats(st)
+
+    @classmethod
+    def from_keyfile(cls, f, device: int = 0) -> "Counter":
+        """a table counter holding the counts of a count file; k from the header.  `f` must be able to hand the 32 header
+        bytes back (seekable or with peek(), like everything cli.open_input returns)"""
+        from . import keyfile
+        if hasattr(f, "peek") and len(f.peek(keyfile.HEADER_BYTES)) >= keyfile.HEADER_BYTES:
+            head = f.peek(keyfile.HEADER_BYTES)[:keyfile.HEADER_BYTES]
+        else:
+            at = f.tell()
+            head = f.read(keyfile.HEADER_BYTES)
+            f.seek(at)
+        try:
+            k = keyfile.peek(io.BytesIO(head))["k"]
+        except ValueError as e:
+            raise _lib.BrxError(_lib.BRX_ERR_FORMAT, str(e))
+        cnt = cls(k, device, _lib.COUNT_TABLE)
+        cnt.load(f)
+        return cnt
+
+    @property
+    def floor(self) -> int:
+        """f > 1 after a count file saved with min_count f was loaded: k-mers seen fewer times are unknown, finish() needs
+        a threshold of at least f - 1 and nothing more can be added until reset(); 1 otherwise"""
+        v = C.c_uint8(0)
+        _lib.check(_lib.lib().brx_counter_floor(self._h, C.byref(v)))
+        return int(v.value)
 
     @classmethod
     def from_count_stream(cls, f, device: int = 0, chunk: int = 64 << 20) -> "Counter":

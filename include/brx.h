@@ -51,7 +51,7 @@ typedef enum brx_status {
     BRX_ERR_NOMEM = -2,       /* host or device allocation failed                      */
     BRX_ERR_HIP = -3,         /* a HIP runtime call failed                             */
     BRX_ERR_NODEVICE = -4,    /* no usable GPU: the product path has no CPU fallback   */
-    BRX_ERR_FORMAT = -5,      /* malformed .solid stream (error.rs: wraps pcon errors) */
+    BRX_ERR_FORMAT = -5,      /* malformed .solid stream or key file (error.rs: wraps pcon errors) */
     BRX_ERR_UNSUPPORTED = -6, /* valid in the reference, not yet implemented here      */
     BRX_ERR_OVERFLOW = -7     /* caller-provided output buffer too small               */
 } brx_status;
@@ -107,7 +107,7 @@ int brx_set_popcount(const brx_set_t *set, uint64_t *n_set_bits);
  * Such a set holds its solid k-mers only as a key list and as the probe index (exact, overflowing lines chain
  * into the next line).  get / get_batch / popcount / count_finish[_into] / the correction entry points work;
  * entries that need the bit vector (.solid import/export, set, insert_batch, device_bits, extract/or_keys)
- * return BRX_ERR_UNSUPPORTED.  Sets are built by the partitioned counter (k <= 21).                          */
+ * return BRX_ERR_UNSUPPORTED (such a set goes to disk as a key file: brx_set_save_fd / brx_set_load_fd).  Sets are built by the partitioned counter (k <= 21).                          */
 int brx_set_sparse(const brx_set_t *set);
 /* 0: the bit vector is in HBM and current; 1: LAZY -- a partitioned brx_set_count_finish[_into] listed the solid
  * hashes and left the 2^(2k-4)-byte vector unwritten (16 GiB at k = 19); it is materialised by the first entry
@@ -311,6 +311,55 @@ int brx_counter_get_counts(brx_counter_t *c, const uint64_t *forward_kmers, uint
 int brx_counter_lookup_prepare(brx_counter_t *c, void *stream);
 int brx_counter_lookup_state(brx_counter_t *c, int *state);
 int brx_counter_lookup_drop(brx_counter_t *c);
+
+/* ---- key files: k-mer counts and solid sets on disk at any odd k.  No counterpart in the reference ----------------------
+ * The reference keeps a set as a .solid file -- the 2^(2k-1)-bit vector, 256 GiB at k = 21 -- and counts as pcon's table of
+ * 2^(2k-1) bytes.  A KEY FILE holds the sorted keys (canonical k-mer >> 1, the bit index every key list carries), optionally
+ * with one count byte each, for odd k from 5 to 31: a 32-byte header (magic "BRXKMERS", version, k, flags, floor, 256 keys per
+ * block, number of keys, sum of the keys mod 2^64 = brx_set_fingerprint's out3[1]) and blocks of 256 keys -- first key, a
+ * width byte, the differences to the key before minus one packed at that width, the count bytes.  br_amd/keyfile.py states
+ * the format in numpy; the encoding is canonical, so equal contents give equal bytes.  Listing, sorting, packing and
+ * unpacking run on the GPU (profile timers "key_list", "key_sort", "key_pack", "key_unpack", then the existing "tab_merge" /
+ * "index_insert"); the file passes through two page-locked pieces of BRX_KEYFILE_SLICE_KB KiB (default 8192), never through
+ * one host allocation of its size.  Descriptors are read and written sequentially, without seeks: a pipe to or from a
+ * compressor works, as with brx_count_fasta_fd.  A malformed stream is BRX_ERR_FORMAT with a message naming the cause (wrong
+ * magic / version / block size, k even or out of range, a key >= 2^(2k-1), a count of 0 or below the floor, blocks out of
+ * order, a key sum that does not match, a truncated stream, trailing bytes); an I/O error is BRX_ERR_ARG.
+ * stats8 (may be NULL): [0] keys, [1] file bytes, [2] blocks, [3] largest width, [4] ns listing + sorting (load: merging
+ * into the table / building the set), [5] ns packing or unpacking, [6] ns reading or writing the fd, [7] ns wall.
+ *
+ * Stable LSD radix sort of n keys by their low key_bits bits (1..64; higher bits are ignored and carried along), 8-bit
+ * digits, ceil(key_bits / 8) passes; d_payload (may be NULL) holds one byte per key that moves with it.  Every pass is a
+ * histogram, a scan and a scatter in launches of their own: no workgroup waits for another.  Scratch (a second key and
+ * payload array, n / 2 bytes of histograms) comes from the device pool; returns after `stream` has been synchronised.    */
+int brx_sort_keys_device(uint64_t *d_keys, uint8_t *d_payload /* may be NULL */, uint64_t n, uint32_t key_bits, void *stream);
+/* The count file of a BRX_COUNT_TABLE counter: every k-mer with min(255, count) >= max(min_count, 1, the counter's floor),
+ * with that count.  The counter is only read: spectrum, finish, abundance and get_counts answer afterwards what they did
+ * before.  Dense and partitioned counters, and a counter merged across ranks (brx_counter_merge_state world != 0), return
+ * BRX_ERR_UNSUPPORTED.  Takes the counter's lock and works on the counter's own stream.                                    */
+int brx_counter_save_fd(brx_counter_t *c, uint8_t min_count /* 0 means 1 */, int out_fd, uint64_t *stats8);
+/* ADDS the counts of a count file to a BRX_COUNT_TABLE counter of the same k (BRX_ERR_ARG otherwise): the table is regrown
+ * for the k-mers it holds plus the file's, counts add and saturate at 255 -- loading the files of shards counted separately
+ * gives the counter of all their reads, as brx_exchange_table_merge does across GPUs.  A set file (no counts) is
+ * BRX_ERR_FORMAT; strategies and merged counters as for save.  A file saved with min_count f > 1 no longer knows the
+ * k-mers seen fewer than f times: it loads only into an EMPTY counter (BRX_ERR_ARG otherwise), which is then FLOORED at f
+ * until brx_counter_reset -- brx_set_count_finish[_into] with abundance < f - 1 (the set would miss members),
+ * add_batch[_device] and a further load return BRX_ERR_ARG, spectrum bins 1..f-1 read 0, a save writes floor max(f,
+ * min_count).  Files with floor 1 merge freely.  A load that fails once the stream is being read (BRX_ERR_FORMAT, I/O,
+ * memory) leaves the counter RESET -- empty, floor 1, usable -- and says so in the message, never half loaded; an argument
+ * fault (k, floor) leaves it as it was.                                                                                    */
+int brx_counter_load_fd(brx_counter_t *c, int in_fd, uint64_t *stats8);
+/* *floor = f for a counter floored by brx_counter_load_fd, 1 otherwise (any strategy)                                     */
+int brx_counter_floor(brx_counter_t *c, uint8_t *floor);
+/* The set file (keys, no counts, floor 0) of any set of odd 5 <= k <= 31, whatever holds it: a valid key list is used as it
+ * is, a sparse set built by insertion lists the lines of its table, a bit vector its bits; the keys are sorted on the way.
+ * The set is only read: a lazy bit vector stays lazy (brx_set_bits_state unchanged), the probe index stays.                */
+int brx_set_save_fd(const brx_set_t *set, int out_fd, uint64_t *stats8);
+/* A new closed set on `device` from a key file of either kind (the counts of a count file are checked and ignored: every key
+ * listed is a member), k from the header.  k >= 21: a sparse set, its key list attached and its chained probe index built;
+ * k <= 19: the key list attached as after a counted finish (k >= 15) and the bit vector written.  get, get_batch,
+ * popcount, fingerprint, .solid export (k <= 19), cover and correction answer as for the set that was saved.               */
+int brx_set_load_fd(int in_fd, int device, brx_set_t **out, uint64_t *stats8);
 
 /* ---- multi-GPU: reads shard over the GPUs, the set is exchanged ONCE -----------------------------
  * The reference is one process with rayon threads over shared memory (src/main.rs:30-33, src/lib.rs:72-139); on N
