@@ -356,7 +356,9 @@ int brx_counter_abundance_batch_device(brx_counter_t *c, const uint8_t *d_bases,
     BRX_TRY(abund_check("brx_counter_abundance_batch_device", c, d_bases, d_offsets, n_reads, total_bases));
     BRX_TRY(use_device(c->device));
     std::lock_guard<std::mutex> g(c->mu);
-    return abund_batch_locked(c, d_bases, d_offsets, n_reads, total_bases, abundance, d_profile, d_hist, d_stats, (hipStream_t)stream);
+    BRX_TRY(abund_batch_locked(c, d_bases, d_offsets, n_reads, total_bases, abundance, d_profile, d_hist, d_stats, (hipStream_t)stream));
+    BRX_HIP(counter_mark(c, (hipStream_t)stream)); // (the counts are still being read on `stream`)
+    return BRX_OK;
 }
 
 int brx_counter_abundance_batch(brx_counter_t *c, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
@@ -392,6 +394,7 @@ int brx_counter_abundance_batch(brx_counter_t *c, const uint8_t *bases, const ui
     if (stats)
         BRX_TRY(sc.get(&d_stats, n_reads));
     hipStream_t s = c->stream;
+    BRX_HIP(counter_join(c, c->stream));
     auto run = [&]() -> int {
         if (total)
             BRX_HIP(hipMemcpyAsync(d_bases, bases, total, hipMemcpyHostToDevice, s));
@@ -432,6 +435,7 @@ int brx_counter_get_counts(brx_counter_t *c, const uint64_t *forward_kmers, uint
     BRX_TRY(sc.get(&d_k, n));
     BRX_TRY(sc.get(&d_o, n));
     hipStream_t s = c->stream;
+    BRX_HIP(counter_join(c, c->stream));
     auto run = [&]() -> int {
         BRX_HIP(hipMemcpyAsync(d_k, forward_kmers, (uint64_t)n * 8, hipMemcpyHostToDevice, s));
         BRX_TRY(abund_get_counts(c, d_k, n, d_o, s));

@@ -307,7 +307,7 @@ int tab_begin(brx_counter *c)
     TabState *t = new TabState();
     c->tab = t;
     BRX_HIP(hipMalloc((void **)&t->d_nkeys, 8));
-    BRX_HIP(hipMemset(t->d_nkeys, 0, 8));
+    BRX_HIP(zero_now(t->d_nkeys, 8)); // (done on return: the first batch may come on any stream)
     return BRX_OK;
 }
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdarg.h>
+#include <atomic>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -42,6 +43,17 @@ hipError_t dev_alloc(void **out, size_t bytes);
 hipError_t dev_free(void *p);
 void dev_pool_trim();
 size_t dev_pool_bytes();
+
+// zeroes memory of an object under construction and returns when that is done, so that the object can be used on any
+// stream at once (a plain hipMemset of device memory is only enqueued on the null stream, and neither the caller's
+// non-blocking streams nor the library's own wait for that one).  Synchronising the null stream also waits for whatever the
+// host has queued on it and on its blocking streams: heavier than the memset needs, accepted in a constructor -- sets have
+// no stream of their own to zero on.
+inline hipError_t zero_now(void *p, size_t bytes)
+{
+    const hipError_t e = hipMemsetAsync(p, 0, bytes, nullptr);
+    return e == hipSuccess ? hipStreamSynchronize(nullptr) : e;
+}
 
 // BRX_TRACE=1: synchronise `s` and print a time-stamped stage name on stderr (finding where a big job stalls)
 void trace_stage(hipStream_t s, const char *what);
@@ -169,8 +181,31 @@ struct brx_counter {
     // counting-table strategy (brx_counttable.hip)
     brx::TabState *tab = nullptr;
     hipStream_t stream; // owned, used by host-pointer entry points
+    // what a stream-taking entry last enqueued on the caller's stream (include/brx.h "streams"): recorded by
+    // counter_mark, waited for in counter_join by the stream a host-pointer entry works on, before it touches the counter
+    hipEvent_t ev = nullptr;
+    std::atomic<bool> ev_pending{false};
     std::mutex mu;
 };
+
+namespace brx {
+inline hipError_t counter_mark(brx_counter *c, hipStream_t s)
+{
+    if (!c->ev || s == c->stream)
+        return hipSuccess;
+    const hipError_t e = hipEventRecord(c->ev, s);
+    if (e == hipSuccess)
+        c->ev_pending = true;
+    return e;
+}
+// `on`: the stream the host-pointer entry works on -- the counter's own, or the null stream (brx_counter_load_counts)
+inline hipError_t counter_join(brx_counter *c, hipStream_t on)
+{
+    if (!c->ev_pending.exchange(false))
+        return hipSuccess;
+    return hipStreamWaitEvent(on, c->ev, 0);
+}
+}
 
 namespace brx {
 // counting table of a BRX_COUNT_TABLE counter as a read-only lookup sees it (brx_counttable.hip)

@@ -1045,6 +1045,7 @@ int brx_counter_save_fd(brx_counter_t *c, uint8_t min_count, int out_fd, uint64_
     std::lock_guard<std::mutex> g(c->mu);
     BRX_TRY(table_counter_only(me, c));
     hipStream_t s = c->stream;
+    BRX_HIP(counter_join(c, c->stream));
     const uint8_t have = tab_floor(c);
     if (min_count < 1)
         min_count = 1;
@@ -1106,6 +1107,7 @@ int brx_counter_load_fd(brx_counter_t *c, int in_fd, uint64_t *stats8)
     std::lock_guard<std::mutex> g(c->mu);
     BRX_TRY(table_counter_only(me, c));
     hipStream_t s = c->stream;
+    BRX_HIP(counter_join(c, c->stream)); // a reset still queued on the caller's stream comes first
     if (tab_floor(c) > 1) {
         set_error("%s: the counter holds a file that kept only counts from %d up; brx_counter_reset it before loading another", me,
                   (int)tab_floor(c));

@@ -1203,6 +1203,7 @@ int brx_count_fasta_fd(brx_counter_t *c, int in_fd, uint32_t max_batch_records, 
         return BRX_ERR_ARG;
     }
     BRX_TRY(use_device(c->device));
+    BRX_HIP(counter_join(c, c->stream)); // a reset still queued on the caller's stream comes first
     return stream_fasta_batches(c->device, in_fd, max_batch_records, c->stream, stats8,
                                 [&](const uint8_t *d_b, const uint64_t *d_o, uint32_t n, uint64_t total, hipStream_t st_) {
                                     return brx_set_count_add_batch_device(c, d_b, d_o, n, total, st_);

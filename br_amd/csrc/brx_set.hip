@@ -305,7 +305,7 @@ int alloc_set(int k, int device, bool zero, brx_set **out, bool sparse = false)
         s->nwords = 0;
         hipError_t e = hipMalloc((void **)&s->d_keylist_n, 8);
         if (e == hipSuccess)
-            e = hipMemset(s->d_keylist_n, 0, 8);
+            e = zero_now(s->d_keylist_n, 8);
         if (e != hipSuccess) {
             set_error("sparse set alloc: %s", hipGetErrorString(e));
             delete s;
@@ -322,7 +322,7 @@ int alloc_set(int k, int device, bool zero, brx_set **out, bool sparse = false)
         return BRX_ERR_NOMEM;
     }
     if (zero) {
-        e = hipMemset(s->d_bits, 0, s->nwords * 4);
+        e = zero_now(s->d_bits, s->nwords * 4); // (done on return: the first insert may come on any stream)
         if (e != hipSuccess) {
             set_error("hipMemset bitset: %s", hipGetErrorString(e));
             (void)hipFree(s->d_bits);
@@ -697,6 +697,8 @@ int brx_set_count_begin(uint8_t k, int device, int strategy, brx_counter_t **out
     c->stream = nullptr;
     c->count_bytes = set_nbits(k) < 32 ? 32 : set_nbits(k); // one u8 per canonical k-mer, >= one output word
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    if (e == hipSuccess)
+        e = hipEventCreateWithFlags(&c->ev, hipEventDisableTiming);
     if (e != hipSuccess) {
         set_error("stream create: %s", hipGetErrorString(e));
         brx_counter_free(c);
@@ -739,15 +741,19 @@ int brx_set_count_add_batch_device(brx_counter_t *c, const uint8_t *d_bases, con
         return BRX_OK;
     hipStream_t s = (hipStream_t)stream;
     if (c->strategy == BRX_COUNT_SORTED)
-        return part_add_batch(c, d_bases, d_offsets, n_reads, total_bases, s);
-    if (c->strategy == BRX_COUNT_TABLE)
-        return tab_add_batch(c, d_bases, d_offsets, n_reads, total_bases, s);
+        return part_add_batch(c, d_bases, d_offsets, n_reads, total_bases, s); // (returns with `s` synchronised)
+    if (c->strategy == BRX_COUNT_TABLE) {
+        BRX_TRY(tab_add_batch(c, d_bases, d_offsets, n_reads, total_bases, s));
+        BRX_HIP(counter_mark(c, s));
+        return BRX_OK;
+    }
     {
         KernelTimer t("count_dense", s);
         kmer_scatter_kernel<0><<<grid_for(n_reads, 1, 1 << 20), 256, 0, s>>>(d_bases, d_offsets, n_reads, c->k,
                                                                           c->d_counts);
     }
     BRX_HIP(hipGetLastError());
+    BRX_HIP(counter_mark(c, s));
     return BRX_OK;
 }
 
@@ -759,6 +765,7 @@ int brx_set_count_add_batch(brx_counter_t *c, const uint8_t *bases, const uint64
     if (!n_reads)
         return BRX_OK;
     std::lock_guard<std::mutex> g(c->mu);
+    BRX_HIP(counter_join(c, c->stream)); // a reset or a batch still queued on the caller's stream comes first
     uint8_t *d_b = nullptr;
     uint64_t *d_o = nullptr;
     uint64_t bc = 0, oc = 0, tot = 0;
@@ -786,14 +793,18 @@ int brx_counter_reset(brx_counter_t *c, void *stream)
     BRX_TRY(use_device(c->device));
     hipStream_t s = (hipStream_t)stream;
     if (c->strategy == BRX_COUNT_SORTED)
-        return part_reset(c);
-    if (c->strategy == BRX_COUNT_TABLE)
-        return tab_reset(c, s);
+        return part_reset(c); // (host state only: nothing is enqueued, and a finish still queued on `s` has left its mark)
+    if (c->strategy == BRX_COUNT_TABLE) {
+        BRX_TRY(tab_reset(c, s));
+        BRX_HIP(counter_mark(c, s));
+        return BRX_OK;
+    }
     if (c->d_counts) {
         KernelTimer t("count_zero", s);
         BRX_HIP(hipMemsetAsync(c->d_counts, 0, c->count_bytes, s));
     }
     c->n_keys = 0;
+    BRX_HIP(counter_mark(c, s));
     return BRX_OK;
 }
 
@@ -809,10 +820,16 @@ int brx_set_count_finish_into(brx_counter_t *c, uint8_t abundance, void *stream,
     BRX_TRY(use_device(c->device));
     index_invalidate(dst);
     hipStream_t s = (hipStream_t)stream; // nullptr = the legacy default stream, like any HIP API
-    if (c->strategy == BRX_COUNT_SORTED)
-        return part_finish_into(c, abundance, s, dst);
-    if (c->strategy == BRX_COUNT_TABLE)
-        return tab_finish_into(c, abundance, s, dst);
+    if (c->strategy == BRX_COUNT_SORTED) {
+        BRX_TRY(part_finish_into(c, abundance, s, dst));
+        BRX_HIP(counter_mark(c, s)); // (the partition passes are still queued on `s`: they read the batches and the workspace)
+        return BRX_OK;
+    }
+    if (c->strategy == BRX_COUNT_TABLE) {
+        BRX_TRY(tab_finish_into(c, abundance, s, dst));
+        BRX_HIP(counter_mark(c, s)); // (the table is still being read on `s`)
+        return BRX_OK;
+    }
     if (dst->sparse) {
         set_error("the dense count strategy needs a bit vector; a sparse set (k=%d) has none", dst->k);
         return BRX_ERR_UNSUPPORTED;
@@ -824,6 +841,7 @@ int brx_set_count_finish_into(brx_counter_t *c, uint8_t abundance, void *stream,
                                                                              abundance, dst->d_bits);
     }
     BRX_HIP(hipGetLastError());
+    BRX_HIP(counter_mark(c, s)); // (the counts are still being read on `s`)
     return BRX_OK;
 }
 
@@ -936,6 +954,7 @@ int brx_counter_load_counts(brx_counter_t *c, uint64_t first, const uint8_t *cou
         return BRX_ERR_ARG;
     }
     BRX_TRY(use_device(c->device));
+    BRX_HIP(counter_join(c, nullptr)); // a reset still queued on the caller's stream comes first
     if (n)
         BRX_HIP(hipMemcpy((uint8_t *)c->d_counts + first, counts, n, hipMemcpyHostToDevice));
     return BRX_OK;
@@ -1090,6 +1109,8 @@ void brx_counter_free(brx_counter_t *c)
             (void)hipFree(c->d_keys);
         if (c->stream)
             (void)hipStreamDestroy(c->stream);
+        if (c->ev)
+            (void)hipEventDestroy(c->ev);
     }
     delete c;
 }

@@ -241,6 +241,11 @@ class Pcon(KmerSet):
         bases, offs = pack_reads(reads)
         _lib.check(_lib.lib().brx_set_insert_batch(self._h, bases.ctypes.data, offs.ctypes.data, len(reads)))
 
+    def insert_batch_device(self, d_bases: int, d_offsets: int, n_reads: int, total_bases: int,
+                            stream: Optional[int] = None) -> None:
+        """insert_reads on device buffers, enqueued on `stream` (brx_set_insert_batch_device)"""
+        _lib.check(_lib.lib().brx_set_insert_batch_device(self._h, d_bases, d_offsets, n_reads, total_bases, stream))
+
     def to_solid_bytes(self) -> bytes:
         n = C.c_size_t(0)
         L = _lib.lib()

@@ -88,6 +88,33 @@ int brx_set_new_from_solid_bytes(const uint8_t *buf, size_t len, int device, brx
 /* Pcon::from_fasta (presence only): OR in every canonical k-mer of every read of length >= k
  *                                                                  src/set/pcon.rs:47-112  */
 int brx_set_insert_batch(brx_set_t *set, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads);
+/* ---- streams: what every entry with a `void *stream` argument promises (tests/test_gpu_streams.py holds it to this) ----
+ * `stream` is a hipStream_t of the handle's device; NULL is the legacy null stream, like any HIP API.  The caller's streams
+ * may be non-blocking (hipStreamNonBlocking: no implicit ordering with the null stream), as the library's own are.
+ *   - INPUTS need only be ready in the order of `stream`: device buffers may still be being written by work queued on
+ *     `stream` before the call.  The library reads them, and everything it derives from them, on `stream`.
+ *   - RESULTS are ready in the order of `stream` -- work queued on `stream` after the call sees them; the host sees them
+ *     after it has synchronised `stream` -- or on return, where the entry says that it returns after its kernels have
+ *     completed or after `stream` has been synchronised.  Values handed back through host pointers are valid on return.
+ *   - a FRESHLY CREATED object (brx_set_new, brx_set_count_begin, brx_set_count_finish, brx_set_load_fd, brx_chain_new) may
+ *     be used on any stream at once: whatever its constructor zeroes or writes is complete when the constructor returns.
+ *   - an entry WITHOUT a stream argument that changes an object (brx_set_count_add_batch, brx_counter_load_counts,
+ *     brx_counter_load_fd, brx_count_fasta_fd) sees everything that earlier calls on the same object enqueued, whichever stream they named:
+ *     brx_counter_reset(c, s) followed by brx_set_count_add_batch(c, ..) counts into the emptied counter although the batch
+ *     runs on the counter's own stream, and brx_set_count_finish_into(c, a, s, dst); brx_counter_reset(c, s) followed by it
+ *     leaves the finish queued on `s` its batches and workspace, for every count strategy.  The same holds for the counter's
+ *     host-path lookups (brx_counter_abundance_batch, brx_counter_get_counts, brx_counter_save_fd).
+ *   - the host-path READERS of a set -- brx_set_get, get_batch, get_batch_indexed, popcount, export_solid_bytes, set,
+ *     brx_set_save_fd -- work on the null stream and do NOT wait for a non-blocking stream: after an asynchronous device
+ *     entry that wrote the set (insert_batch_device, or_keys_device, count_finish_into) the ordering is the CALLER's:
+ *     synchronise that stream first.  Pointers handed out (brx_set_device_bits, brx_set_keylist_device,
+ *     brx_counter_device_counts, brx_counter_l1_view) are the caller's to order likewise.
+ *   - state that is built on first use (a lazy bit vector, the probe index, the successor table, a partitioned counter's
+ *     count view) is complete before it is published: a later call sees it whole, whichever stream it names.
+ *   - one MUTABLE object (a counter; a set while it is being built; a chain) is driven from one stream at a time, unless
+ *     an entry says otherwise: a caller that moves it to another stream orders the two streams itself (an event, or a
+ *     synchronise).  The partition workspace of a BRX_COUNT_SORTED counter and a chain's workspace have no ordering of
+ *     their own beyond this rule.  A closed set is immutable and may be read on any number of streams at once.         */
 /* same on device buffers, asynchronous on `stream` for bit-vector sets                          */
 int brx_set_insert_batch_device(brx_set_t *set, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads,
                                 uint64_t total_bases, void *stream);
