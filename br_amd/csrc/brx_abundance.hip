@@ -260,7 +260,7 @@ int abund_view(const brx_counter *c, const char *what, AbundArgs &a, int &src)
 {
     a.k = c->k;
     if (c->strategy == BRX_COUNT_DENSE) {
-        a.dense = reinterpret_cast<const uint8_t *>(c->d_counts);
+        a.dense = reinterpret_cast<const uint8_t *>(c->d_counts.get());
         src = SRC_DENSE;
         return BRX_OK;
     }

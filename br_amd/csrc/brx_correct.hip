@@ -38,8 +38,8 @@ namespace brx {
 uint64_t scan_tmp_bytes(uint32_t n);
 int exclusive_scan_lens(const uint32_t *d_lens, uint32_t n, uint64_t *d_tmp, uint64_t *d_out_offsets,
                         unsigned long long *d_total, hipStream_t s);
-int upload_batch(const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, uint8_t **d_bases, uint64_t *bases_cap,
-                 uint64_t **d_off, uint64_t *off_cap, uint64_t *total, hipStream_t stream);
+int upload_batch(const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, DevBuf<uint8_t> &d_bases, DevBuf<uint64_t> &d_off,
+                 uint64_t *total, hipStream_t stream);
 }
 
 namespace {
@@ -2371,23 +2371,8 @@ __global__ __launch_bounds__(256) void compact_kernel(const uint8_t *__restrict_
     }
 }
 
-int ensure(void **p, uint64_t *cap, uint64_t need)
-{
-    if (need <= *cap && *p)
-        return BRX_OK;
-    if (*p)
-        (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    uint64_t want = need + need / 8 + 256;
-    hipError_t e = hipMalloc(p, want);
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%llu B workspace): %s", (unsigned long long)want, hipGetErrorString(e));
-        return BRX_ERR_NOMEM;
-    }
-    *cap = want;
-    return BRX_OK;
-}
+// headroom of the chain's byte-sized workspaces
+inline uint64_t ws_headroom(uint64_t need) { return need / 8 + 256; }
 
 constexpr uint64_t RESIDENT_LANES = 256ull * 4ull * 6ull * 64ull; // CUs x SIMDs x waves x lanes at occupancy 6
 
@@ -2668,13 +2653,14 @@ int launch_rev_lean(brx_chain *ch, PassParams p, const brx_method_t &md, hipStre
     // room for four open triggers per read on average (the bench's data: 1.2); a scan that finds no room hands its read back
     const uint64_t trig_cap64 = 4ull * p.n_reads + 4096ull;
     const uint32_t trig_cap = trig_cap64 > 0x7fffffffull ? 0x7fffffffu : (uint32_t)trig_cap64;
-    BRX_TRY(ensure((void **)&ch->d_rev_list, &ch->rev_list_bytes, (uint64_t)p.n_reads * 4ull));
-    BRX_TRY(ensure((void **)&ch->d_rev_flag, &ch->rev_flag_bytes, (uint64_t)p.n_reads * 4ull));
-    BRX_TRY(ensure(&ch->d_rev_trig, &ch->rev_trig_bytes, (uint64_t)trig_cap * sizeof(TrigRec)));
+    const uint64_t list_bytes = (uint64_t)p.n_reads * 4ull, trig_bytes = (uint64_t)trig_cap * sizeof(TrigRec);
+    BRX_TRY(ch->d_rev_list.reserve_bytes(list_bytes, ws_headroom(list_bytes), "workspace"));
+    BRX_TRY(ch->d_rev_flag.reserve_bytes(list_bytes, ws_headroom(list_bytes), "workspace"));
+    BRX_TRY(ch->d_rev_trig.reserve_bytes(trig_bytes, ws_headroom(trig_bytes), "workspace"));
     BRX_HIP(hipMemsetAsync(p.ctrl + CTL_REV_HANDBACK, 0, 8, s));
     BRX_HIP(hipMemsetAsync(p.ctrl + CTL_REV_TRIGS, 0, 8, s));
     BRX_HIP(hipMemsetAsync(ch->d_rev_flag, 0, (uint64_t)p.n_reads * 4ull, s));
-    TrigRec *trig = (TrigRec *)ch->d_rev_trig;
+    TrigRec *trig = (TrigRec *)ch->d_rev_trig.get();
     {
         const uint32_t blocks = pass_blocks(p.n_reads, 64);
         KernelTimer t(names[md.method], s);
@@ -2744,26 +2730,6 @@ int brx_chain_new_pass(const brx_set_t *set, const brx_method_t *methods, uint32
     ch->methods.assign(methods, methods + n_methods);
     ch->two_side = second_pass == BRX_PASS_NONE;
     ch->second_pass = second_pass;
-    ch->stream = nullptr;
-    ch->d_stage[0] = ch->d_stage[1] = nullptr;
-    ch->stage_bytes = 0;
-    ch->d_lens[0] = ch->d_lens[1] = nullptr;
-    ch->lens_cap = 0;
-    ch->d_scan_tmp = nullptr;
-    ch->scan_tmp_cap = 0;
-    ch->d_ctrl = nullptr;
-    ch->h_ctrl = nullptr;
-    ch->d_path = nullptr;
-    ch->path_bytes = 0;
-    ch->d_in = nullptr;
-    ch->d_in_cap = 0;
-    ch->d_off = nullptr;
-    ch->d_off_cap = 0;
-    ch->d_out = nullptr;
-    ch->d_out_cap = 0;
-    ch->d_out_off = nullptr;
-    ch->d_out_off_cap = 0;
-    memset(ch->last_stats, 0, sizeof(ch->last_stats));
     if (const char *e = getenv("BRX_MAXPATH")) { // tests: a short visited list, so that walks outgrow it
         const int v = atoi(e);
         if (v >= 1 && v <= (1 << 20))
@@ -2771,7 +2737,7 @@ int brx_chain_new_pass(const brx_set_t *set, const brx_method_t *methods, uint32
     }
     hipError_t e = hipStreamCreateWithFlags(&ch->stream, hipStreamNonBlocking);
     if (e == hipSuccess)
-        e = hipMalloc((void **)&ch->d_ctrl, CTL_N * 8);
+        e = ch->d_ctrl.reserve(CTL_N, 0, "chain control block") == BRX_OK ? hipSuccess : hipErrorOutOfMemory;
     if (e == hipSuccess)
         e = hipHostMalloc((void **)&ch->h_ctrl, CTL_N * 8, hipHostMallocDefault);
     if (e != hipSuccess) {
@@ -2907,22 +2873,10 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
 
     // (lens, scan scratch) do not depend on slack
     {
-        uint64_t cap_b = ch->lens_cap * 4;
-        const uint64_t need = (uint64_t)n_reads * 4;
-        if (need > cap_b || !ch->d_lens[0]) {
-            for (int q = 0; q < 2; q++) {
-                if (ch->d_lens[q])
-                    (void)hipFree(ch->d_lens[q]);
-                ch->d_lens[q] = nullptr;
-            }
-            const uint64_t want = (uint64_t)n_reads + n_reads / 8 + 64;
-            BRX_HIP(hipMalloc((void **)&ch->d_lens[0], want * 4));
-            BRX_HIP(hipMalloc((void **)&ch->d_lens[1], want * 4));
-            ch->lens_cap = want;
-        }
-        uint64_t tmp_bytes = ch->scan_tmp_cap;
-        BRX_TRY(ensure((void **)&ch->d_scan_tmp, &tmp_bytes, scan_tmp_bytes(n_reads)));
-        ch->scan_tmp_cap = tmp_bytes;
+        for (int q = 0; q < 2; q++)
+            BRX_TRY(ch->d_lens[q].reserve(n_reads, n_reads / 8 + 64, "read lengths"));
+        const uint64_t tmp_bytes = scan_tmp_bytes(n_reads);
+        BRX_TRY(ch->d_scan_tmp.reserve_bytes(tmp_bytes, ws_headroom(tmp_bytes), "workspace"));
     }
 
     // walks (Two/Graph/Greedy/GapSize forward passes) are faster on the bit vector: materialise a lazy one now
@@ -2967,20 +2921,12 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
             // pass_blocks(n_reads, 16) blocks of 16 groups bounds every width (a handful of redone reads needs a
             // handful of lists, not 32768 of them)
             const uint64_t n_groups = sized_path_lists(n_reads); // (at least one block of the narrowest list / verify kernel)
-            BRX_TRY(ensure((void **)&ch->d_path, &ch->path_bytes, n_groups * maxpath * 8ull));
+            const uint64_t path_bytes = n_groups * maxpath * 8ull;
+            BRX_TRY(ch->d_path.reserve_bytes(path_bytes, ws_headroom(path_bytes), "workspace"));
         }
         const uint64_t stage_need = total_bases + (total_bases >> 2) * slack + 64ull * ((uint64_t)n_reads + 1) + 64;
-        if (stage_need > ch->stage_bytes || !ch->d_stage[0]) {
-            for (int q = 0; q < 2; q++) {
-                if (ch->d_stage[q])
-                    (void)hipFree(ch->d_stage[q]);
-                ch->d_stage[q] = nullptr;
-            }
-            ch->stage_bytes = 0;
-            BRX_HIP(hipMalloc((void **)&ch->d_stage[0], stage_need));
-            BRX_HIP(hipMalloc((void **)&ch->d_stage[1], stage_need));
-            ch->stage_bytes = stage_need;
-        }
+        for (int q = 0; q < 2; q++)
+            BRX_TRY(ch->d_stage[q].reserve(stage_need, 0, "staging"));
 
         // the chain: src/lib.rs:44-55.  buffer "rev" = stored back to front w.r.t. the original read
         const uint8_t *cur = d_bases;
@@ -3021,7 +2967,7 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
                 p.out = ch->d_stage[pp];
                 p.out_lens = ch->d_lens[pp];
                 p.slack = slack;
-                p.ctrl = (unsigned long long *)ch->d_ctrl;
+                p.ctrl = (unsigned long long *)ch->d_ctrl.get();
                 p.path_k = ch->d_path;
                 p.maxpath = maxpath;
                 BRX_HIP(hipMemsetAsync(ch->d_ctrl + CTL_WORK, 0, 8, s));
@@ -3053,7 +2999,7 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
                 if ((mth == BRX_ONE || mth == BRX_GRAPH || mth == BRX_GAP_SIZE) && lane_dir) {
                     // forward passes of One, Graph and GapSize (and the reverse ones of the latter two): one lane per chunk
                     // of a read (brx_onelane.hip) where that form applies
-                    const LanePassInfo info{cur_staged ? ch->stage_bytes : total_bases, mth};
+                    const LanePassInfo info{cur_staged ? ch->d_stage[0].bytes() : total_bases, mth};
                     const int lst = lane_pass(ch, p, info, s);
                     if (lst != BRX_OK && lst != BRX_ERR_UNSUPPORTED)
                         return lst;
@@ -3250,21 +3196,18 @@ int brx_chain_correct_batch(brx_chain_t *ch, const uint8_t *bases, const uint64_
             }
         }
         // (upload_batch takes `bases` as the start of the stream offsets[] index into)
-        BRX_TRY(upload_batch(src - base0, offsets, n_reads, &ch->d_in, &ch->d_in_cap, &ch->d_off, &ch->d_off_cap, &total, ch->stream));
+        BRX_TRY(upload_batch(src - base0, offsets, n_reads, ch->d_in, ch->d_off, &total, ch->stream));
     }
-    {
-        uint64_t cap_b = ch->d_out_off_cap * 8;
-        BRX_TRY(ensure((void **)&ch->d_out_off, &cap_b, ((uint64_t)n_reads + 1) * 8));
-        ch->d_out_off_cap = cap_b / 8;
-    }
+    const uint64_t off_bytes = ((uint64_t)n_reads + 1) * 8;
+    BRX_TRY(ch->d_out_off.reserve_bytes(off_bytes, ws_headroom(off_bytes), "workspace"));
     const double t_up = ms_since(t_in);
     uint64_t out_total = 0;
     uint64_t want = total + total / 16 + 4096;
     for (int attempt = 0; attempt < 3; attempt++) {
-        BRX_TRY(ensure((void **)&ch->d_out, &ch->d_out_cap, want));
-        int st = correct_batch_device_locked(ch, ch->d_in, ch->d_off, n_reads, total, ch->d_out, ch->d_out_cap, ch->d_out_off,
+        BRX_TRY(ch->d_out.reserve(want, ws_headroom(want), "workspace"));
+        int st = correct_batch_device_locked(ch, ch->d_in, ch->d_off, n_reads, total, ch->d_out, ch->d_out.cap(), ch->d_out_off,
                                              &out_total, ch->stream);
-        if (st == BRX_ERR_OVERFLOW && out_total > ch->d_out_cap) {
+        if (st == BRX_ERR_OVERFLOW && out_total > ch->d_out.cap()) {
             want = out_total + 64;
             continue;
         }
@@ -3389,43 +3332,16 @@ void brx_chain_free(brx_chain_t *ch)
     if (ch->sub)
         brx_chain_free(ch->sub);
     ch->sub = nullptr;
-    if (use_device(ch->device) == BRX_OK)
-        lane_ws_free(ch);
     host_buf_release(ch->h_in);
     ch->h_in = nullptr;
     if (use_device(ch->device) == BRX_OK) {
-        for (int q = 0; q < 2; q++) {
-            if (ch->d_stage[q])
-                (void)hipFree(ch->d_stage[q]);
-            if (ch->d_lens[q])
-                (void)hipFree(ch->d_lens[q]);
-        }
-        if (ch->d_scan_tmp)
-            (void)hipFree(ch->d_scan_tmp);
-        if (ch->d_ctrl)
-            (void)hipFree(ch->d_ctrl);
-        if (ch->d_path)
-            (void)hipFree(ch->d_path);
-        if (ch->d_rev_list)
-            (void)hipFree(ch->d_rev_list);
-        if (ch->d_rev_flag)
-            (void)hipFree(ch->d_rev_flag);
-        if (ch->d_rev_trig)
-            (void)hipFree(ch->d_rev_trig);
         if (ch->h_ctrl)
             (void)hipHostFree(ch->h_ctrl);
-        if (ch->d_in)
-            (void)hipFree(ch->d_in);
-        if (ch->d_off)
-            (void)hipFree(ch->d_off);
-        if (ch->d_out)
-            (void)hipFree(ch->d_out);
-        if (ch->d_out_off)
-            (void)hipFree(ch->d_out_off);
         if (ch->stream)
             (void)hipStreamDestroy(ch->stream);
     }
-    delete ch;
+    lane_ws_free(ch);
+    delete ch; // its device buffers go back to the pool here, with the chain's device current
 }
 
 } // extern "C"

@@ -26,10 +26,10 @@ using namespace brx;
 namespace brx {
 
 struct TabState {
-    uint64_t *d_lines = nullptr;   // 8 u64 per line
-    uint32_t *d_counts = nullptr;  // 8 u32 per line (entry 7 unused)
+    DevBuf<uint64_t> d_lines;      // 8 u64 per line
+    DevBuf<uint32_t> d_counts;     // 8 u32 per line (entry 7 unused)
     uint32_t log_lines = 0, m = 0;
-    unsigned long long *d_nkeys = nullptr; // distinct keys in the table
+    DevBuf<unsigned long long> d_nkeys; // distinct keys in the table
     uint64_t keys_known = 0;       // d_nkeys when it was last read back
     uint64_t pending = 0;          // bases counted since: at most that many more keys
     uint64_t bases_total = 0;      // bases counted in all: at most that many occurrences
@@ -204,12 +204,8 @@ uint32_t slot_grid(uint64_t n_slots) { return read_grid((n_slots + 255ull) / 256
 
 void free_table(TabState *t)
 {
-    if (t->d_lines)
-        (void)hipFree(t->d_lines);
-    if (t->d_counts)
-        (void)hipFree(t->d_counts);
-    t->d_lines = nullptr;
-    t->d_counts = nullptr;
+    t->d_lines.reset();
+    t->d_counts.reset();
     t->log_lines = 0;
 }
 
@@ -250,45 +246,28 @@ int regrow(brx_counter *c, uint64_t need, hipStream_t s)
         return BRX_ERR_ARG;
     }
     const uint64_t line_bytes = 64ull << log_lines, count_bytes = 32ull << log_lines;
-    uint64_t *nl = nullptr;
-    uint32_t *nc = nullptr;
-    hipError_t e = hipMalloc((void **)&nl, line_bytes);
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&nc, count_bytes);
-    if (e != hipSuccess) {
-        if (nl)
-            (void)hipFree(nl);
-        set_error("hipMalloc(%llu B counting table of 2^%d lines for up to %llu k-mers): %s", (unsigned long long)(line_bytes + count_bytes),
-                  log_lines, (unsigned long long)need, hipGetErrorString(e));
-        return BRX_ERR_NOMEM;
-    }
+    DevBuf<uint64_t> nl;
+    DevBuf<uint32_t> nc;
+    BRX_TRY(nl.reserve_bytes(line_bytes, 0, "counting table lines"));
+    BRX_TRY(nc.reserve_bytes(count_bytes, 0, "counting table counters"));
     const uint64_t held = t->d_lines ? (96ull << t->log_lines) : 0ull;
     if (held + line_bytes + count_bytes > t->peak_bytes)
         t->peak_bytes = held + line_bytes + count_bytes;
     {
         KernelTimer z("tab_zero", s);
-        e = hipMemsetAsync(nl, 0, line_bytes, s);
-        if (e == hipSuccess)
-            e = hipMemsetAsync(nc, 0, count_bytes, s);
+        BRX_HIP(hipMemsetAsync(nl, 0, line_bytes, s));
+        BRX_HIP(hipMemsetAsync(nc, 0, count_bytes, s));
     }
-    if (e == hipSuccess && t->d_lines && t->keys_known) {
+    if (t->d_lines && t->keys_known) {
         KernelTimer r("tab_rehash", s);
         const uint64_t n_old = 8ull << t->log_lines;
         table_rehash_counts_kernel<<<slot_grid(n_old), 256, 0, s>>>(t->d_lines, t->d_counts, n_old, k, nl, nc, 32u - (uint32_t)log_lines,
                                                                     (uint32_t)m, (uint32_t)(k - m + 1));
-        e = hipGetLastError();
+        BRX_HIP(hipGetLastError());
     }
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(s); // the old table is freed below
-    if (e != hipSuccess) {
-        (void)hipFree(nl);
-        (void)hipFree(nc);
-        set_error("counting table regrow: %s", hipGetErrorString(e));
-        return BRX_ERR_HIP;
-    }
-    free_table(t);
-    t->d_lines = nl;
-    t->d_counts = nc;
+    BRX_HIP(hipStreamSynchronize(s)); // the old table is freed below
+    t->d_lines = std::move(nl);
+    t->d_counts = std::move(nc);
     t->log_lines = (uint32_t)log_lines;
     t->m = (uint32_t)m;
     return BRX_OK;
@@ -306,20 +285,14 @@ int tab_begin(brx_counter *c)
     }
     TabState *t = new TabState();
     c->tab = t;
-    BRX_HIP(hipMalloc((void **)&t->d_nkeys, 8));
+    BRX_TRY(t->d_nkeys.reserve(1, 0, "counting table key counter"));
     BRX_HIP(zero_now(t->d_nkeys, 8)); // (done on return: the first batch may come on any stream)
     return BRX_OK;
 }
 
 void tab_free(brx_counter *c)
 {
-    TabState *t = c->tab;
-    if (!t)
-        return;
-    free_table(t);
-    if (t->d_nkeys)
-        (void)hipFree(t->d_nkeys);
-    delete t;
+    delete c->tab;
     c->tab = nullptr;
 }
 
@@ -380,8 +353,7 @@ int tab_finish_into(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set *
     }
     if (t->pending)
         BRX_TRY(read_keys(t, s));
-    if (!dst->d_keylist_n)
-        BRX_HIP(hipMalloc((void **)&dst->d_keylist_n, 8));
+    BRX_TRY(dst->d_keylist_n.reserve(1, 0, "key list counter"));
     BRX_HIP(hipMemsetAsync(dst->d_keylist_n, 0, 8, s));
     if (!dst->sparse) { // the bits are written here, in the same pass (nothing left lazy)
         BRX_HIP(hipMemsetAsync(dst->d_bits, 0, dst->nwords * 4, s));
@@ -395,20 +367,13 @@ int tab_finish_into(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set *
             if (want > t->keys_known)
                 want = t->keys_known;
             want += 64;
-            if (dst->keylist_cap < want || !dst->d_keylist) {
-                if (dst->d_keylist)
-                    (void)hipFree(dst->d_keylist);
-                dst->d_keylist = nullptr;
-                dst->keylist_cap = 0;
-                BRX_HIP(hipMalloc((void **)&dst->d_keylist, want * 8));
-                dst->keylist_cap = want;
-            }
+            BRX_TRY(dst->d_keylist.reserve(want, 0, "solid key list"));
         }
         KernelTimer kt("tab_select", s);
         const uint64_t n_slots = 8ull << t->log_lines;
         if (list)
             table_select_kernel<true><<<slot_grid(n_slots), 256, 0, s>>>(t->d_lines, t->d_counts, n_slots, abundance, dst->d_keylist,
-                                                                        dst->keylist_cap, dst->d_keylist_n, dst->sparse ? nullptr : dst->d_bits,
+                                                                        dst->d_keylist.cap(), dst->d_keylist_n, dst->sparse ? nullptr : dst->d_bits.get(),
                                                                         dst->nwords * 32);
         else
             table_select_kernel<false><<<slot_grid(n_slots), 256, 0, s>>>(t->d_lines, t->d_counts, n_slots, abundance, nullptr, 0, nullptr,
@@ -430,6 +395,8 @@ int tab_split_by_owner(brx_counter *c, int world, hipStream_t s, uint64_t **d_ke
     if (t->pending)
         BRX_TRY(read_keys(t, s));
     const uint64_t n = t->d_lines ? t->keys_known : 0ull;
+    DevBuf<uint64_t> keys; // handed to the caller at the end
+    DevBuf<uint8_t> cnts;
     if (n) {
         const uint64_t n_slots = 8ull << t->log_lines;
         DevScratch ws;
@@ -453,14 +420,8 @@ int tab_split_by_owner(brx_counter *c, int world, hipStream_t s, uint64_t **d_ke
             set_error("counting table split: %llu entries found, %llu k-mers counted", (unsigned long long)off[world], (unsigned long long)n);
             return BRX_ERR_HIP;
         }
-        hipError_t e = hipMalloc((void **)d_keys, n * 8);
-        if (e == hipSuccess)
-            e = hipMalloc((void **)d_cnts, n);
-        if (e != hipSuccess) {
-            set_error("hipMalloc(%llu B, the table's %llu entries grouped by owner): %s", (unsigned long long)(n * 9), (unsigned long long)n,
-                      hipGetErrorString(e));
-            return BRX_ERR_NOMEM;
-        }
+        BRX_TRY(keys.reserve(n, 0, "the table's keys grouped by owner"));
+        BRX_TRY(cnts.reserve(n, 0, "the table's counts grouped by owner"));
         if ((96ull << t->log_lines) + n * 9 > t->peak_bytes)
             t->peak_bytes = (96ull << t->log_lines) + n * 9;
         BRX_HIP(hipMemcpyAsync(d_off, off.data(), ((size_t)world + 1) * 8, hipMemcpyHostToDevice, s));
@@ -468,7 +429,7 @@ int tab_split_by_owner(brx_counter *c, int world, hipStream_t s, uint64_t **d_ke
         {
             KernelTimer kt("tab_split", s);
             table_owner_split_kernel<<<slot_grid(n_slots), 256, 0, s>>>(t->d_lines, t->d_counts, n_slots, (uint32_t)world, d_off, d_cursor,
-                                                                       *d_keys, *d_cnts);
+                                                                       keys, cnts);
         }
         BRX_HIP(hipGetLastError());
         BRX_HIP(hipStreamSynchronize(s)); // (`off` is a local; the table is freed below)
@@ -476,6 +437,8 @@ int tab_split_by_owner(brx_counter *c, int world, hipStream_t s, uint64_t **d_ke
     free_table(t); // every entry is in the arrays now: never two tables at once
     BRX_HIP(hipMemsetAsync(t->d_nkeys, 0, 8, s));
     t->keys_known = t->pending = t->bases_total = 0;
+    *d_keys = keys.release(); // the caller's from here (it adopts them)
+    *d_cnts = cnts.release();
     return BRX_OK;
 }
 

@@ -301,25 +301,6 @@ __global__ __launch_bounds__(256) void cover_copy_kernel(CoverArgs a)
     }
 }
 
-// device scratch of one call, from the block pool; released when the call returns
-struct Scratch {
-    std::vector<void *> blocks;
-    ~Scratch()
-    {
-        for (void *p : blocks)
-            (void)hipFree(p);
-    }
-    template <typename T>
-    int get(T **out, uint64_t n)
-    {
-        void *p = nullptr;
-        BRX_HIP(hipMalloc(&p, (n ? n : 1) * sizeof(T)));
-        blocks.push_back(p);
-        *out = (T *)p;
-        return BRX_OK;
-    }
-};
-
 // how the kernels reach the set.  Never writes the bit vector: a lazy one stays lazy, the index answers for it
 int cover_view(const brx_set *set, hipStream_t s, CoverArgs &a)
 {
@@ -362,7 +343,7 @@ int check_batch(const char *what, const brx_set_t *set, const void *d_bases, con
 }
 
 // work list + cover kernel.  `tile_bound` tiles at most (known without asking the device)
-int cover_launch(const brx_set *set, CoverArgs &a, uint64_t total_bases, Scratch &sc, uint64_t &tile_bound, hipStream_t s)
+int cover_launch(const brx_set *set, CoverArgs &a, uint64_t total_bases, DevScratch &sc, uint64_t &tile_bound, hipStream_t s)
 {
     BRX_TRY(cover_view(set, s, a));
     const uint32_t n_reads = a.n_reads;
@@ -411,7 +392,7 @@ int brx_set_cover_batch_device(const brx_set_t *set, const uint8_t *d_bases, con
     if (!n_reads || (!d_flags && !d_masked && !d_stats))
         return BRX_OK;
     hipStream_t s = (hipStream_t)stream;
-    Scratch sc;
+    DevScratch sc;
     CoverArgs a{};
     a.n_reads = n_reads;
     a.bases = d_bases;
@@ -447,7 +428,7 @@ int brx_set_cover_batch(const brx_set_t *set, const uint8_t *bases, const uint64
     BRX_TRY(use_device(set->device));
     if (!n_reads || (!flags && !masked && !stats))
         return BRX_OK;
-    Scratch sc;
+    DevScratch sc;
     uint8_t *d_bases = nullptr, *d_flags = nullptr, *d_masked = nullptr;
     uint64_t *d_off = nullptr;
     brx_cover_stats_t *d_stats = nullptr;
@@ -495,7 +476,7 @@ int brx_set_cover_split_batch_device(const brx_set_t *set, const uint8_t *d_base
         BRX_HIP(hipStreamSynchronize(s));
         return BRX_OK;
     }
-    Scratch sc;
+    DevScratch sc;
     CoverArgs a{};
     a.n_reads = n_reads;
     a.bases = d_bases;
@@ -624,7 +605,7 @@ int brx_set_cover_split_batch(const brx_set_t *set, const uint8_t *bases, const 
         set_error("%s: batch too large for one call", me);
         return BRX_ERR_ARG;
     }
-    Scratch sc;
+    DevScratch sc;
     uint8_t *d_bases = nullptr, *d_out = nullptr;
     uint64_t *d_off = nullptr, *d_oo = nullptr, *d_ps = nullptr;
     uint32_t *d_pr = nullptr;

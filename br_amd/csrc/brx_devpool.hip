@@ -3,8 +3,8 @@
 // A job file -> file creates a counter, a set and a chain, and drops them again: 4 GB of keys, the 2 GiB probe index, the
 // staging buffers.  hipFree of such a block usually takes microseconds and now and then a third of a second (the driver
 // unmaps it), hipMalloc pays for the page tables again -- measured with tools/e2e_repeat.py: one repetition in eight lost
-// 0.7 s to two frees, and bench.py's `e2e` block showed build legs of 1.4 s instead of 0.13 s.  Every hipMalloc / hipFree
-// of the library's translation units goes through dev_alloc / dev_free (the macros at the end of brx_internal.hpp);
+// 0.7 s to two frees, and bench.py's `e2e` block showed build legs of 1.4 s instead of 0.13 s.  Every device block of the
+// library's translation units comes from dev_alloc and goes back through dev_free (their owners: brx_devbuf.hpp);
 // blocks of at least POOL_MIN bytes are parked here when freed, up to BRX_DEVPOOL_GB (default 48) GiB per process and only
 // while at least an eighth of the card is free, and a
 // request takes the smallest parked block that is large enough and at most twice its size.

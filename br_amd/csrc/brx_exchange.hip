@@ -133,18 +133,13 @@ struct brx_comm {
     int world = 1, rank = 0, device = 0;
     ncclComm_t comm = nullptr;
     // workspace kept between jobs
-    uint32_t *d_recv = nullptr;    // keys received from every rank for the owned digit range
-    uint64_t recv_cap = 0;         // bytes
-    uint64_t *d_tables = nullptr;  // world x (B1+1) gathered level-1 offset tables, then the owner's segment tables (table merge:
-                                   // world x world send counts; its spectrum: world x 256 bins)
-    uint64_t tables_cap = 0;
-    uint64_t *d_gather = nullptr;  // every rank's solid-hash list, rank after rank
-    uint64_t gather_cap = 0;
-    uint64_t *d_counts = nullptr;  // world u64
-    int *d_wide = nullptr;         // int32 slice of the dense reduction
-    uint64_t wide_cap = 0;
-    uint64_t *d_zero_tab = nullptr; // B1 + 1 zeros: the level-1 offsets of a rank that counted nothing
-    uint64_t zero_tab_cap = 0;
+    brx::DevBuf<uint32_t> d_recv;    // keys received from every rank for the owned digit range
+    brx::DevBuf<uint64_t> d_tables;  // world x (B1+1) gathered level-1 offset tables, then the owner's segment tables (table merge:
+                                     // world x world send counts; its spectrum: world x 256 bins)
+    brx::DevBuf<uint64_t> d_gather;  // every rank's solid-hash list, rank after rank
+    brx::DevBuf<uint64_t> d_counts;  // world u64 pairs
+    brx::DevBuf<int> d_wide;         // int32 slice of the dense reduction
+    brx::DevBuf<uint64_t> d_zero_tab; // B1 + 1 zeros: the level-1 offsets of a rank that counted nothing
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t rounds_a2a = 0, rounds_gather = 0;
     // how the current call failed, if it did: a failure every rank KNOWS about (it went through a status exchange) lets
@@ -157,22 +152,10 @@ struct brx_comm {
 
 namespace {
 
-int grow(void **p, uint64_t *cap, uint64_t need, const char *what)
+// the communicator's workspace is sized in bytes, with a sixteenth and 256 B to spare
+template <typename T> int grow_ws(DevBuf<T> &b, uint64_t need_bytes, const char *what)
 {
-    if (*p && need <= *cap)
-        return BRX_OK;
-    if (*p)
-        (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const uint64_t want = need + need / 16 + 256;
-    hipError_t e = hipMalloc(p, want);
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%llu B, %s): %s", (unsigned long long)want, what, hipGetErrorString(e));
-        return BRX_ERR_NOMEM;
-    }
-    *cap = want;
-    return BRX_OK;
+    return b.reserve_bytes(need_bytes, need_bytes / 16 + 256, what);
 }
 
 // every rank's `send` (send_counts[r] elements of `esize` bytes for rank r, back to back) to its owner; `recv` likewise.
@@ -304,9 +287,7 @@ int brx_comm_init(const uint8_t *id128, int world, int rank, int device, brx_com
         delete cm;
         return BRX_ERR_HIP;
     }
-    hipError_t e = hipMalloc((void **)&cm->d_counts, (size_t)world * 8 * 2);
-    if (e != hipSuccess) {
-        set_error("comm alloc: %s", hipGetErrorString(e));
+    if (cm->d_counts.reserve((uint64_t)world * 2, 0, "communicator") != BRX_OK) {
         brx_comm_free(cm);
         return BRX_ERR_NOMEM;
     }
@@ -371,15 +352,10 @@ void brx_comm_free(brx_comm_t *cm)
 {
     if (!cm)
         return;
-    if (use_device(cm->device) == BRX_OK) {
-        for (void *p : {(void *)cm->d_recv, (void *)cm->d_tables, (void *)cm->d_gather, (void *)cm->d_counts, (void *)cm->d_wide,
-                        (void *)cm->d_zero_tab})
-            if (p)
-                (void)hipFree(p);
-    }
+    (void)use_device(cm->device);
     if (cm->comm && g_rccl.h)
         (void)g_rccl.CommDestroy(cm->comm);
-    delete cm;
+    delete cm; // its device buffers go back to the pool here
 }
 
 // The host-side arithmetic of the key exchange, a pure function of the gathered level-1 offset tables -- exported
@@ -499,7 +475,7 @@ int replicate_solid(brx_comm *cm, brx_set_t *dst, const void *d_list, uint64_t n
         off[r + 1] = off[r] + n_of[r];
     }
     const uint64_t n_all = off[W];
-    local = grow((void **)&cm->d_gather, &cm->gather_cap, (n_all + 1) * 8, "gathered solid k-mers");
+    local = grow_ws(cm->d_gather, (n_all + 1) * 8, "gathered solid k-mers");
     BRX_TRY(agree(cm, local, s));
     if (n_mine)
         BRX_HIP(hipMemcpyAsync(cm->d_gather + off[me], d_list, n_mine * 8, hipMemcpyDeviceToDevice, s));
@@ -531,7 +507,7 @@ void abort_after_local_failure(brx_comm *cm)
 }
 
 struct ExchangeJob {
-    uint64_t *d_extracted = nullptr; // owned: freed by the caller whatever happens
+    DevBuf<uint64_t> d_extracted;    // the owner's solid hashes, when they had to be taken from the bit vector
     bool counter_borrows = false;    // the counter refers to cm->d_recv: reset it before returning
 };
 
@@ -549,9 +525,9 @@ int owned_list(brx_set_t *dst, ExchangeJob &job, void **d_list, uint64_t *n_mine
         BRX_HIP(hipStreamSynchronize(s));
         uint64_t pc = 0;
         BRX_TRY(brx_set_popcount(dst, &pc));
-        BRX_HIP(hipMalloc((void **)&job.d_extracted, (pc + 64) * 8));
+        BRX_TRY(job.d_extracted.reserve(pc + 64, 0, "solid k-mers of the bit vector"));
         BRX_TRY(brx_set_extract_keys_device(dst, 0, dst->nwords * 32, job.d_extracted, pc + 64, n_mine, s));
-        *d_list = job.d_extracted;
+        *d_list = job.d_extracted.get();
     }
     BRX_HIP(hipStreamSynchronize(s));
     return BRX_OK;
@@ -590,14 +566,14 @@ int exchange_body(brx_comm *cm, brx_counter_t *c, uint8_t abundance, brx_set_t *
     int local = brx_counter_l1_view(c, &pk, &po, &B1, &nk);
     const uint32_t T = B1 + 1;
     if (local == BRX_OK && !po) {
-        local = grow((void **)&cm->d_zero_tab, &cm->zero_tab_cap, (uint64_t)T * 8, "empty offset table");
+        local = grow_ws(cm->d_zero_tab, (uint64_t)T * 8, "empty offset table");
         if (local == BRX_OK && hipMemsetAsync(cm->d_zero_tab, 0, (uint64_t)T * 8, s) != hipSuccess)
             local = BRX_ERR_HIP;
         po = cm->d_zero_tab;
         nk = 0;
     }
     if (local == BRX_OK)
-        local = grow((void **)&cm->d_tables, &cm->tables_cap, (uint64_t)W * T * 8 * 2, "offset tables");
+        local = grow_ws(cm->d_tables, (uint64_t)W * T * 8 * 2, "offset tables");
     BRX_TRY(agree(cm, local, s));
 
     // 2. everybody's offset table to everybody (small), then to the host: all message sizes follow from them
@@ -614,7 +590,7 @@ int exchange_body(brx_comm *cm, brx_counter_t *c, uint8_t abundance, brx_set_t *
 
     // 3. keys to their owners
     if (local == BRX_OK)
-        local = grow((void **)&cm->d_recv, &cm->recv_cap, (n_recv + 1) * 4, "received keys");
+        local = grow_ws(cm->d_recv, (n_recv + 1) * 4, "received keys");
     BRX_TRY(agree(cm, local, s));
     const double t_a2a = now_ms();
     BRX_TRY(all_to_all_v(cm, pk, send_counts.data(), cm->d_recv, recv_counts.data(), biggest, 4, ncclUint32, s));
@@ -676,8 +652,6 @@ int brx_exchange_build_partitioned(brx_comm_t *cm, brx_counter_t *c, uint8_t abu
     if (rc != BRX_OK)
         abort_after_local_failure(cm);
     // ONE way out: whatever happened, the counter is empty again and no longer refers to the receive buffer
-    if (job.d_extracted)
-        (void)hipFree(job.d_extracted);
     const std::string msg = rc != BRX_OK ? brx_last_error() : "";
     const int rst = brx_counter_reset(c, s);
     if (rc != BRX_OK) {
@@ -730,7 +704,7 @@ static int reduce_counts_body(brx_comm_t *cm, brx_counter_t *c, uint8_t abundanc
     const uint64_t slice = 1ull << 30;
     uint8_t *p = (uint8_t *)d_counts;
     if (local == BRX_OK && !exact_u8)
-        local = grow((void **)&cm->d_wide, &cm->wide_cap, std::min(slice, nbytes) * 4, "int32 reduction slice");
+        local = grow_ws(cm->d_wide, std::min(slice, nbytes) * 4, "int32 reduction slice");
     BRX_TRY(agree(cm, local, s));
     for (uint64_t lo = 0; lo < nbytes; lo += slice) {
         const uint64_t n = std::min(slice, nbytes - lo);
@@ -755,27 +729,9 @@ static int reduce_counts_body(brx_comm_t *cm, brx_counter_t *c, uint8_t abundanc
 // replication of the solid lists (replicate_solid) gives every rank the job's set.
 namespace {
 
-struct TableJob { // device arrays of one merge, freed by the caller whatever happens
-    uint64_t *d_skeys = nullptr, *d_rkeys = nullptr;
-    uint8_t *d_scnts = nullptr, *d_rcnts = nullptr;
-    void drop_send()
-    {
-        if (d_skeys)
-            (void)hipFree(d_skeys);
-        if (d_scnts)
-            (void)hipFree(d_scnts);
-        d_skeys = nullptr;
-        d_scnts = nullptr;
-    }
-    void drop_recv()
-    {
-        if (d_rkeys)
-            (void)hipFree(d_rkeys);
-        if (d_rcnts)
-            (void)hipFree(d_rcnts);
-        d_rkeys = nullptr;
-        d_rcnts = nullptr;
-    }
+struct TableJob { // device arrays of one merge
+    DevBuf<uint64_t> d_skeys, d_rkeys;
+    DevBuf<uint8_t> d_scnts, d_rcnts;
 };
 
 // what the three table entries ask of their arguments; `want_merged`: the counter must have been merged over this
@@ -813,9 +769,16 @@ int table_merge_body(brx_comm *cm, brx_counter_t *c, hipStream_t s, TableJob &jo
 
     // 1.-3. every entry of the table, own share included, into (keys, counts) grouped by owner; the table is freed
     std::vector<uint64_t> send_counts(W, 0), recv_counts(W, 0), all((size_t)W * W, 0);
-    int local = tab_split_by_owner(c, W, s, &job.d_skeys, &job.d_scnts, send_counts.data());
+    uint64_t *sk = nullptr;
+    uint8_t *sc = nullptr;
+    int local = tab_split_by_owner(c, W, s, &sk, &sc, send_counts.data());
+    uint64_t n_split = 0;
+    for (int r = 0; r < W; r++)
+        n_split += send_counts[r];
+    job.d_skeys.adopt(sk, n_split); // (the split hands its arrays over)
+    job.d_scnts.adopt(sc, n_split);
     if (local == BRX_OK)
-        local = grow((void **)&cm->d_tables, &cm->tables_cap, (uint64_t)W * W * 8, "send counts of every rank");
+        local = grow_ws(cm->d_tables, (uint64_t)W * W * 8, "send counts of every rank");
     BRX_TRY(agree(cm, local, s));
 
     // 4. everybody's send counts to everybody: every message size and the job's largest message follow
@@ -833,25 +796,23 @@ int table_merge_body(brx_comm *cm, brx_counter_t *c, hipStream_t s, TableJob &jo
     }
 
     // 5. (key, count) pairs to their owners: two arrays, 9 bytes per entry
-    hipError_t e = hipMalloc((void **)&job.d_rkeys, (n_recv + 1) * 8);
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&job.d_rcnts, n_recv + 1);
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%llu B, received table entries): %s", (unsigned long long)((n_recv + 1) * 9), hipGetErrorString(e));
-        local = BRX_ERR_NOMEM;
-    }
+    local = job.d_rkeys.reserve(n_recv + 1, 0, "received table keys");
+    if (local == BRX_OK)
+        local = job.d_rcnts.reserve(n_recv + 1, 0, "received table counts");
     BRX_TRY(agree(cm, local, s));
     const double t_a2a = now_ms();
     BRX_TRY(all_to_all_v(cm, job.d_skeys, send_counts.data(), job.d_rkeys, recv_counts.data(), biggest, 8, ncclUint64, s));
     BRX_TRY(all_to_all_v(cm, job.d_scnts, send_counts.data(), job.d_rcnts, recv_counts.data(), biggest, 1, ncclUint8, s));
     BRX_HIP(hipStreamSynchronize(s));
     const double t_a2a_done = now_ms();
-    job.drop_send();
+    job.d_skeys.reset();
+    job.d_scnts.reset();
 
     // 6. the owner's table: a key comes at most once per source, its counts add up to 255.  The last status exchange
     //    tells every rank whether the JOB has merged counters.
     local = tab_load_pairs(c, job.d_rkeys, job.d_rcnts, n_recv, s);
-    job.drop_recv();
+    job.d_rkeys.reset();
+    job.d_rcnts.reset();
     BRX_TRY(agree(cm, local, s));
     tab_set_merged(c, W, me);
     cm->stats[0] = (n_send - send_counts[me]) * 9;         // entry bytes sent over the links
@@ -868,7 +829,7 @@ int table_spectrum_body(brx_comm *cm, brx_counter_t *c, uint64_t *hist256, int l
 {
     const int W = cm->world, me = cm->rank;
     if (local == BRX_OK)
-        local = grow((void **)&cm->d_tables, &cm->tables_cap, (uint64_t)W * 256 * 8, "spectrum of every rank");
+        local = grow_ws(cm->d_tables, (uint64_t)W * 256 * 8, "spectrum of every rank");
     uint64_t *mine = cm->d_tables + (size_t)me * 256;
     if (local == BRX_OK && hipMemsetAsync(mine, 0, 256 * 8, s) != hipSuccess) {
         set_error("exchange_spectrum: hipMemsetAsync failed");
@@ -952,8 +913,6 @@ int brx_exchange_table_merge(brx_comm_t *cm, brx_counter_t *c, void *stream)
     const int rc = table_merge_body(cm, c, s, job);
     if (rc != BRX_OK)
         abort_after_local_failure(cm);
-    job.drop_send();
-    job.drop_recv();
     if (rc != BRX_OK) { // the table was taken apart: what is left is an empty counter
         const std::string msg = brx_last_error();
         (void)hipStreamSynchronize(s);
@@ -1000,13 +959,6 @@ int brx_exchange_table_finish(brx_comm_t *cm, brx_counter_t *c, uint8_t abundanc
     const int rc = table_finish_body(cm, c, abundance, dst, s, job);
     if (rc != BRX_OK)
         abort_after_local_failure(cm);
-    if (job.d_extracted) {
-        const std::string msg = rc != BRX_OK ? brx_last_error() : "";
-        (void)hipStreamSynchronize(s);
-        (void)hipFree(job.d_extracted);
-        if (rc != BRX_OK)
-            set_error("%s", msg.c_str());
-    }
     return rc;
 }
 

@@ -196,25 +196,19 @@ static int index_build_locked(brx_set *set, const uint64_t *d_keys, uint64_t n, 
     set->idx_gen++;
     const uint64_t n_lines = 1ull << log_lines;
     if (set->lines_alloc < n_lines) {
-        if (set->d_lines)
-            (void)hipFree(set->d_lines);
-        set->d_lines = nullptr;
+        set->d_lines.reset();
         set->lines_alloc = 0;
-        hipError_t e = hipMalloc((void **)&set->d_lines, n_lines * 64ull + n_lines / 8ull + 64ull); // lines + occupancy bits
-        if (e != hipSuccess) {
-            set_error("hipMalloc(%llu B probe index): %s", (unsigned long long)(n_lines * 64ull), hipGetErrorString(e));
-            return BRX_ERR_NOMEM;
-        }
+        BRX_TRY(set->d_lines.reserve_bytes(n_lines * 64ull + n_lines / 8ull + 64ull, 0, "probe index")); // lines + occupancy bits
         set->lines_alloc = n_lines;
     }
-    unsigned long long *d_ovf = nullptr;
-    BRX_HIP(hipMalloc((void **)&d_ovf, 8));
-    hipError_t e = hipMemsetAsync(d_ovf, 0, 8, s);
-    if (e == hipSuccess) {
+    DevBuf<unsigned long long> d_ovf;
+    BRX_TRY(d_ovf.reserve(1, 0, "probe index build"));
+    BRX_HIP(hipMemsetAsync(d_ovf, 0, 8, s));
+    {
         KernelTimer t("index_zero", s);
-        e = hipMemsetAsync(set->d_lines, 0, n_lines * 64ull + n_lines / 8ull + 64ull, s);
+        BRX_HIP(hipMemsetAsync(set->d_lines, 0, n_lines * 64ull + n_lines / 8ull + 64ull, s));
     }
-    if (e == hipSuccess && n) {
+    if (n) {
         KernelTimer t("index_insert", s);
         uint64_t blocks = (n + 255) / 256;
         if (blocks > 256 * 16)
@@ -225,18 +219,11 @@ static int index_build_locked(brx_set *set, const uint64_t *d_keys, uint64_t n, 
         else
             index_insert_kernel<false><<<(int)blocks, 256, 0, s>>>(d_keys, n, set->d_lines, 32u - (uint32_t)log_lines, (uint32_t)m,
                                                                    (uint32_t)(k - m + 1), k, d_ovf, (uint32_t *)(set->d_lines + n_lines * 8ull));
-        e = hipGetLastError();
+        BRX_HIP(hipGetLastError());
     }
     unsigned long long ovf = 0;
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(&ovf, d_ovf, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(s);
-    (void)hipFree(d_ovf);
-    if (e != hipSuccess) {
-        set_error("probe index build: %s", hipGetErrorString(e));
-        return BRX_ERR_HIP;
-    }
+    BRX_HIP(hipMemcpyAsync(&ovf, d_ovf, 8, hipMemcpyDeviceToHost, s));
+    BRX_HIP(hipStreamSynchronize(s));
     set->idx_log_lines = (uint32_t)log_lines;
     set->idx_m = (uint32_t)m;
     set->idx_keys = n;
@@ -291,12 +278,8 @@ int index_insert_reads(brx_set *set, const uint8_t *d_bases, const uint64_t *d_o
             set_error("probe index: bad minimizer length %d for k=%d", m, k);
             return BRX_ERR_ARG;
         }
-        uint64_t *nl = nullptr;
-        hipError_t e = hipMalloc((void **)&nl, (64ull << log_lines) + ((1ull << log_lines) >> 3) + 64ull); // (+ room for occupancy bits)
-        if (e != hipSuccess) {
-            set_error("hipMalloc(%llu B sparse set table): %s", (unsigned long long)(64ull << log_lines), hipGetErrorString(e));
-            return BRX_ERR_NOMEM;
-        }
+        DevBuf<uint64_t> nl;
+        BRX_TRY(nl.reserve_bytes((64ull << log_lines) + ((1ull << log_lines) >> 3) + 64ull, 0, "sparse set table")); // (+ room for occupancy bits)
         BRX_HIP(hipMemsetAsync(nl, 0, 64ull << log_lines, s));
         if (have && set->idx_keys) {
             KernelTimer t("index_rehash", s);
@@ -304,35 +287,22 @@ int index_insert_reads(brx_set *set, const uint8_t *d_bases, const uint64_t *d_o
                                                         (uint32_t)m, (uint32_t)(k - m + 1));
         }
         BRX_HIP(hipStreamSynchronize(s));
-        if (set->d_lines)
-            (void)hipFree(set->d_lines);
-        set->d_lines = nl;
+        set->d_lines = std::move(nl);
         set->lines_alloc = 1ull << log_lines;
         set->idx_log_lines = (uint32_t)log_lines;
         set->idx_m = (uint32_t)m;
     }
-    unsigned long long *d_new = nullptr;
-    BRX_HIP(hipMalloc((void **)&d_new, 8));
-    hipError_t e = hipMemsetAsync(d_new, 0, 8, s);
-    if (e == hipSuccess && n_reads) {
+    DevBuf<unsigned long long> d_new;
+    BRX_TRY(d_new.reserve(1, 0, "sparse set insert"));
+    BRX_HIP(hipMemsetAsync(d_new, 0, 8, s));
+    if (n_reads) {
         KernelTimer t("index_insert_reads", s);
-        int st = flat_presence_insert(d_bases, d_offsets, n_reads, total_bases, k, nullptr, set->d_lines, 32u - set->idx_log_lines,
-                                      set->idx_m, d_new, s);
-        if (st != BRX_OK) {
-            (void)hipFree(d_new);
-            return st;
-        }
+        BRX_TRY(flat_presence_insert(d_bases, d_offsets, n_reads, total_bases, k, nullptr, set->d_lines, 32u - set->idx_log_lines,
+                                     set->idx_m, d_new, s));
     }
     unsigned long long added = 0;
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(&added, d_new, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(s);
-    (void)hipFree(d_new);
-    if (e != hipSuccess) {
-        set_error("sparse set insert: %s", hipGetErrorString(e));
-        return BRX_ERR_HIP;
-    }
+    BRX_HIP(hipMemcpyAsync(&added, d_new, 8, hipMemcpyDeviceToHost, s));
+    BRX_HIP(hipStreamSynchronize(s));
     set->idx_keys += added;
     set->idx_exact = true;
     set->idx_linebits = false; // filled k-mer by k-mer: no occupancy bits
@@ -389,7 +359,7 @@ int index_ensure(const brx_set *cset, hipStream_t s)
         unsigned long long nl = 0;
         BRX_HIP(hipMemcpyAsync(&nl, set->d_keylist_n, 8, hipMemcpyDeviceToHost, s));
         BRX_HIP(hipStreamSynchronize(s));
-        listed = nl <= set->keylist_cap; // a truncated list is useless
+        listed = nl <= set->d_keylist.cap(); // a truncated list is useless
         n = nl;
     }
     if (!listed) {
@@ -398,7 +368,7 @@ int index_ensure(const brx_set *cset, hipStream_t s)
     }
     if (no_bits(set) && !listed) {
         set_error("set without bit vector and without a complete key list (%llu solid k-mers counted, room for %llu)", (unsigned long long)n,
-                  (unsigned long long)set->keylist_cap);
+                  (unsigned long long)set->d_keylist.cap());
         return BRX_ERR_NOMEM;
     }
     if (!no_bits(set) && set->k - index_auto_m(set->k, n) + 1 < 3 && env_int("BRX_INDEX_M", 0) <= 0) {
@@ -408,14 +378,11 @@ int index_ensure(const brx_set *cset, hipStream_t s)
     }
     if (listed)
         return index_build_locked(set, set->d_keylist, n, 0, 0, s);
-    uint64_t *d_keys = nullptr;
-    BRX_HIP(hipMalloc((void **)&d_keys, (n ? n : 1) * 8));
+    DevBuf<uint64_t> d_keys;
+    BRX_TRY(d_keys.reserve(n ? n : 1, 0, "keys of the set"));
     uint64_t got = 0;
-    int st = brx_set_extract_keys_device(set, 0, set->nwords * 32, d_keys, n, &got, s);
-    if (st == BRX_OK)
-        st = index_build_locked(set, d_keys, got, 0, 0, s);
-    (void)hipFree(d_keys);
-    return st;
+    BRX_TRY(brx_set_extract_keys_device(set, 0, set->nwords * 32, d_keys, n, &got, s));
+    return index_build_locked(set, d_keys, got, 0, 0, s);
 }
 
 } // namespace brx
@@ -430,14 +397,11 @@ int brx_set_index_build(brx_set_t *set, int m, int log2_lines, void *stream)
     BRX_HIP(hipStreamSynchronize((hipStream_t)stream));
     uint64_t n = 0;
     BRX_TRY(brx_set_popcount(set, &n));
-    uint64_t *d_keys = nullptr;
-    BRX_HIP(hipMalloc((void **)&d_keys, (n ? n : 1) * 8));
+    DevBuf<uint64_t> d_keys;
+    BRX_TRY(d_keys.reserve(n ? n : 1, 0, "keys of the set"));
     uint64_t got = 0;
-    int st = brx_set_extract_keys_device(set, 0, set->nwords * 32, d_keys, n, &got, stream);
-    if (st == BRX_OK)
-        st = index_build_from_keys(set, d_keys, got, m, log2_lines, (hipStream_t)stream);
-    (void)hipFree(d_keys);
-    return st;
+    BRX_TRY(brx_set_extract_keys_device(set, 0, set->nwords * 32, d_keys, n, &got, stream));
+    return index_build_from_keys(set, d_keys, got, m, log2_lines, (hipStream_t)stream);
 }
 
 int brx_set_index_build_from_keys_device(brx_set_t *set, const uint64_t *d_keys, uint64_t n, int m, int log2_lines, void *stream)
@@ -462,7 +426,7 @@ int brx_set_keylist_device(const brx_set_t *set, void **d_keys, uint64_t *n, voi
     unsigned long long nl = 0;
     BRX_HIP(hipMemcpyAsync(&nl, set->d_keylist_n, 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
     BRX_HIP(hipStreamSynchronize((hipStream_t)stream));
-    if (nl > set->keylist_cap)
+    if (nl > set->d_keylist.cap())
         return BRX_OK; // truncated list: treat as absent
     *d_keys = set->d_keylist;
     *n = nl;
@@ -535,38 +499,25 @@ int brx_set_fingerprint(const brx_set_t *set, uint64_t *out3, void *stream)
         return BRX_ERR_ARG;
     BRX_TRY(use_device(set->device));
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long *d = nullptr;
-    BRX_HIP(hipMalloc((void **)&d, 24));
-    hipError_t e = hipMemsetAsync(d, 0, 24, s);
-    const char *what = "list";
-    if (e == hipSuccess) {
-        if (set->keylist_valid) { // (a truncated list is never left valid with a set that has nothing else)
-            fp_list_kernel<<<2048, 256, 0, s>>>(set->d_keylist, set->d_keylist_n, set->keylist_cap, d);
-        } else if (no_bits(set)) {
-            // no bit vector (sparse, or lazy and not written): the chained table is exact and holds every key once
-            if (!set->idx_valid || !set->d_lines) {
-                (void)hipFree(d);
-                set_error("fingerprint: the set has neither a bit vector, nor a key list, nor a table");
-                return BRX_ERR_UNSUPPORTED;
-            }
-            what = "table";
-            fp_table_kernel<<<4096, 256, 0, s>>>(set->d_lines, 1ull << set->idx_log_lines, d);
-        } else {
-            what = "bits";
-            fp_bits_kernel<<<4096, 256, 0, s>>>(set->d_bits, set->nwords, d);
+    DevBuf<unsigned long long> d;
+    BRX_TRY(d.reserve(3, 0, "fingerprint"));
+    BRX_HIP(hipMemsetAsync(d, 0, 24, s));
+    if (set->keylist_valid) { // (a truncated list is never left valid with a set that has nothing else)
+        fp_list_kernel<<<2048, 256, 0, s>>>(set->d_keylist, set->d_keylist_n, set->d_keylist.cap(), d);
+    } else if (no_bits(set)) {
+        // no bit vector (sparse, or lazy and not written): the chained table is exact and holds every key once
+        if (!set->idx_valid || !set->d_lines) {
+            set_error("fingerprint: the set has neither a bit vector, nor a key list, nor a table");
+            return BRX_ERR_UNSUPPORTED;
         }
-        e = hipGetLastError();
+        fp_table_kernel<<<4096, 256, 0, s>>>(set->d_lines, 1ull << set->idx_log_lines, d);
+    } else {
+        fp_bits_kernel<<<4096, 256, 0, s>>>(set->d_bits, set->nwords, d);
     }
+    BRX_HIP(hipGetLastError());
     unsigned long long h[3] = {0, 0, 0};
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(h, d, 24, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(s);
-    (void)hipFree(d);
-    if (e != hipSuccess) {
-        set_error("fingerprint (%s): %s", what, hipGetErrorString(e));
-        return BRX_ERR_HIP;
-    }
+    BRX_HIP(hipMemcpyAsync(h, d, 24, hipMemcpyDeviceToHost, s));
+    BRX_HIP(hipStreamSynchronize(s));
     out3[0] = h[0];
     out3[1] = h[1];
     out3[2] = h[2];
@@ -580,9 +531,8 @@ int brx_set_index_drop(brx_set_t *set)
     std::lock_guard<std::mutex> g(set->idx_mu);
     set->idx_valid = false;
     set->idx_gen++;
-    if (set->d_lines && use_device(set->device) == BRX_OK)
-        (void)hipFree(set->d_lines);
-    set->d_lines = nullptr;
+    (void)use_device(set->device);
+    set->d_lines.reset();
     set->lines_alloc = 0;
     return BRX_OK;
 }
@@ -619,34 +569,19 @@ int brx_set_get_batch_indexed(const brx_set_t *set, const uint64_t *forward_kmer
         *n_fallback = 0;
     if (!n)
         return BRX_OK;
-    uint64_t *d_k = nullptr;
-    uint8_t *d_o = nullptr;
-    unsigned long long *d_f = nullptr;
-    BRX_HIP(hipMalloc((void **)&d_k, (uint64_t)n * 8));
-    hipError_t e = hipMalloc((void **)&d_o, n);
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&d_f, 8);
-    if (e == hipSuccess)
-        e = hipMemset(d_f, 0, 8);
-    if (e == hipSuccess)
-        e = hipMemcpy(d_k, forward_kmers, (uint64_t)n * 8, hipMemcpyHostToDevice);
+    DevBuf<uint64_t> d_k;
+    DevBuf<uint8_t> d_o;
+    DevBuf<unsigned long long> d_f;
+    BRX_TRY(d_k.reserve(n, 0, "get_batch_indexed k-mers"));
+    BRX_TRY(d_o.reserve(n, 0, "get_batch_indexed answers"));
+    BRX_TRY(d_f.reserve(1, 0, "get_batch_indexed"));
+    BRX_HIP(hipMemset(d_f, 0, 8));
+    BRX_HIP(hipMemcpy(d_k, forward_kmers, (uint64_t)n * 8, hipMemcpyHostToDevice));
     unsigned long long fb = 0;
-    if (e == hipSuccess) {
-        IdxView v{set->d_lines, 32u - set->idx_log_lines, set->idx_m, (uint32_t)set->k - set->idx_m + 1u};
-        index_get_kernel<<<(n + 255) / 256, 256>>>(v, no_bits(set) ? nullptr : set->d_bits, d_k, n, set->k, d_o, d_f);
-        e = hipMemcpy(out, d_o, n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess)
-            e = hipMemcpy(&fb, d_f, 8, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(d_k);
-    if (d_o)
-        (void)hipFree(d_o);
-    if (d_f)
-        (void)hipFree(d_f);
-    if (e != hipSuccess) {
-        set_error("get_batch_indexed: %s", hipGetErrorString(e));
-        return BRX_ERR_HIP;
-    }
+    IdxView v{set->d_lines, 32u - set->idx_log_lines, set->idx_m, (uint32_t)set->k - set->idx_m + 1u};
+    index_get_kernel<<<(n + 255) / 256, 256>>>(v, no_bits(set) ? nullptr : set->d_bits.get(), d_k, n, set->k, d_o, d_f);
+    BRX_HIP(hipMemcpy(out, d_o, n, hipMemcpyDeviceToHost));
+    BRX_HIP(hipMemcpy(&fb, d_f, 8, hipMemcpyDeviceToHost));
     if (n_fallback)
         *n_fallback = fb;
     return BRX_OK;

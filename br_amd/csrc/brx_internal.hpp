@@ -10,6 +10,7 @@
 
 #include "../../include/brx.h"
 #include "brx_kmer.hpp"
+#include "brx_devbuf.hpp"
 
 namespace brx {
 
@@ -38,9 +39,7 @@ void *host_buf_acquire(size_t bytes);
 void host_buf_release(void *p);
 bool host_buf_is_pinned(const void *p);
 
-// device memory through the block pool (brx_devpool.hip); every hipMalloc / hipFree below this header is one of these
-hipError_t dev_alloc(void **out, size_t bytes);
-hipError_t dev_free(void *p);
+// device memory through the block pool (brx_devpool.hip; dev_alloc / dev_free are declared in brx_devbuf.hpp)
 void dev_pool_trim();
 size_t dev_pool_bytes();
 
@@ -96,7 +95,7 @@ struct brx_set {
     int k;
     int device;
     uint64_t nwords;   // u32 words
-    uint32_t *d_bits;  // nwords, zero padded; nullptr for a sparse set
+    brx::DevBuf<uint32_t> d_bits; // nwords, zero padded; empty for a sparse set
     // sparse set (k >= 21: 2^(2k-1) bits do not fit): the solid hashes live in the key list and in the probe
     // index only, whose overflowing lines then chain into the next line instead of falling back to the bits
     bool sparse;
@@ -107,7 +106,7 @@ struct brx_set {
     bool idx_open;           // ... and k-mer by k-mer (brx_set_insert_batch on a sparse set): more can be added
     // probe index over the same set (brx_index.hpp): built on demand, invalidated by every mutation
     // of the bits that goes through the ABI
-    uint64_t *d_lines;       // 8 u64 per line
+    brx::DevBuf<uint64_t> d_lines; // 8 u64 per line
     uint64_t lines_alloc;    // lines allocated (the allocation also holds lines_alloc / 8 bytes of occupancy bits behind the lines)
     bool idx_linebits = false; // the occupancy bits are current (indexes built from a key list)
     uint32_t idx_log_lines;
@@ -117,15 +116,14 @@ struct brx_set {
     // successor table beside the index (brx_onelane.hip): per line, one byte per slot -- for either orientation of the
     // slot's k-mer, whether it has exactly one solid successor and which.  Built on first use by a walking corrector,
     // stale whenever the index changes (idx_gen counts the changes).
-    uint64_t *d_succ = nullptr;
+    brx::DevBuf<uint64_t> d_succ;
     uint64_t succ_lines = 0;     // lines the table was allocated for
     uint64_t succ_gen = ~0ull;   // idx_gen it was built at
     uint64_t idx_gen = 0;
     uint64_t idx_keys, idx_overflow_keys;
     // solid hashes of the current bits, when the builder produced them on the side (partitioned finish)
-    uint64_t *d_keylist;
-    uint64_t keylist_cap;                 // entries
-    unsigned long long *d_keylist_n;      // device counter (may exceed keylist_cap: list truncated)
+    brx::DevBuf<uint64_t> d_keylist;             // (its cap(): entries)
+    brx::DevBuf<unsigned long long> d_keylist_n; // device counter (may exceed the list's capacity: list truncated)
     bool keylist_valid;
     std::mutex idx_mu;
 };
@@ -172,12 +170,12 @@ struct brx_counter {
     int device;
     int strategy;
     // dense: u8 table packed in u32 words (2^(2k-1) bytes, padded to 32 B)
-    uint32_t *d_counts;
+    brx::DevBuf<uint32_t> d_counts;
     uint64_t count_bytes;
     // partitioned strategy (brx_partbuild.hip)
     brx::PartState *part;
-    uint64_t *d_keys;
-    uint64_t n_keys, cap_keys;
+    brx::DevBuf<uint64_t> d_keys;
+    uint64_t n_keys;
     // counting-table strategy (brx_counttable.hip)
     brx::TabState *tab = nullptr;
     hipStream_t stream; // owned, used by host-pointer entry points
@@ -219,7 +217,7 @@ __host__ __device__ inline uint32_t table_owner_of(uint64_t hash, uint32_t world
 }
 // The table side of that merge (brx_counttable.hip).  split: every entry of the table into two arrays the call allocates
 // (keys u64 = bit indices, counts u8 = min(255, count)), grouped by owner, per_owner[r] entries for rank r in rank order;
-// the table is freed, the arrays are the caller's (hipFree; both nullptr when nothing was counted).  load_pairs: a fresh
+// the table is freed, the arrays are the caller's (DevBuf::adopt them; both nullptr when nothing was counted).  load_pairs: a fresh
 // table for `n` (key, count) pairs, counts of one key summed up to 255 -- the counter must hold no table (after split).
 // Both synchronise `s`.  set_merged / merged: the mark a merged counter carries until it is reset (world 0: not merged).
 int tab_split_by_owner(brx_counter *c, int world, hipStream_t s, uint64_t **d_keys, uint8_t **d_cnts, uint64_t *per_owner);
@@ -253,39 +251,26 @@ int abund_refuse_partitioned(const char *what, int k);
 }
 
 struct brx_chain {
-    const brx_set *set;
-    int device;
+    const brx_set *set = nullptr;
+    int device = 0;
     std::vector<brx_method_t> methods;
-    bool two_side;           // second_pass == BRX_PASS_NONE
+    bool two_side = false;   // second_pass == BRX_PASS_NONE
     int second_pass = BRX_PASS_REVERSE; // BRX_PASS_*
-    hipStream_t stream; // owned
+    hipStream_t stream = nullptr; // owned
     // workspace (grown on demand)
-    uint8_t *d_stage[2];
-    uint64_t stage_bytes;
-    uint32_t *d_lens[2];
-    uint64_t lens_cap;
-    uint64_t *d_scan_tmp;
-    uint64_t scan_tmp_cap;
-    uint64_t *d_path;   // graph-walk visited lists (Graph / GapSize)
-    uint32_t *d_rev_list = nullptr; // reads the lean reverse pass handed back (rev_scan_kernel)
-    uint64_t rev_list_bytes = 0;
-    uint32_t *d_rev_flag = nullptr; // ... one word per read: entered into that list already
-    uint64_t rev_flag_bytes = 0;
-    void *d_rev_trig = nullptr;     // triggers the lean reverse pass left to the verify pass (TrigRec)
-    uint64_t rev_trig_bytes = 0;
-    uint64_t path_bytes;
-    uint64_t *d_ctrl;   // device control block (work counter, overflow, stats)
-    uint64_t *h_ctrl;   // pinned mirror
+    brx::DevBuf<uint8_t> d_stage[2];
+    brx::DevBuf<uint32_t> d_lens[2];
+    brx::DevBuf<uint64_t> d_scan_tmp;
+    brx::DevBuf<uint64_t> d_path;     // graph-walk visited lists (Graph / GapSize)
+    brx::DevBuf<uint32_t> d_rev_list; // reads the lean reverse pass handed back (rev_scan_kernel)
+    brx::DevBuf<uint32_t> d_rev_flag; // ... one word per read: entered into that list already
+    brx::DevBuf<uint8_t> d_rev_trig;  // triggers the lean reverse pass left to the verify pass (TrigRec)
+    brx::DevBuf<uint64_t> d_ctrl;     // device control block (work counter, overflow, stats)
+    uint64_t *h_ctrl = nullptr;       // pinned mirror
     // host-entry staging
-    uint8_t *d_in;
-    uint64_t d_in_cap;
-    uint64_t *d_off;
-    uint64_t d_off_cap;
-    uint8_t *d_out;
-    uint64_t d_out_cap;
-    uint64_t *d_out_off;
-    uint64_t d_out_off_cap;
-    uint64_t last_stats[8];
+    brx::DevBuf<uint8_t> d_in, d_out;
+    brx::DevBuf<uint64_t> d_off, d_out_off;
+    uint64_t last_stats[8] = {};
     // workspace sizes that a batch of this chain has needed so far: the next batch starts from them, so that one
     // long walk or one read that grows a lot costs its own batch a second run, not every batch after it
     uint32_t slack_seen = 1, maxpath_seen = 4096;
@@ -299,28 +284,3 @@ struct brx_chain {
     void *async_job = nullptr; // a batch in flight (brx_chain_correct_batch_async), owned by the chain
     std::mutex mu;
 };
-
-// The library's device memory comes from the block pool (brx_devpool.hip, which does not include this header).
-#define hipMalloc(ptr, bytes) brx::dev_alloc((void **)(ptr), (bytes))
-#define hipFree(ptr) brx::dev_free((void *)(ptr))
-
-namespace brx {
-// device blocks of one call, from the block pool; released when the call returns
-struct DevScratch {
-    std::vector<void *> blocks;
-    ~DevScratch()
-    {
-        for (void *p : blocks)
-            (void)hipFree(p);
-    }
-    template <typename T>
-    int get(T **out, uint64_t n)
-    {
-        void *p = nullptr;
-        BRX_HIP(hipMalloc(&p, (n ? n : 1) * sizeof(T)));
-        blocks.push_back(p);
-        *out = (T *)p;
-        return BRX_OK;
-    }
-};
-}

@@ -757,12 +757,11 @@ int read_header(int fd, KeyHeader *h)
     return BRX_OK;
 }
 
-// the blocks behind a header, from in_fd to *d_keys (and *d_cnts when want_counts) -- blocks of the device pool the caller
-// frees (nullptr when the file holds no key).  st8[1..3], [5], [6] are filled.  Returns after `s` has been synchronised.
-int read_blocks(int fd, const KeyHeader &h, bool want_counts, hipStream_t s, uint64_t **d_keys, uint8_t **d_cnts, uint64_t *st8)
+// the blocks behind a header, from in_fd to d_keys (and d_cnts when want_counts; both empty when the file holds no key).  st8[1..3], [5], [6] are filled.  Returns after `s` has been synchronised.
+int read_blocks(int fd, const KeyHeader &h, bool want_counts, hipStream_t s, DevBuf<uint64_t> &d_keys, DevBuf<uint8_t> &d_cnts, uint64_t *st8)
 {
-    *d_keys = nullptr;
-    *d_cnts = nullptr;
+    d_keys.reset();
+    d_cnts.reset();
     const uint64_t n = h.n, n_blocks = (n + KF_BLOCK - 1) / KF_BLOCK;
     const size_t piece = slice_bytes();
     uint64_t file_bytes = 32, max_w = 0, ns_fd = 0;
@@ -783,13 +782,9 @@ int read_blocks(int fd, const KeyHeader &h, bool want_counts, hipStream_t s, uin
     }
     BRX_TRY(ws.get(&d_ctl, 2));
     if (n) {
-        hipError_t e = hipMalloc((void **)d_keys, n * 8);
-        if (e == hipSuccess && h.with_counts && want_counts)
-            e = hipMalloc((void **)d_cnts, n);
-        if (e != hipSuccess) {
-            set_error("key file: hipMalloc(%llu B for %llu keys): %s", (u64)(n * 9), (u64)n, hipGetErrorString(e));
-            return BRX_ERR_NOMEM;
-        }
+        BRX_TRY(d_keys.reserve(n, 0, "keys of the key file"));
+        if (h.with_counts && want_counts)
+            BRX_TRY(d_cnts.reserve(n, 0, "counts of the key file"));
     }
     auto run = [&]() -> int {
         BRX_HIP(hipMemsetAsync(d_ctl, 0, 16, s));
@@ -836,8 +831,8 @@ int read_blocks(int fd, const KeyHeader &h, bool want_counts, hipStream_t s, uin
             {
                 KernelTimer kt("key_unpack", s);
                 unpack_kernel<<<read_grid((nb + 3u) / 4u, 256u * 16u), 256, 0, s>>>(d_buf[cur], d_off[cur], nb, done, n, set_nbits(h.k),
-                                                                                   h.with_counts ? 1u : 0u, h.floor > 1 ? h.floor : 1u, *d_keys,
-                                                                                   *d_cnts, d_ctl, (uint32_t *)(d_ctl + 1));
+                                                                                   h.with_counts ? 1u : 0u, h.floor > 1 ? h.floor : 1u, d_keys,
+                                                                                   d_cnts, d_ctl, (uint32_t *)(d_ctl + 1));
                 BRX_HIP(hipGetLastError());
             }
             BRX_HIP(hipEventRecord(ev.e[cur], s));
@@ -867,7 +862,7 @@ int read_blocks(int fd, const KeyHeader &h, bool want_counts, hipStream_t s, uin
         }
         if (n_blocks > 1) {
             KernelTimer kt("key_unpack", s);
-            order_check_kernel<<<read_grid((n_blocks + 255) / 256, 256u * 16u), 256, 0, s>>>(*d_keys, n_blocks, (uint32_t *)(d_ctl + 1));
+            order_check_kernel<<<read_grid((n_blocks + 255) / 256, 256u * 16u), 256, 0, s>>>(d_keys, n_blocks, (uint32_t *)(d_ctl + 1));
             BRX_HIP(hipGetLastError());
         }
         u64 ctl[2] = {0, 0};
@@ -900,12 +895,8 @@ int read_blocks(int fd, const KeyHeader &h, bool want_counts, hipStream_t s, uin
     st8[6] = ns_fd;
     st8[5] = ns_since(t0) - ns_fd;
     if (st != BRX_OK || e != hipSuccess) {
-        if (*d_keys)
-            (void)hipFree(*d_keys);
-        if (*d_cnts)
-            (void)hipFree(*d_cnts);
-        *d_keys = nullptr;
-        *d_cnts = nullptr;
+        d_keys.reset();
+        d_cnts.reset();
         if (st == BRX_OK) {
             set_error("key file: unpack: %s", hipGetErrorString(e));
             return BRX_ERR_HIP;
@@ -942,11 +933,11 @@ int table_counter_only(const char *me, brx_counter *c)
     return BRX_OK;
 }
 
-// the keys of a set, whatever holds it, into a block of the device pool the caller frees; a lazy bit vector stays lazy
-int list_set(const brx_set *cset, hipStream_t s, uint64_t **d_out, uint64_t *n_out)
+// the keys of a set, whatever holds it, into d_out; a lazy bit vector stays lazy
+int list_set(const brx_set *cset, hipStream_t s, DevBuf<uint64_t> &d_out, uint64_t *n_out)
 {
     brx_set *set = const_cast<brx_set *>(cset);
-    *d_out = nullptr;
+    d_out.reset();
     *n_out = 0;
     {
         std::lock_guard<std::mutex> g(set->idx_mu);
@@ -954,11 +945,11 @@ int list_set(const brx_set *cset, hipStream_t s, uint64_t **d_out, uint64_t *n_o
             u64 nl = 0;
             BRX_HIP(hipMemcpyAsync(&nl, set->d_keylist_n, 8, hipMemcpyDeviceToHost, s));
             BRX_HIP(hipStreamSynchronize(s));
-            if (nl <= set->keylist_cap) { // (a truncated list is no list)
+            if (nl <= set->d_keylist.cap()) { // (a truncated list is no list)
                 if (nl) {
-                    BRX_HIP(hipMalloc((void **)d_out, nl * 8));
+                    BRX_TRY(d_out.reserve(nl, 0, "keys of the set"));
                     KernelTimer kt("key_list", s);
-                    BRX_HIP(hipMemcpyAsync(*d_out, set->d_keylist, nl * 8, hipMemcpyDeviceToDevice, s));
+                    BRX_HIP(hipMemcpyAsync(d_out, set->d_keylist, nl * 8, hipMemcpyDeviceToDevice, s));
                 }
                 *n_out = nl;
                 return BRX_OK;
@@ -976,10 +967,10 @@ int list_set(const brx_set *cset, hipStream_t s, uint64_t **d_out, uint64_t *n_o
             u64 *d_n = nullptr;
             BRX_TRY(ws.get(&d_n, 1));
             BRX_HIP(hipMemsetAsync(d_n, 0, 8, s));
-            BRX_HIP(hipMalloc((void **)d_out, cap * 8));
+            BRX_TRY(d_out.reserve(cap, 0, "keys of the set"));
             {
                 KernelTimer kt("key_list", s);
-                table_list_kernel<<<grid_of(n_slots, LIST_CHUNK), 256, 0, s>>>(set->d_lines, nullptr, n_slots, 1u, *d_out, nullptr, cap, d_n);
+                table_list_kernel<<<grid_of(n_slots, LIST_CHUNK), 256, 0, s>>>(set->d_lines, nullptr, n_slots, 1u, d_out, nullptr, cap, d_n);
                 BRX_HIP(hipGetLastError());
             }
             u64 got = 0;
@@ -999,10 +990,10 @@ int list_set(const brx_set *cset, hipStream_t s, uint64_t **d_out, uint64_t *n_o
     BRX_TRY(brx_set_popcount(set, &n));
     if (!n)
         return BRX_OK;
-    BRX_HIP(hipMalloc((void **)d_out, n * 8));
+    BRX_TRY(d_out.reserve(n, 0, "keys of the set"));
     {
         KernelTimer kt("key_list", s);
-        BRX_TRY(brx_set_extract_keys_device(set, 0, set->nwords * 32, *d_out, n, &got, s));
+        BRX_TRY(brx_set_extract_keys_device(set, 0, set->nwords * 32, d_out, n, &got, s));
     }
     *n_out = got;
     return BRX_OK;
@@ -1138,18 +1129,16 @@ int brx_counter_load_fd(brx_counter_t *c, int in_fd, uint64_t *stats8)
                   (int)h.floor, (u64)info[2]);
         return BRX_ERR_ARG;
     }
-    uint64_t *d_keys = nullptr;
-    uint8_t *d_cnts = nullptr;
-    st = read_blocks(in_fd, h, true, s, &d_keys, &d_cnts, st8);
+    DevBuf<uint64_t> d_keys;
+    DevBuf<uint8_t> d_cnts;
+    st = read_blocks(in_fd, h, true, s, d_keys, d_cnts, st8);
     if (st == BRX_OK && h.n) {
         auto t1 = Clock::now();
         st = tab_merge_pairs(c, d_keys, d_cnts, h.n, s);
         st8[4] = ns_since(t1);
     }
-    if (d_keys)
-        (void)hipFree(d_keys);
-    if (d_cnts)
-        (void)hipFree(d_cnts);
+    d_keys.reset(); // (before the counter is reset after a failure)
+    d_cnts.reset();
     if (st != BRX_OK)
         return fail(st);
     if (h.floor > 1)
@@ -1177,17 +1166,15 @@ int brx_set_save_fd(const brx_set_t *set, int out_fd, uint64_t *stats8)
     BRX_TRY(use_device(set->device));
     hipStream_t s = nullptr;
     BRX_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    uint64_t *d_keys = nullptr;
+    DevBuf<uint64_t> d_keys;
     uint64_t n = 0;
-    int st = list_set(set, s, &d_keys, &n);
+    int st = list_set(set, s, d_keys, &n);
     if (st == BRX_OK)
         st = sort_pairs(d_keys, nullptr, n, (uint32_t)(2 * set->k - 1), s);
     st8[4] = ns_since(t0);
     if (st == BRX_OK)
         st = pack_and_write(set->k, d_keys, nullptr, n, 0, out_fd, s, st8);
     (void)hipStreamSynchronize(s);
-    if (d_keys)
-        (void)hipFree(d_keys);
     (void)hipStreamDestroy(s);
     st8[0] = n;
     st8[7] = ns_since(t0);
@@ -1211,24 +1198,21 @@ int brx_set_load_fd(int in_fd, int device, brx_set_t **out, uint64_t *stats8)
     BRX_TRY(read_header(in_fd, &h));
     hipStream_t s = nullptr;
     BRX_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    uint64_t *d_keys = nullptr;
-    uint8_t *d_cnts = nullptr;
+    DevBuf<uint64_t> d_keys;
+    DevBuf<uint8_t> d_cnts;
     brx_set *set = nullptr;
-    int st = read_blocks(in_fd, h, false, s, &d_keys, &d_cnts, st8); // (the counts of a count file are checked and dropped)
+    int st = read_blocks(in_fd, h, false, s, d_keys, d_cnts, st8); // (the counts of a count file are checked and dropped)
     if (st == BRX_OK)
         st = set_alloc_unwritten(h.k, device, &set);
     auto build = [&]() -> int {
         auto t1 = Clock::now();
         // the keys become the set's key list: what a finish leaves
-        if (!set->d_keylist_n)
-            BRX_HIP(hipMalloc((void **)&set->d_keylist_n, 8));
+        BRX_TRY(set->d_keylist_n.reserve(1, 0, "key list counter"));
         const u64 n = h.n;
         BRX_HIP(hipMemcpyAsync(set->d_keylist_n, &n, 8, hipMemcpyHostToDevice, s));
         BRX_HIP(hipStreamSynchronize(s));
-        set->d_keylist = d_keys;
-        set->keylist_cap = h.n;
+        set->d_keylist = std::move(d_keys);
         set->keylist_valid = true;
-        d_keys = nullptr;
         if (set->sparse) {
             BRX_TRY(index_build_from_keys(set, set->d_keylist, h.n, 0, 0, s));
         } else {
@@ -1236,10 +1220,7 @@ int brx_set_load_fd(int in_fd, int device, brx_set_t **out, uint64_t *stats8)
             BRX_TRY(ensure_bits(set, s, me));
             if (!index_wanted(set->k)) { // as after a finish at this k: the bits are the set
                 set->keylist_valid = false;
-                if (set->d_keylist)
-                    (void)hipFree(set->d_keylist);
-                set->d_keylist = nullptr;
-                set->keylist_cap = 0;
+                set->d_keylist.reset();
             }
         }
         st8[4] = ns_since(t1);
@@ -1249,8 +1230,6 @@ int brx_set_load_fd(int in_fd, int device, brx_set_t **out, uint64_t *stats8)
         st = build();
     (void)hipStreamSynchronize(s);
     (void)hipStreamDestroy(s);
-    if (d_keys)
-        (void)hipFree(d_keys);
     if (st != BRX_OK) {
         if (set)
             brx_set_free(set);

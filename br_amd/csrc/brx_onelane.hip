@@ -2139,28 +2139,13 @@ __global__ __launch_bounds__(256) void lane_apply_walk_kernel(LaneArgs a)
 }
 
 struct LaneWork {
-    uint32_t *nu = nullptr, *u_read = nullptr, *u_q = nullptr, *u_res = nullptr, *fail_list = nullptr, *P = nullptr;
-    uint16_t *M = nullptr;
-    UnitDesc *u_desc = nullptr;
-    uint4 *u_in = nullptr;
-    uint32_t *E[MAX_DEPTH] = {nullptr, nullptr, nullptr};
-    uint32_t *BW[MAX_DEPTH] = {nullptr, nullptr, nullptr};
-    uint64_t *ubase = nullptr, *u_qk = nullptr;
-    uint64_t reads_cap = 0, units_cap = 0, p_cap = 0, e_cap = 0, bw_cap = 0;
+    DevBuf<uint32_t> nu, u_read, u_q, u_res, fail_list, P;
+    DevBuf<uint16_t> M;
+    DevBuf<UnitDesc> u_desc;
+    DevBuf<uint4> u_in;
+    DevBuf<uint32_t> E[MAX_DEPTH], BW[MAX_DEPTH];
+    DevBuf<uint64_t> ubase, u_qk;
 };
-
-int grow_dev(void **ptr, uint64_t bytes)
-{
-    if (*ptr)
-        (void)hipFree(*ptr);
-    *ptr = nullptr;
-    hipError_t e = hipMalloc(ptr, bytes);
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%llu B, lane pass workspace): %s", (unsigned long long)bytes, hipGetErrorString(e));
-        return BRX_ERR_NOMEM;
-    }
-    return BRX_OK;
-}
 
 template <bool IDX, int M>
 void launch_lane_walk(const LaneArgs &a, uint32_t blocks, hipStream_t s)
@@ -2196,15 +2181,7 @@ uint32_t env_u32(const char *name, uint32_t dflt)
 
 void lane_ws_free(brx_chain *ch)
 {
-    LaneWork *w = (LaneWork *)ch->lane_ws;
-    if (!w)
-        return;
-    for (void *q : {(void *)w->u_in, (void *)w->u_desc, (void *)w->nu, (void *)w->u_read, (void *)w->u_q, (void *)w->u_res, (void *)w->fail_list, (void *)w->P, (void *)w->M,
-                    (void *)w->E[0], (void *)w->E[1], (void *)w->E[2], (void *)w->BW[0], (void *)w->BW[1], (void *)w->BW[2], (void *)w->ubase,
-                    (void *)w->u_qk})
-        if (q)
-            (void)hipFree(q);
-    delete w;
+    delete (LaneWork *)ch->lane_ws;
     ch->lane_ws = nullptr;
 }
 
@@ -2265,47 +2242,26 @@ int lane_pass(brx_chain *ch, const PassParams &p, const LanePassInfo &info, hipS
         return BRX_ERR_UNSUPPORTED;
     const uint64_t p_bound = (info.in_total_bound >> 4) + 5ull * p.n_reads + 16ull;                        // dwords
     const uint64_t e_bound = (info.in_total_bound >> 2) + 16ull * (units_bound + 2ull * p.n_reads) + 64ull; // entries
-    if (w->reads_cap < p.n_reads) {
-        w->reads_cap = 0; // (a growth that fails half-way leaves freed pointers: nothing here may be trusted then)
-        const uint64_t cap = (uint64_t)p.n_reads + p.n_reads / 8 + 64;
-        BRX_TRY(grow_dev((void **)&w->nu, cap * 4));
-        BRX_TRY(grow_dev((void **)&w->fail_list, cap * 4));
-        BRX_TRY(grow_dev((void **)&w->ubase, (cap + 1) * 8));
-        w->reads_cap = cap;
-    }
-    if (w->units_cap < units_bound) {
-        w->units_cap = 0; // (a growth that fails half-way leaves freed pointers: nothing here may be trusted then)
-        const uint64_t cap = units_bound + units_bound / 8 + 64;
-        BRX_TRY(grow_dev((void **)&w->u_read, cap * 4));
-        BRX_TRY(grow_dev((void **)&w->u_q, cap * 4));
-        BRX_TRY(grow_dev((void **)&w->u_qk, cap * 8));
-        BRX_TRY(grow_dev((void **)&w->u_res, cap * 32));
-        BRX_TRY(grow_dev((void **)&w->u_desc, cap * sizeof(UnitDesc)));
-        BRX_TRY(grow_dev((void **)&w->u_in, cap * 16));
-        w->units_cap = cap;
-    }
-    if (w->p_cap < p_bound) {
-        w->p_cap = 0; // (a growth that fails half-way leaves freed pointers: nothing here may be trusted then)
-        const uint64_t cap = p_bound + p_bound / 16;
-        BRX_TRY(grow_dev((void **)&w->P, cap * 4));
-        BRX_TRY(grow_dev((void **)&w->M, cap * 2));
-        w->p_cap = cap;
-    }
-    if (w->e_cap < e_bound) {
-        w->e_cap = 0; // (a growth that fails half-way leaves freed pointers: nothing here may be trusted then)
-        const uint64_t cap = e_bound + e_bound / 16;
+    const char *what = "lane pass workspace";
+    const uint64_t n = p.n_reads, hr = n / 8 + 64; // per read
+    BRX_TRY(w->nu.reserve(n, hr, what));
+    BRX_TRY(w->fail_list.reserve(n, hr, what));
+    BRX_TRY(w->ubase.reserve(n + 1, hr, what));
+    const uint64_t hu = units_bound / 8 + 64; // per unit
+    BRX_TRY(w->u_read.reserve(units_bound, hu, what));
+    BRX_TRY(w->u_q.reserve(units_bound, hu, what));
+    BRX_TRY(w->u_qk.reserve(units_bound, hu, what));
+    BRX_TRY(w->u_res.reserve(units_bound * 8, hu * 8, what)); // (32 B per unit)
+    BRX_TRY(w->u_desc.reserve(units_bound, hu, what));
+    BRX_TRY(w->u_in.reserve(units_bound, hu, what));
+    BRX_TRY(w->P.reserve(p_bound, p_bound / 16, what));
+    BRX_TRY(w->M.reserve(p_bound, p_bound / 16, what));
+    for (int d = 0; d < MAX_DEPTH; d++)
+        BRX_TRY(w->E[d].reserve(e_bound, e_bound / 16, what));
+    if (walk)
         for (int d = 0; d < MAX_DEPTH; d++)
-            BRX_TRY(grow_dev((void **)&w->E[d], cap * 4));
-        w->e_cap = cap;
-    }
-    if (walk && w->bw_cap < e_bound) {
-        w->bw_cap = 0;
-        const uint64_t cap = e_bound + e_bound / 16;
-        for (int d = 0; d < MAX_DEPTH; d++)
-            BRX_TRY(grow_dev((void **)&w->BW[d], cap * 4));
-        w->bw_cap = cap;
-    }
-    if (scan_tmp_bytes(p.n_reads) > ch->scan_tmp_cap) {
+            BRX_TRY(w->BW[d].reserve(e_bound, e_bound / 16, what));
+    if (scan_tmp_bytes(p.n_reads) > ch->d_scan_tmp.bytes()) {
         set_error("lane pass: scan scratch smaller than the batch");
         return BRX_ERR_ARG;
     }
@@ -2335,7 +2291,7 @@ int lane_pass(brx_chain *ch, const PassParams &p, const LanePassInfo &info, hipS
     a.M = use_mask ? w->M : nullptr;
     for (int d = 0; d < MAX_DEPTH; d++) {
         a.E[d] = w->E[d];
-        a.EW[d] = reinterpret_cast<uint2 *>(w->E[d]); // (8-byte entries at half the index: the same bytes)
+        a.EW[d] = reinterpret_cast<uint2 *>(w->E[d].get()); // (8-byte entries at half the index: the same bytes)
         a.BW[d] = w->BW[d];
     }
     if (info.method == BRX_GRAPH)
@@ -2343,10 +2299,10 @@ int lane_pass(brx_chain *ch, const PassParams &p, const LanePassInfo &info, hipS
     a.fail_list = w->fail_list;
     a.succ = nullptr;
     a.dbg = nullptr;
-    unsigned long long *d_dbg = nullptr;
+    DevBuf<unsigned long long> d_dbg;
 #ifdef BRX_LANE_TIMING
     if (!walk && env_u32("BRX_LANE_TIMING", 0u) != 0u) { // (debug: when do the waves of the automaton start and end?)
-        BRX_HIP(hipMalloc((void **)&d_dbg, (1 + 3 * 16384) * 8));
+        BRX_TRY(d_dbg.reserve(1 + 3 * 16384, 0, "lane timing"));
         BRX_HIP(hipMemsetAsync(d_dbg, 0, (1 + 3 * 16384) * 8, s));
         a.dbg = d_dbg;
     }
@@ -2358,14 +2314,10 @@ int lane_pass(brx_chain *ch, const PassParams &p, const LanePassInfo &info, hipS
         std::lock_guard<std::mutex> g(set->idx_mu);
         const uint64_t n_lines = 1ull << (32u - p.idx.line_shift);
         if (!set->d_succ || set->succ_lines != n_lines || set->succ_gen != set->idx_gen) {
-            if (set->d_succ && set->succ_lines != n_lines) {
-                (void)hipFree(set->d_succ);
-                set->d_succ = nullptr;
-            }
-            if (!set->d_succ) {
-                BRX_TRY(grow_dev((void **)&set->d_succ, n_lines * 8ull));
-                set->succ_lines = n_lines;
-            }
+            if (set->succ_lines != n_lines)
+                set->d_succ.reset();
+            BRX_TRY(set->d_succ.reserve(n_lines, 0, "successor table"));
+            set->succ_lines = n_lines;
             KernelTimer t("succ_build", s);
             const uint64_t blocks = (n_lines + 255ull) / 256ull;
             succ_build_kernel<<<(uint32_t)(blocks < 65536ull ? blocks : 65536ull), 256, 0, s>>>(p, n_lines, set->d_succ);
@@ -2446,7 +2398,6 @@ int lane_pass(brx_chain *ch, const PassParams &p, const LanePassInfo &info, hipS
         std::vector<unsigned long long> h(1 + 3 * 16384);
         BRX_HIP(hipMemcpyAsync(h.data(), d_dbg, h.size() * 8, hipMemcpyDeviceToHost, s));
         BRX_HIP(hipStreamSynchronize(s));
-        (void)hipFree(d_dbg);
         const size_t nw = (size_t)(h[0] < 16384ull ? h[0] : 16384ull);
         if (nw) {
             std::vector<double> st(nw), en(nw), it(nw), lr(nw);

@@ -1808,11 +1808,16 @@ __global__ void add_counts_kernel(const uint64_t *__restrict__ off, uint32_t B1,
     }
 }
 
+// A batch either owns its two arrays (own_keys / own_l1off hold them, d_keys / d_l1off point into them) or borrows them
+// from the caller (segments received from other ranks: the owners stay empty).
 struct PartBatch {
     uint32_t *d_keys = nullptr;  // keys after level 1, grouped by digit 1
-    uint64_t cap = 0, n = 0;
+    uint64_t n = 0;
     uint64_t *d_l1off = nullptr; // B1 + 1
-    bool borrowed = false;       // memory owned by the caller (segments received from other ranks)
+    DevBuf<uint32_t> own_keys;
+    DevBuf<uint64_t> own_l1off;
+    bool borrowed() const { return !own_keys; }
+    uint64_t cap() const { return own_keys.cap(); }
 };
 
 } // namespace
@@ -1825,54 +1830,30 @@ struct PartState {
     bool use_wide = false; // which of the two the levels >= 2 of the finish in progress follow
     std::vector<PartBatch> batches, spare;
     // generic workspace
-    uint32_t *d_ntiles = nullptr;      // per parent
-    uint64_t ntiles_cap = 0;
-    uint64_t *d_item_off = nullptr;    // per parent + 1
-    uint64_t item_off_cap = 0;
-    LnItem *d_items = nullptr;         // per work item
-    uint64_t items_cap = 0;
-    uint32_t *d_matrix = nullptr;      // per-tile digit counts
-    uint64_t matrix_cap = 0;
-    uint64_t *d_pos = nullptr;         // levels >= 2: exclusive scan of the matrix; level 1: [n_ranges + 1][B] range starts
-    uint64_t pos_cap = 0;
-    uint64_t *d_scan_tmp = nullptr;
-    uint64_t scan_tmp_cap = 0;
-    unsigned long long *d_scalars = nullptr; // [0] n_items, [1] total keys of the last scan, [2..3] hf_sample_kernel
-    uint64_t *d_coff[MAX_LEVELS] = {nullptr, nullptr, nullptr, nullptr}; // child offsets (nchild + 1)
-    uint32_t *d_keys_mid = nullptr;    // outputs of the middle levels (ping-pong when there are 4 levels)
-    uint64_t keys_mid_cap = 0;
-    uint32_t *d_keys_mid2 = nullptr;
-    uint64_t keys_mid2_cap = 0;
-    uint16_t *d_keys_fin = nullptr;    // last level output
-    uint64_t keys_fin_cap = 0;
-    uint32_t *d_merged = nullptr;      // all batches merged per level-1 bucket (only when > 1 batch)
-    uint64_t merged_cap = 0;
-    uint64_t *d_l1off_all = nullptr;
-    uint32_t *d_cnts = nullptr;        // B1 running counts (merge)
-    uint64_t *d_shift = nullptr;       // B1 (merge)
+    DevBuf<uint32_t> d_ntiles;    // per parent
+    DevBuf<uint64_t> d_item_off;  // per parent + 1
+    DevBuf<LnItem> d_items;       // per work item
+    DevBuf<uint32_t> d_matrix;    // per-tile digit counts
+    DevBuf<uint64_t> d_pos;       // levels >= 2: exclusive scan of the matrix; level 1: [n_ranges + 1][B] range starts
+    DevBuf<uint64_t> d_scan_tmp;
+    DevBuf<unsigned long long> d_scalars; // [0] n_items, [1] total keys of the last scan, [2..3] hf_sample_kernel
+    DevBuf<uint64_t> d_coff[MAX_LEVELS];  // child offsets (nchild + 1)
+    DevBuf<uint32_t> d_keys_mid, d_keys_mid2; // outputs of the middle levels (ping-pong when there are 4 levels)
+    DevBuf<uint16_t> d_keys_fin;  // last level output
+    DevBuf<uint32_t> d_merged;    // all batches merged per level-1 bucket (only when > 1 batch)
+    DevBuf<uint64_t> d_l1off_all;
+    DevBuf<uint32_t> d_cnts;      // B1 running counts (merge)
+    DevBuf<uint64_t> d_shift;     // B1 (merge)
     // count view for lookups (part_lookup_prepare): d_keys_fin rewritten bucket by bucket, d_coff[nlev - 1] delimits them
     std::atomic<bool> view_valid{false}; // (read without the counter's lock by the entries' first check) cleared by everything that touches the batches or the workspace above
     bool view_empty = false;           // ... of a counter without keys: answers 0 everywhere, nothing to read
-    uint8_t *d_view_cnt = nullptr;     // min(255, count) beside every key of d_keys_fin
-    uint64_t view_cnt_cap = 0;
+    DevBuf<uint8_t> d_view_cnt;        // min(255, count) beside every key of d_keys_fin
 };
 
-static int ensure_dev(void **p, uint64_t *cap, uint64_t need_bytes)
+// the partition workspace is sized in bytes, with a sixteenth and 256 B to spare
+template <typename T> static int ws_reserve(DevBuf<T> &b, uint64_t need_bytes)
 {
-    if (*p && need_bytes <= *cap)
-        return BRX_OK;
-    if (*p)
-        (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const uint64_t want = need_bytes + need_bytes / 16 + 256;
-    hipError_t e = hipMalloc(p, want);
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%llu B partition workspace): %s", (unsigned long long)want, hipGetErrorString(e));
-        return BRX_ERR_NOMEM;
-    }
-    *cap = want;
-    return BRX_OK;
+    return b.reserve_bytes(need_bytes, need_bytes / 16 + 256, "partition workspace");
 }
 
 // presence-only insertion of a batch (see flat_insert_kernel); table == nullptr: into `bits`
@@ -1970,47 +1951,20 @@ int part_begin(brx_counter *c)
             w.nchild[3] = w.nchild[2] << b3;
         }
     }
-    hipError_t e = hipMalloc((void **)&st->d_scalars, 32);
-    for (int l = 0; l < pl.nlev && e == hipSuccess; l++) {
+    const char *what = "partition state";
+    BRX_TRY(st->d_scalars.reserve(4, 0, what));
+    for (int l = 0; l < pl.nlev; l++) {
         const uint64_t nc = pl.nchild[l] > st->pl_wide.nchild[l] ? pl.nchild[l] : st->pl_wide.nchild[l];
-        e = hipMalloc((void **)&st->d_coff[l], (nc + 1) * 8);
+        BRX_TRY(st->d_coff[l].reserve(nc + 1, 0, what));
     }
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&st->d_l1off_all, (pl.nchild[0] + 1) * 8);
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&st->d_cnts, (pl.nchild[0] + 1) * 4);
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&st->d_shift, (pl.nchild[0] + 1) * 8);
-    if (e != hipSuccess) {
-        set_error("partition state alloc: %s", hipGetErrorString(e));
-        return BRX_ERR_NOMEM;
-    }
-    return BRX_OK;
+    BRX_TRY(st->d_l1off_all.reserve(pl.nchild[0] + 1, 0, what));
+    BRX_TRY(st->d_cnts.reserve(pl.nchild[0] + 1, 0, what));
+    return st->d_shift.reserve(pl.nchild[0] + 1, 0, what);
 }
 
 void part_free(brx_counter *c)
 {
-    PartState *st = c->part;
-    if (!st)
-        return;
-    for (auto *v : {&st->batches, &st->spare})
-        for (auto &b : *v) {
-            if (b.borrowed)
-                continue;
-            if (b.d_keys)
-                (void)hipFree(b.d_keys);
-            if (b.d_l1off)
-                (void)hipFree(b.d_l1off);
-        }
-    for (void *p : {(void *)st->d_ntiles, (void *)st->d_item_off, (void *)st->d_items, (void *)st->d_matrix,
-                    (void *)st->d_pos, (void *)st->d_scan_tmp, (void *)st->d_scalars, (void *)st->d_coff[0],
-                    (void *)st->d_coff[1], (void *)st->d_coff[2], (void *)st->d_coff[3], (void *)st->d_keys_mid,
-                    (void *)st->d_keys_mid2, (void *)st->d_keys_fin,
-                    (void *)st->d_merged, (void *)st->d_l1off_all, (void *)st->d_cnts, (void *)st->d_shift,
-                    (void *)st->d_view_cnt})
-        if (p)
-            (void)hipFree(p);
-    delete st;
+    delete c->part;
     c->part = nullptr;
 }
 
@@ -2019,8 +1973,8 @@ int part_reset(brx_counter *c)
     PartState *st = c->part;
     st->view_valid = false;
     for (auto &b : st->batches)
-        if (!b.borrowed)
-            st->spare.push_back(b);
+        if (!b.borrowed())
+            st->spare.push_back(std::move(b));
     st->batches.clear();
     return BRX_OK;
 }
@@ -2037,7 +1991,7 @@ int part_l1_view(brx_counter *c, void **d_keys, void **d_l1off, uint32_t *n_buck
         *n_keys = 0;
         return BRX_OK;
     }
-    if (st->batches.size() != 1 || st->batches[0].borrowed) {
+    if (st->batches.size() != 1 || st->batches[0].borrowed()) {
         set_error("l1_view needs exactly one locally counted batch (have %zu)", st->batches.size());
         return BRX_ERR_ARG;
     }
@@ -2059,9 +2013,7 @@ int part_add_partitioned(brx_counter *c, const uint32_t *d_keys, const uint64_t 
     b.d_keys = const_cast<uint32_t *>(d_keys);
     b.d_l1off = const_cast<uint64_t *>(d_l1off);
     b.n = n_keys;
-    b.cap = n_keys;
-    b.borrowed = true;
-    st->batches.push_back(b);
+    st->batches.push_back(std::move(b));
     return BRX_OK;
 }
 
@@ -2069,16 +2021,9 @@ int part_add_partitioned(brx_counter *c, const uint32_t *d_keys, const uint64_t 
 // level 1: one per range and digit)
 static int ensure_matrix(PartState *st, uint64_t n_entries, uint64_t n_pos)
 {
-    uint64_t capb = st->matrix_cap;
-    BRX_TRY(ensure_dev((void **)&st->d_matrix, &capb, (n_entries + 1) * 4));
-    st->matrix_cap = capb;
-    capb = st->pos_cap;
-    BRX_TRY(ensure_dev((void **)&st->d_pos, &capb, (n_pos + 2) * 8));
-    st->pos_cap = capb;
-    capb = st->scan_tmp_cap;
-    BRX_TRY(ensure_dev((void **)&st->d_scan_tmp, &capb, scan_tmp_bytes((uint32_t)n_entries) + 64));
-    st->scan_tmp_cap = capb;
-    return BRX_OK;
+    BRX_TRY(ws_reserve(st->d_matrix, (n_entries + 1) * 4));
+    BRX_TRY(ws_reserve(st->d_pos, (n_pos + 2) * 8));
+    return ws_reserve(st->d_scan_tmp, scan_tmp_bytes((uint32_t)n_entries) + 64);
 }
 
 static size_t scatter_lds_bytes(uint32_t tile, int bits)
@@ -2104,16 +2049,16 @@ int part_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_off
     const uint64_t max_keys = total_bases; // upper bound of the number of k-mers of this batch
     PartBatch b;
     for (size_t i = 0; i < st->spare.size(); i++)
-        if (st->spare[i].cap >= max_keys) {
-            b = st->spare[i];
+        if (st->spare[i].cap() >= max_keys) {
+            b = std::move(st->spare[i]);
             st->spare.erase(st->spare.begin() + (long)i);
             break;
         }
     if (!b.d_keys) {
-        uint64_t capb = 0;
-        BRX_TRY(ensure_dev((void **)&b.d_keys, &capb, (max_keys + 1) * 4));
-        b.cap = capb / 4;
-        BRX_HIP(hipMalloc((void **)&b.d_l1off, (pl.nchild[0] + 1) * 8));
+        BRX_TRY(ws_reserve(b.own_keys, (max_keys + 1) * 4));
+        BRX_TRY(b.own_l1off.reserve(pl.nchild[0] + 1, 0, "partition offsets"));
+        b.d_keys = b.own_keys;
+        b.d_l1off = b.own_l1off;
     }
     const uint32_t B = 1u << pl.bits[0];
     const uint64_t n_items64 = (total_bases + L1_TILE - 1) / L1_TILE;
@@ -2149,7 +2094,7 @@ int part_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_off
     a.rsum = st->d_pos;
     a.coff = b.d_l1off;
     a.keys_out = b.d_keys;
-    a.out_cap = b.cap;
+    a.out_cap = b.cap();
     {
         KernelTimer t("part_l1_hist", s);
         l1_hist_kernel<<<n_ranges, 256, (size_t)B * 4, s>>>(a);
@@ -2174,7 +2119,7 @@ int part_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_off
     BRX_HIP(hipMemcpyAsync(&tot, st->d_scalars + 1, 8, hipMemcpyDeviceToHost, s));
     BRX_HIP(hipStreamSynchronize(s));
     b.n = tot;
-    st->batches.push_back(b);
+    st->batches.push_back(std::move(b));
     return BRX_OK;
 }
 
@@ -2198,15 +2143,9 @@ static int run_level(PartState *st, int l, const uint32_t *keys_in, const uint64
         return BRX_ERR_UNSUPPORTED;
     }
     {
-        uint64_t capb = st->ntiles_cap;
-        BRX_TRY(ensure_dev((void **)&st->d_ntiles, &capb, (n_parents + 1) * 4));
-        st->ntiles_cap = capb;
-        capb = st->item_off_cap;
-        BRX_TRY(ensure_dev((void **)&st->d_item_off, &capb, (n_parents + 2) * 8));
-        st->item_off_cap = capb;
-        capb = st->items_cap;
-        BRX_TRY(ensure_dev((void **)&st->d_items, &capb, (ub_items + 1) * sizeof(LnItem)));
-        st->items_cap = capb;
+        BRX_TRY(ws_reserve(st->d_ntiles, (n_parents + 1) * 4));
+        BRX_TRY(ws_reserve(st->d_item_off, (n_parents + 2) * 8));
+        BRX_TRY(ws_reserve(st->d_items, (ub_items + 1) * sizeof(LnItem)));
     }
     BRX_TRY(ensure_matrix(st, n_entries > n_parents ? n_entries : n_parents, n_entries > n_parents ? n_entries : n_parents));
     tiles_from_offsets_kernel<<<(unsigned)((n_parents + 255) / 256), 256, 0, s>>>(poff, n_parents, tile, st->d_ntiles);
@@ -2292,8 +2231,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
         if (no_set)
             return BRX_OK; // nothing counted: bins 1..255 stay 0
         if (dst->sparse) {
-            if (!dst->d_keylist_n)
-                BRX_HIP(hipMalloc((void **)&dst->d_keylist_n, 8));
+            BRX_TRY(dst->d_keylist_n.reserve(1, 0, "key list counter"));
             BRX_HIP(hipMemsetAsync(dst->d_keylist_n, 0, 8, s));
             dst->keylist_valid = true; // the empty list
         } else {
@@ -2305,9 +2243,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
         keys1 = st->batches[0].d_keys;
         l1off = st->batches[0].d_l1off;
     } else {
-        uint64_t capb = st->merged_cap;
-        BRX_TRY(ensure_dev((void **)&st->d_merged, &capb, (total + 1) * 4));
-        st->merged_cap = capb;
+        BRX_TRY(ws_reserve(st->d_merged, (total + 1) * 4));
         BRX_TRY(ensure_matrix(st, B1 + 1, B1 + 1));
         BRX_HIP(hipMemsetAsync(st->d_cnts, 0, (uint64_t)B1 * 4, s));
         for (auto &b : st->batches)
@@ -2323,11 +2259,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
         l1off = st->d_l1off_all;
     }
 
-    {
-        uint64_t capb = st->keys_fin_cap;
-        BRX_TRY(ensure_dev((void **)&st->d_keys_fin, &capb, (total + 64) * 2));
-        st->keys_fin_cap = capb;
-    }
+    BRX_TRY(ws_reserve(st->d_keys_fin, (total + 64) * 2));
     // solid-key list for the probe index: a solid hash was seen more than `abundance` times, so there are at
     // most total / (abundance + 1) of them; real data is far below that, and a list that turns out too short
     // is simply not used (the index is then built from the bit vector)
@@ -2339,31 +2271,17 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
         // (a set without bits has nothing but this list: it gets the exact bound)
         const uint64_t div = (dst->sparse || lazy) ? abundance + 1u : (abundance + 1u > 8u ? abundance + 1u : 8u);
         const uint64_t want = total / div + (1ull << 20);
-        if (dst->keylist_cap < want || !dst->d_keylist) {
-            if (dst->d_keylist)
-                (void)hipFree(dst->d_keylist);
-            dst->d_keylist = nullptr;
-            dst->keylist_cap = 0;
-            BRX_HIP(hipMalloc((void **)&dst->d_keylist, want * 8));
-            dst->keylist_cap = want;
-        }
-        if (!dst->d_keylist_n)
-            BRX_HIP(hipMalloc((void **)&dst->d_keylist_n, 8));
+        BRX_TRY(dst->d_keylist.reserve(want, 0, "solid key list"));
+        BRX_TRY(dst->d_keylist_n.reserve(1, 0, "key list counter"));
         BRX_HIP(hipMemsetAsync(dst->d_keylist_n, 0, 8, s));
     }
     // levels 2 .. nlev: u32 keys through one or two middle buffers, u16 out of the last level
     static const char *hist_tag[MAX_LEVELS] = {"part_l1_hist", "part_l2_hist", "part_l3_hist", "part_l4_hist"};
     static const char *scat_tag[MAX_LEVELS] = {"part_l1_scatter", "part_l2_scatter", "part_l3_scatter", "part_l4_scatter"};
-    if (pl.nlev >= 3) {
-        uint64_t capb = st->keys_mid_cap;
-        BRX_TRY(ensure_dev((void **)&st->d_keys_mid, &capb, (total + 64) * 4));
-        st->keys_mid_cap = capb;
-    }
-    if (pl.nlev >= 4) {
-        uint64_t capb = st->keys_mid2_cap;
-        BRX_TRY(ensure_dev((void **)&st->d_keys_mid2, &capb, (total + 64) * 4));
-        st->keys_mid2_cap = capb;
-    }
+    if (pl.nlev >= 3)
+        BRX_TRY(ws_reserve(st->d_keys_mid, (total + 64) * 4));
+    if (pl.nlev >= 4)
+        BRX_TRY(ws_reserve(st->d_keys_mid2, (total + 64) * 4));
     const uint32_t *kin = keys1;
     const uint64_t *poff = l1off;
     // no slices to write (lazy / sparse): stop one level early and hash-count the coarser buckets, if they are small
@@ -2410,7 +2328,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
             const size_t lds = ((size_t)4 << log_t) + hf_ebuf(1024) * 8 + 16;
             BRX_HIP(hipFuncSetAttribute((const void *)hash_final_kernel<1024, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             const int grid = (int)(nb_hf < 256ull * 4ull ? nb_hf : 256ull * 4ull);
-            hash_final_kernel<1024, 1024><<<grid, 1024, lds, s>>>(kin, poff, nb_hf, R_hf, abundance, log_t, dst->d_keylist, dst->keylist_cap,
+            hash_final_kernel<1024, 1024><<<grid, 1024, lds, s>>>(kin, poff, nb_hf, R_hf, abundance, log_t, dst->d_keylist, dst->d_keylist.cap(),
                                                           dst->d_keylist_n, dup, min_lt, ratio_forced);
         } else { // one wave per bucket; at most 256..2048 table entries, about 4x the average bucket (each bucket then uses
                  // 2.5 slots per distinct key expected: clearing and scanning cost T / 256 LDS accesses per lane).  Sizing
@@ -2425,7 +2343,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
             const size_t lds = 4 * (((size_t)4 << log_t) + hf_ebuf(64) * 8 + 16);
             const uint64_t want = (nb_hf + 3) / 4;
             const int grid = (int)(want < 256ull * 16ull ? want : 256ull * 16ull);
-            hash_final_kernel<64, 256><<<grid, 256, lds, s>>>(kin, poff, nb_hf, R_hf, abundance, log_t, dst->d_keylist, dst->keylist_cap,
+            hash_final_kernel<64, 256><<<grid, 256, lds, s>>>(kin, poff, nb_hf, R_hf, abundance, log_t, dst->d_keylist, dst->d_keylist.cap(),
                                                          dst->d_keylist_n, dup, min_lt, ratio_forced);
         }
         BRX_HIP(hipGetLastError());
@@ -2436,9 +2354,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
     }
     const uint64_t *fin_off = st->d_coff[pl.nlev - 1];
     if (view) {
-        uint64_t capb = st->view_cnt_cap;
-        BRX_TRY(ensure_dev((void **)&st->d_view_cnt, &capb, total + 64));
-        st->view_cnt_cap = capb;
+        BRX_TRY(ws_reserve(st->d_view_cnt, total + 64));
         {
             KernelTimer t("part_view", s);
             const uint64_t nb = pl.nchild[pl.nlev - 1];
@@ -2468,10 +2384,10 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
         const int grid = (int)((want_waves + P3_WAVES - 1) / P3_WAVES);
         if (dst->sparse || lazy)
             final_count_kernel<true, false><<<grid, 64 * P3_WAVES, 0, s>>>(st->d_keys_fin, fin_off, nb, abundance, nullptr,
-                                                                          dst->d_keylist, dst->keylist_cap, dst->d_keylist_n);
+                                                                          dst->d_keylist, dst->d_keylist.cap(), dst->d_keylist_n);
         else if (emit)
             final_count_kernel<true, true><<<grid, 64 * P3_WAVES, 0, s>>>(st->d_keys_fin, fin_off, nb, abundance, dst->d_bits,
-                                                                         dst->d_keylist, dst->keylist_cap, dst->d_keylist_n);
+                                                                         dst->d_keylist, dst->d_keylist.cap(), dst->d_keylist_n);
         else
             final_count_kernel<false, true><<<grid, 64 * P3_WAVES, 0, s>>>(st->d_keys_fin, fin_off, nb, abundance, dst->d_bits,
                                                                           nullptr, 0, nullptr);
@@ -2518,10 +2434,7 @@ void part_lookup_drop(brx_counter *c)
 {
     PartState *st = c->part;
     st->view_valid = false;
-    if (st->d_view_cnt)
-        (void)hipFree(st->d_view_cnt);
-    st->d_view_cnt = nullptr;
-    st->view_cnt_cap = 0;
+    st->d_view_cnt.reset();
 }
 
 bool part_lookup_ready(const brx_counter *c) { return c->part && c->part->view_valid; }
@@ -2532,9 +2445,9 @@ bool part_lookup_view(const brx_counter *c, const uint16_t **keys, const uint8_t
     const PartState *st = c->part;
     if (!st || !st->view_valid)
         return false;
-    *keys = st->view_empty ? nullptr : st->d_keys_fin;
-    *counts = st->view_empty ? nullptr : st->d_view_cnt;
-    *off = st->view_empty ? nullptr : st->d_coff[st->pl.nlev - 1];
+    *keys = st->view_empty ? nullptr : st->d_keys_fin.get();
+    *counts = st->view_empty ? nullptr : st->d_view_cnt.get();
+    *off = st->view_empty ? nullptr : st->d_coff[st->pl.nlev - 1].get();
     return true;
 }
 

@@ -540,107 +540,30 @@ struct OutOpts {
 // device-side buffers of one GPU worker
 struct DevBufs {
     // output forms: statistics in / out (2 n), the split form of the batch and its piece table
-    brx_cover_stats_t *d_cover_st = nullptr;
-    uint8_t *d_split = nullptr;
-    uint64_t *d_split_off = nullptr;
-    uint32_t *d_piece_read = nullptr;
-    uint64_t cover_st_cap = 0, split_cap = 0, piece_cap = 0;
-    template <typename T>
-    static int grow(T **p, uint64_t *cap, uint64_t need)
-    {
-        if (need <= *cap && *p)
-            return BRX_OK;
-        if (*p)
-            (void)hipFree(*p);
-        *p = nullptr;
-        *cap = need + need / 8 + 64;
-        BRX_HIP(hipMalloc((void **)p, *cap * sizeof(T)));
-        return BRX_OK;
-    }
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    uint64_t *d_off = nullptr, *d_out_off = nullptr;
-    uint64_t in_cap = 0, out_cap = 0, off_cap = 0;
+    brx::DevBuf<brx_cover_stats_t> d_cover_st;
+    brx::DevBuf<uint8_t> d_split;
+    brx::DevBuf<uint64_t> d_split_off;
+    brx::DevBuf<uint32_t> d_piece_read;
+    brx::DevBuf<uint8_t> d_in, d_out;
+    brx::DevBuf<uint64_t> d_off, d_out_off;
     // the FASTA text of the batch (format_kernel): definitions, their ends, record starts, the text
-    uint8_t *d_defs = nullptr, *d_text = nullptr;
-    uint32_t *d_def_end = nullptr;
-    uint64_t *d_text_off = nullptr;
-    uint64_t defs_cap = 0, text_cap = 0, tmeta_cap = 0;
+    brx::DevBuf<uint8_t> d_defs, d_text;
+    brx::DevBuf<uint32_t> d_def_end;
+    brx::DevBuf<uint64_t> d_text_off;
     int ensure_text_meta(uint64_t defs_bytes, uint32_t n)
     {
-        if (defs_bytes + 1 > defs_cap) {
-            if (d_defs)
-                (void)hipFree(d_defs);
-            d_defs = nullptr;
-            defs_cap = defs_bytes + defs_bytes / 4 + 4096;
-            BRX_HIP(hipMalloc((void **)&d_defs, defs_cap));
-        }
-        if ((uint64_t)n + 1 > tmeta_cap) {
-            if (d_def_end)
-                (void)hipFree(d_def_end);
-            if (d_text_off)
-                (void)hipFree(d_text_off);
-            d_def_end = nullptr;
-            d_text_off = nullptr;
-            tmeta_cap = (uint64_t)n + n / 8 + 64;
-            BRX_HIP(hipMalloc((void **)&d_def_end, tmeta_cap * 4));
-            BRX_HIP(hipMalloc((void **)&d_text_off, tmeta_cap * 8));
-        }
-        return BRX_OK;
+        BRX_TRY(d_defs.reserve(defs_bytes + 1, defs_bytes / 4 + 4095, "definition lines"));
+        BRX_TRY(d_def_end.reserve((uint64_t)n + 1, n / 8 + 63, "definition ends"));
+        return d_text_off.reserve((uint64_t)n + 1, n / 8 + 63, "record starts");
     }
-    int ensure_text(uint64_t bytes)
-    {
-        if (bytes + 64 > text_cap) {
-            if (d_text)
-                (void)hipFree(d_text);
-            d_text = nullptr;
-            text_cap = bytes + bytes / 8 + 4096;
-            BRX_HIP(hipMalloc((void **)&d_text, text_cap));
-        }
-        return BRX_OK;
-    }
+    int ensure_text(uint64_t bytes) { return d_text.reserve(bytes + 64, bytes / 8 + 4032, "FASTA text"); }
     int ensure(uint64_t bases, uint32_t n)
     {
-        if (bases + 64 > in_cap) {
-            if (d_in)
-                (void)hipFree(d_in);
-            d_in = nullptr;
-            in_cap = bases + bases / 8 + 4096;
-            BRX_HIP(hipMalloc((void **)&d_in, in_cap));
-        }
+        BRX_TRY(d_in.reserve(bases + 64, bases / 8 + 4032, "batch"));
         const uint64_t want_out = bases + bases / 16 + 4096;
-        if (want_out > out_cap) {
-            if (d_out)
-                (void)hipFree(d_out);
-            d_out = nullptr;
-            out_cap = want_out + want_out / 8;
-            BRX_HIP(hipMalloc((void **)&d_out, out_cap));
-        }
-        if ((uint64_t)n + 1 > off_cap) {
-            if (d_off)
-                (void)hipFree(d_off);
-            if (d_out_off)
-                (void)hipFree(d_out_off);
-            d_off = d_out_off = nullptr;
-            off_cap = (uint64_t)n + n / 8 + 64;
-            BRX_HIP(hipMalloc((void **)&d_off, off_cap * 8));
-            BRX_HIP(hipMalloc((void **)&d_out_off, off_cap * 8));
-        }
-        return BRX_OK;
-    }
-    ~DevBufs()
-    {
-        if (d_in)
-            (void)hipFree(d_in);
-        if (d_out)
-            (void)hipFree(d_out);
-        if (d_off)
-            (void)hipFree(d_off);
-        if (d_out_off)
-            (void)hipFree(d_out_off);
-        for (void *q : {(void *)d_defs, (void *)d_text, (void *)d_def_end, (void *)d_text_off, (void *)d_cover_st, (void *)d_split,
-                        (void *)d_split_off, (void *)d_piece_read})
-            if (q)
-                (void)hipFree(q);
+        BRX_TRY(d_out.reserve(want_out, want_out / 8, "corrected batch"));
+        BRX_TRY(d_off.reserve((uint64_t)n + 1, n / 8 + 63, "offsets"));
+        return d_out_off.reserve((uint64_t)n + 1, n / 8 + 63, "corrected offsets");
     }
 };
 
@@ -652,7 +575,7 @@ int cover_one_batch(const brx_set_t *set, const OutOpts &oo, DevBufs &dv, hipStr
 {
     const uint32_t n = b.n();
     if (oo.stats) {
-        BRX_TRY(DevBufs::grow(&dv.d_cover_st, &dv.cover_st_cap, 2ull * n));
+        BRX_TRY(dv.d_cover_st.reserve(2ull * n, 2ull * n / 8 + 64, "cover statistics"));
         BRX_TRY(brx_set_cover_batch_device(set, dv.d_in, dv.d_off, n, b.total, nullptr, nullptr, dv.d_cover_st, s));
     }
     if (oo.stats || oo.mode == BRX_OUT_MASK)
@@ -691,10 +614,9 @@ int cover_one_batch(const brx_set_t *set, const OutOpts &oo, DevBufs &dv, hipStr
         set_error("split: batch too large");
         return BRX_ERR_ARG;
     }
-    BRX_TRY(DevBufs::grow(&dv.d_split, &dv.split_cap, out_total + 64));
-    uint64_t cap2 = dv.piece_cap;
-    BRX_TRY(DevBufs::grow(&dv.d_split_off, &cap2, piece_cap + 1));
-    BRX_TRY(DevBufs::grow(&dv.d_piece_read, &dv.piece_cap, piece_cap + 1));
+    BRX_TRY(dv.d_split.reserve(out_total + 64, (out_total + 64) / 8 + 64, "split batch"));
+    BRX_TRY(dv.d_split_off.reserve(piece_cap + 1, (piece_cap + 1) / 8 + 64, "piece offsets"));
+    BRX_TRY(dv.d_piece_read.reserve(piece_cap + 1, (piece_cap + 1) / 8 + 64, "piece table"));
     uint32_t np = 0;
     uint64_t bytes = 0;
     BRX_TRY(brx_set_cover_split_batch_device(set, dv.d_out, dv.d_out_off, n, out_total, oo.min_len, dv.d_split, out_total, dv.d_split_off,
@@ -754,14 +676,11 @@ int correct_one_batch(brx_chain_t *chain, DevBufs &dv, hipStream_t s, Batch &b, 
         BRX_HIP(hipStreamSynchronize(s));
     const double t2 = now_s();
     uint64_t out_total = 0;
-    int st = brx_chain_correct_batch_device(chain, dv.d_in, dv.d_off, n, b.total, dv.d_out, dv.out_cap, dv.d_out_off,
+    int st = brx_chain_correct_batch_device(chain, dv.d_in, dv.d_off, n, b.total, dv.d_out, dv.d_out.cap(), dv.d_out_off,
                                             &out_total, s);
-    if (st == BRX_ERR_OVERFLOW && out_total > dv.out_cap) { // corrections grew the batch beyond the estimate
-        (void)hipFree(dv.d_out);
-        dv.d_out = nullptr;
-        dv.out_cap = out_total + out_total / 16 + 4096;
-        BRX_HIP(hipMalloc((void **)&dv.d_out, dv.out_cap));
-        st = brx_chain_correct_batch_device(chain, dv.d_in, dv.d_off, n, b.total, dv.d_out, dv.out_cap, dv.d_out_off,
+    if (st == BRX_ERR_OVERFLOW && out_total > dv.d_out.cap()) { // corrections grew the batch beyond the estimate
+        BRX_TRY(dv.d_out.reserve(out_total + out_total / 16 + 4096, 0, "corrected batch"));
+        st = brx_chain_correct_batch_device(chain, dv.d_in, dv.d_off, n, b.total, dv.d_out, dv.d_out.cap(), dv.d_out_off,
                                             &out_total, s);
     }
     BRX_TRY(st);

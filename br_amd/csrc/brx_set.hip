@@ -299,11 +299,10 @@ int alloc_set(int k, int device, bool zero, brx_set **out, bool sparse = false)
     s->k = k;
     s->device = device;
     s->nwords = set_nwords(k);
-    s->d_bits = nullptr;
     s->sparse = sparse || sparse_k(k);
     if (s->sparse) { // no bit vector: an empty key list is the empty set
         s->nwords = 0;
-        hipError_t e = hipMalloc((void **)&s->d_keylist_n, 8);
+        hipError_t e = s->d_keylist_n.reserve(1, 0, "key list counter") == BRX_OK ? hipSuccess : hipErrorOutOfMemory;
         if (e == hipSuccess)
             e = zero_now(s->d_keylist_n, 8);
         if (e != hipSuccess) {
@@ -315,17 +314,14 @@ int alloc_set(int k, int device, bool zero, brx_set **out, bool sparse = false)
         *out = s;
         return BRX_OK;
     }
-    hipError_t e = hipMalloc((void **)&s->d_bits, s->nwords * 4);
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%llu B bitset, k=%d): %s", (unsigned long long)(s->nwords * 4), k, hipGetErrorString(e));
+    if (s->d_bits.reserve(s->nwords, 0, "bitset") != BRX_OK) {
         delete s;
         return BRX_ERR_NOMEM;
     }
     if (zero) {
-        e = zero_now(s->d_bits, s->nwords * 4); // (done on return: the first insert may come on any stream)
+        const hipError_t e = zero_now(s->d_bits, s->nwords * 4); // (done on return: the first insert may come on any stream)
         if (e != hipSuccess) {
             set_error("hipMemset bitset: %s", hipGetErrorString(e));
-            (void)hipFree(s->d_bits);
             delete s;
             return BRX_ERR_HIP;
         }
@@ -371,8 +367,8 @@ int tab_info(brx_counter *c, uint64_t *info4, hipStream_t s);
 // a set of this k with nothing written yet (brx_set_load_fd fills it from a key list)
 int set_alloc_unwritten(int k, int device, brx_set **out) { return alloc_set(k, device, false, out); }
 // used by the correction chain and the host-pointer entry points
-int upload_batch(const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, uint8_t **d_bases, uint64_t *bases_cap,
-                 uint64_t **d_off, uint64_t *off_cap, uint64_t *total, hipStream_t stream)
+int upload_batch(const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, DevBuf<uint8_t> &d_bases, DevBuf<uint64_t> &d_off,
+                 uint64_t *total, hipStream_t stream)
 {
     const uint64_t base0 = offsets[0];
     const uint64_t tot = offsets[n_reads] - base0;
@@ -381,32 +377,18 @@ int upload_batch(const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads
             set_error("offsets not monotone at read %u", r);
             return BRX_ERR_ARG;
         }
-    if (tot + 64 > *bases_cap) {
-        if (*d_bases)
-            (void)hipFree(*d_bases);
-        *d_bases = nullptr;
-        *bases_cap = 0;
-        BRX_HIP(hipMalloc((void **)d_bases, tot + 64));
-        *bases_cap = tot + 64;
-    }
-    if ((uint64_t)n_reads + 1 > *off_cap) {
-        if (*d_off)
-            (void)hipFree(*d_off);
-        *d_off = nullptr;
-        *off_cap = 0;
-        BRX_HIP(hipMalloc((void **)d_off, ((uint64_t)n_reads + 1) * 8));
-        *off_cap = (uint64_t)n_reads + 1;
-    }
+    BRX_TRY(d_bases.reserve(tot + 64, 0, "batch"));
+    BRX_TRY(d_off.reserve((uint64_t)n_reads + 1, 0, "offsets"));
     if (tot)
-        BRX_HIP(hipMemcpyAsync(*d_bases, bases + base0, tot, hipMemcpyHostToDevice, stream));
+        BRX_HIP(hipMemcpyAsync(d_bases, bases + base0, tot, hipMemcpyHostToDevice, stream));
     if (base0 == 0) {
-        BRX_HIP(hipMemcpyAsync(*d_off, offsets, ((uint64_t)n_reads + 1) * 8, hipMemcpyHostToDevice, stream));
+        BRX_HIP(hipMemcpyAsync(d_off, offsets, ((uint64_t)n_reads + 1) * 8, hipMemcpyHostToDevice, stream));
         BRX_HIP(hipStreamSynchronize(stream));
     } else {
         std::vector<uint64_t> rel((size_t)n_reads + 1);
         for (uint32_t r = 0; r <= n_reads; r++)
             rel[r] = offsets[r] - base0;
-        BRX_HIP(hipMemcpyAsync(*d_off, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, stream));
+        BRX_HIP(hipMemcpyAsync(d_off, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, stream));
         BRX_HIP(hipStreamSynchronize(stream));
     }
     *total = tot;
@@ -462,33 +444,24 @@ int brx_set_insert_batch(brx_set_t *set, const uint8_t *bases, const uint64_t *o
     if (n_reads == 0)
         return BRX_OK;
     if (set->sparse) { // Hash::from_fasta (src/set/hash.rs:40-60): straight into the chained table
-        uint8_t *d_b = nullptr;
-        uint64_t *d_o = nullptr;
-        uint64_t bc = 0, oc = 0, tot = 0;
-        int st = upload_batch(bases, offsets, n_reads, &d_b, &bc, &d_o, &oc, &tot, 0);
-        if (st == BRX_OK)
-            st = index_insert_reads(set, d_b, d_o, n_reads, tot, 0);
-        if (d_b)
-            (void)hipFree(d_b);
-        if (d_o)
-            (void)hipFree(d_o);
-        return st;
+        DevBuf<uint8_t> d_b;
+        DevBuf<uint64_t> d_o;
+        uint64_t tot = 0;
+        BRX_TRY(upload_batch(bases, offsets, n_reads, d_b, d_o, &tot, 0));
+        return index_insert_reads(set, d_b, d_o, n_reads, tot, 0);
     }
     BRX_TRY(need_bits(set, "insert_batch"));
     index_invalidate(set);
-    uint8_t *d_b = nullptr;
-    uint64_t *d_o = nullptr;
-    uint64_t bc = 0, oc = 0, tot = 0;
-    int st = upload_batch(bases, offsets, n_reads, &d_b, &bc, &d_o, &oc, &tot, 0);
-    if (st == BRX_OK) {
+    DevBuf<uint8_t> d_b;
+    DevBuf<uint64_t> d_o;
+    uint64_t tot = 0;
+    BRX_TRY(upload_batch(bases, offsets, n_reads, d_b, d_o, &tot, 0));
+    int st;
+    {
         KernelTimer t("insert", 0);
         st = flat_presence_insert(d_b, d_o, n_reads, tot, set->k, set->d_bits, nullptr, 0, 0, nullptr, 0);
     }
-    hipError_t e = hipDeviceSynchronize();
-    if (d_b)
-        (void)hipFree(d_b);
-    if (d_o)
-        (void)hipFree(d_o);
+    const hipError_t e = hipDeviceSynchronize();
     if (st != BRX_OK)
         return st;
     if (e != hipSuccess) {
@@ -560,26 +533,13 @@ int brx_set_get_batch(const brx_set_t *set, const uint64_t *forward_kmers, uint3
         BRX_TRY(index_ensure(set, nullptr));
         return brx_set_get_batch_indexed(set, forward_kmers, n, out, nullptr);
     }
-    uint64_t *d_k = nullptr;
-    uint8_t *d_o = nullptr;
-    BRX_HIP(hipMalloc((void **)&d_k, (uint64_t)n * 8));
-    hipError_t e = hipMalloc((void **)&d_o, n);
-    if (e != hipSuccess) {
-        (void)hipFree(d_k);
-        set_error("hipMalloc: %s", hipGetErrorString(e));
-        return BRX_ERR_NOMEM;
-    }
-    e = hipMemcpy(d_k, forward_kmers, (uint64_t)n * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        get_kernel<<<(n + 255) / 256, 256>>>(set->d_bits, d_k, n, set->k, d_o);
-        e = hipMemcpy(out, d_o, n, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(d_k);
-    (void)hipFree(d_o);
-    if (e != hipSuccess) {
-        set_error("get_batch: %s", hipGetErrorString(e));
-        return BRX_ERR_HIP;
-    }
+    DevBuf<uint64_t> d_k;
+    DevBuf<uint8_t> d_o;
+    BRX_TRY(d_k.reserve(n, 0, "get_batch k-mers"));
+    BRX_TRY(d_o.reserve(n, 0, "get_batch answers"));
+    BRX_HIP(hipMemcpy(d_k, forward_kmers, (uint64_t)n * 8, hipMemcpyHostToDevice));
+    get_kernel<<<(n + 255) / 256, 256>>>(set->d_bits, d_k, n, set->k, d_o);
+    BRX_HIP(hipMemcpy(out, d_o, n, hipMemcpyDeviceToHost));
     return BRX_OK;
 }
 
@@ -620,17 +580,12 @@ int brx_set_popcount(const brx_set_t *set, uint64_t *n_set_bits)
         *n_set_bits = nl;
         return BRX_OK;
     }
-    unsigned long long *d_t = nullptr;
-    BRX_HIP(hipMalloc((void **)&d_t, 8));
+    DevBuf<unsigned long long> d_t;
+    BRX_TRY(d_t.reserve(1, 0, "popcount"));
     BRX_HIP(hipMemset(d_t, 0, 8));
     popcount_kernel<<<grid_for(set->nwords, 256 * 8), 256>>>(set->d_bits, set->nwords, d_t);
     unsigned long long t = 0;
-    hipError_t e = hipMemcpy(&t, d_t, 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d_t);
-    if (e != hipSuccess) {
-        set_error("popcount: %s", hipGetErrorString(e));
-        return BRX_ERR_HIP;
-    }
+    BRX_HIP(hipMemcpy(&t, d_t, 8, hipMemcpyDeviceToHost));
     *n_set_bits = t;
     return BRX_OK;
 }
@@ -653,19 +608,8 @@ void brx_set_free(brx_set_t *set)
 {
     if (!set)
         return;
-    if (use_device(set->device) == BRX_OK) {
-        if (set->d_bits)
-            (void)hipFree(set->d_bits);
-        if (set->d_lines)
-            (void)hipFree(set->d_lines);
-        if (set->d_keylist)
-            (void)hipFree(set->d_keylist);
-        if (set->d_keylist_n)
-            (void)hipFree(set->d_keylist_n);
-        if (set->d_succ)
-            (void)hipFree(set->d_succ);
-    }
-    delete set;
+    (void)use_device(set->device);
+    delete set; // its device buffers go back to the pool here
 }
 
 // ---- counting ---------------------------------------------------------------------------------
@@ -690,10 +634,8 @@ int brx_set_count_begin(uint8_t k, int device, int strategy, brx_counter_t **out
     c->k = k;
     c->device = device;
     c->strategy = strategy;
-    c->d_counts = nullptr;
     c->part = nullptr;
-    c->d_keys = nullptr;
-    c->n_keys = c->cap_keys = 0;
+    c->n_keys = 0;
     c->stream = nullptr;
     c->count_bytes = set_nbits(k) < 32 ? 32 : set_nbits(k); // one u8 per canonical k-mer, >= one output word
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
@@ -713,7 +655,7 @@ int brx_set_count_begin(uint8_t k, int device, int strategy, brx_counter_t **out
         *out = c;
         return BRX_OK;
     }
-    e = hipMalloc((void **)&c->d_counts, c->count_bytes);
+    e = c->d_counts.reserve_bytes(c->count_bytes, 0, "u8 count table") == BRX_OK ? hipSuccess : hipErrorOutOfMemory;
     if (e == hipSuccess) {
         KernelTimer t("count_zero", c->stream);
         e = hipMemsetAsync(c->d_counts, 0, c->count_bytes, c->stream);
@@ -766,17 +708,13 @@ int brx_set_count_add_batch(brx_counter_t *c, const uint8_t *bases, const uint64
         return BRX_OK;
     std::lock_guard<std::mutex> g(c->mu);
     BRX_HIP(counter_join(c, c->stream)); // a reset or a batch still queued on the caller's stream comes first
-    uint8_t *d_b = nullptr;
-    uint64_t *d_o = nullptr;
-    uint64_t bc = 0, oc = 0, tot = 0;
-    int st = upload_batch(bases, offsets, n_reads, &d_b, &bc, &d_o, &oc, &tot, c->stream);
+    DevBuf<uint8_t> d_b;
+    DevBuf<uint64_t> d_o;
+    uint64_t tot = 0;
+    int st = upload_batch(bases, offsets, n_reads, d_b, d_o, &tot, c->stream);
     if (st == BRX_OK)
         st = brx_set_count_add_batch_device(c, d_b, d_o, n_reads, tot, c->stream);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (d_b)
-        (void)hipFree(d_b);
-    if (d_o)
-        (void)hipFree(d_o);
+    const hipError_t e = hipStreamSynchronize(c->stream);
     if (st != BRX_OK)
         return st;
     if (e != hipSuccess) {
@@ -837,7 +775,7 @@ int brx_set_count_finish_into(brx_counter_t *c, uint8_t abundance, void *stream,
     dst->bits_stale = false; // every word is written below
     {
         KernelTimer t("threshold", s);
-        threshold_kernel<<<grid_for(dst->nwords, 256, 256 * 16), 256, 0, s>>>((const uint4 *)c->d_counts, dst->nwords,
+        threshold_kernel<<<grid_for(dst->nwords, 256, 256 * 16), 256, 0, s>>>((const uint4 *)c->d_counts.get(), dst->nwords,
                                                                              abundance, dst->d_bits);
     }
     BRX_HIP(hipGetLastError());
@@ -874,45 +812,29 @@ int brx_counter_spectrum(brx_counter_t *c, uint64_t *hist256, void *stream)
         return BRX_ERR_ARG;
     BRX_TRY(use_device(c->device));
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long *d_h = nullptr;
-    BRX_HIP(hipMalloc((void **)&d_h, 256 * 8));
-    hipError_t e = hipMemsetAsync(d_h, 0, 256 * 8, s);
+    DevBuf<unsigned long long> d_h;
+    BRX_TRY(d_h.reserve(256, 0, "spectrum"));
+    BRX_HIP(hipMemsetAsync(d_h, 0, 256 * 8, s));
     const uint64_t nbytes = set_nbits(c->k); // real entries (the table may be padded to 32 B)
     if (c->strategy == BRX_COUNT_SORTED || c->strategy == BRX_COUNT_TABLE) {
         // no u8 table to read: the partitioned keys are counted bucket by bucket, the hash table's slots are binned (bins
         // 1..255); bin 0 is the rest
-        int st = e != hipSuccess ? BRX_ERR_HIP : c->strategy == BRX_COUNT_TABLE ? tab_spectrum(c, s, d_h) : part_spectrum(c, s, d_h);
-        if (st == BRX_OK) {
-            e = hipMemcpyAsync(hist256, d_h, 256 * 8, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess)
-                e = hipStreamSynchronize(s);
-            if (e != hipSuccess) {
-                set_error("spectrum: %s", hipGetErrorString(e));
-                st = BRX_ERR_HIP;
-            }
-        }
-        (void)hipFree(d_h);
-        if (st != BRX_OK)
-            return st;
+        BRX_TRY(c->strategy == BRX_COUNT_TABLE ? tab_spectrum(c, s, d_h) : part_spectrum(c, s, d_h));
+        BRX_HIP(hipMemcpyAsync(hist256, d_h, 256 * 8, hipMemcpyDeviceToHost, s));
+        BRX_HIP(hipStreamSynchronize(s));
         uint64_t seen = 0;
         for (int i = 1; i < 256; i++)
             seen += hist256[i];
         hist256[0] = nbytes - seen;
         return BRX_OK;
     }
-    if (e == hipSuccess) {
+    {
         KernelTimer t("spectrum", s);
         // padded tail (k <= 2) would add zeros: count whole words of real entries only
         spectrum_kernel<<<grid_for(nbytes / 4 ? nbytes / 4 : 1, 256 * 16, 2048), 256, 0, s>>>(c->d_counts, nbytes / 4 ? nbytes / 4 : 1, d_h);
-        e = hipMemcpyAsync(hist256, d_h, 256 * 8, hipMemcpyDeviceToHost, s);
+        BRX_HIP(hipMemcpyAsync(hist256, d_h, 256 * 8, hipMemcpyDeviceToHost, s));
     }
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(s);
-    (void)hipFree(d_h);
-    if (e != hipSuccess) {
-        set_error("spectrum: %s", hipGetErrorString(e));
-        return BRX_ERR_HIP;
-    }
+    BRX_HIP(hipStreamSynchronize(s));
     if (nbytes < 4) // k = 1: 2 entries in a padded word; remove the 2 padding zeros of the first word
         hist256[0] -= 4 - nbytes;
     return BRX_OK;
@@ -956,7 +878,7 @@ int brx_counter_load_counts(brx_counter_t *c, uint64_t first, const uint8_t *cou
     BRX_TRY(use_device(c->device));
     BRX_HIP(counter_join(c, nullptr)); // a reset still queued on the caller's stream comes first
     if (n)
-        BRX_HIP(hipMemcpy((uint8_t *)c->d_counts + first, counts, n, hipMemcpyHostToDevice));
+        BRX_HIP(hipMemcpy((uint8_t *)c->d_counts.get() + first, counts, n, hipMemcpyHostToDevice));
     return BRX_OK;
 }
 
@@ -972,7 +894,7 @@ int brx_counter_clamp(brx_counter_t *c, uint8_t cap, void *stream)
     hipStream_t s = (hipStream_t)stream; // nullptr = the legacy default stream, like any HIP API
     {
         KernelTimer t("clamp", s);
-        clamp_kernel<<<grid_for(c->count_bytes / 16, 256, 256 * 16), 256, 0, s>>>((uint4 *)c->d_counts,
+        clamp_kernel<<<grid_for(c->count_bytes / 16, 256, 256 * 16), 256, 0, s>>>((uint4 *)c->d_counts.get(),
                                                                                 c->count_bytes / 16, cap);
     }
     BRX_HIP(hipStreamSynchronize(s));
@@ -1050,24 +972,17 @@ int brx_set_extract_keys_device(const brx_set_t *set, uint64_t first_hash, uint6
     }
     BRX_TRY(use_device(set->device));
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long *d_cnt = nullptr;
-    BRX_HIP(hipMalloc((void **)&d_cnt, 8));
-    hipError_t e = hipMemsetAsync(d_cnt, 0, 8, s);
+    DevBuf<unsigned long long> d_cnt;
+    BRX_TRY(d_cnt.reserve(1, 0, "extract_keys"));
+    BRX_HIP(hipMemsetAsync(d_cnt, 0, 8, s));
     const uint64_t nw = n_hashes / 32;
-    if (e == hipSuccess && nw) {
+    if (nw) {
         KernelTimer t("extract_keys", s);
         extract_kernel<<<grid_for(nw / 4 + 1, 256, 256 * 8), 256, 0, s>>>(set->d_bits, first_hash / 32, nw, d_cnt, d_out, cap);
     }
     unsigned long long n = 0;
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(&n, d_cnt, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(s);
-    (void)hipFree(d_cnt);
-    if (e != hipSuccess) {
-        set_error("extract: %s", hipGetErrorString(e));
-        return BRX_ERR_HIP;
-    }
+    BRX_HIP(hipMemcpyAsync(&n, d_cnt, 8, hipMemcpyDeviceToHost, s));
+    BRX_HIP(hipStreamSynchronize(s));
     *n_out = n;
     if (n > cap) {
         set_error("extract found %llu keys, buffer holds %llu", n, (unsigned long long)cap);
@@ -1098,21 +1013,18 @@ void brx_counter_free(brx_counter_t *c)
 {
     if (!c)
         return;
-    if (use_device(c->device) == BRX_OK) {
-        if (c->part)
-            part_free(c);
-        if (c->tab)
-            tab_free(c);
-        if (c->d_counts)
-            (void)hipFree(c->d_counts);
-        if (c->d_keys)
-            (void)hipFree(c->d_keys);
+    const bool on_device = use_device(c->device) == BRX_OK;
+    if (c->part)
+        part_free(c);
+    if (c->tab)
+        tab_free(c);
+    if (on_device) {
         if (c->stream)
             (void)hipStreamDestroy(c->stream);
         if (c->ev)
             (void)hipEventDestroy(c->ev);
     }
-    delete c;
+    delete c; // its device buffers go back to the pool here
 }
 
 } // extern "C"

@@ -163,16 +163,13 @@ int brx_revcomp_batch(const uint8_t *bases, const uint64_t *offsets, uint32_t n_
         }
     if (total == 0)
         return BRX_OK;
-    uint8_t *d_in = nullptr, *d_o = nullptr;
-    uint64_t *d_off = nullptr;
+    DevBuf<uint8_t> d_in, d_o;
+    DevBuf<uint64_t> d_off;
+    BRX_TRY(d_in.reserve(total, 0, "reads"));
+    BRX_TRY(d_o.reserve(total, 0, "reverse complements"));
+    BRX_TRY(d_off.reserve((uint64_t)n_reads + 1, 0, "offsets"));
     hipStream_t s = nullptr;
     hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&d_in, total);
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&d_o, total);
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&d_off, ((size_t)n_reads + 1) * 8);
     if (e == hipSuccess)
         e = hipMemcpyAsync(d_in, bases, total, hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
@@ -190,12 +187,6 @@ int brx_revcomp_batch(const uint8_t *bases, const uint64_t *offsets, uint32_t n_
         set_error("brx_revcomp_batch: %s", hipGetErrorString(e));
         st = e == hipErrorOutOfMemory ? BRX_ERR_NOMEM : BRX_ERR_HIP;
     }
-    if (d_in)
-        (void)hipFree(d_in);
-    if (d_o)
-        (void)hipFree(d_o);
-    if (d_off)
-        (void)hipFree(d_off);
     if (s)
         (void)hipStreamDestroy(s);
     return st;

@@ -175,48 +175,24 @@ int brx_synth_reads_device(const brx_synth_t *cfg, int device, const uint8_t *d_
         BRX_HIP(hipStreamSynchronize(s));
         return BRX_OK;
     }
-    uint32_t *d_lens = nullptr;
-    uint64_t *d_tmp = nullptr;
-    unsigned long long *d_total = nullptr;
-    BRX_HIP(hipMalloc((void **)&d_lens, (uint64_t)n_reads * 4));
-    hipError_t e = hipMalloc((void **)&d_tmp, scan_tmp_bytes(n_reads) + 8);
-    if (e != hipSuccess) {
-        (void)hipFree(d_lens);
-        set_error("hipMalloc: %s", hipGetErrorString(e));
-        return BRX_ERR_NOMEM;
-    }
-    d_total = (unsigned long long *)((uint8_t *)d_tmp + scan_tmp_bytes(n_reads));
-    int st = BRX_OK;
+    DevBuf<uint32_t> d_lens;
+    DevBuf<uint64_t> d_tmp;
+    BRX_TRY(d_lens.reserve(n_reads, 0, "synthetic read lengths"));
+    BRX_TRY(d_tmp.reserve_bytes(scan_tmp_bytes(n_reads) + 8, 0, "scan scratch"));
+    unsigned long long *d_total = (unsigned long long *)((uint8_t *)d_tmp.get() + scan_tmp_bytes(n_reads));
     read_lens_kernel<<<(n_reads + 63) / 64, 64, 0, s>>>(*cfg, d_genome, first_read, n_reads, d_lens);
-    st = exclusive_scan_lens(d_lens, n_reads, d_tmp, d_offsets, d_total, s);
+    BRX_TRY(exclusive_scan_lens(d_lens, n_reads, d_tmp, d_offsets, d_total, s));
     unsigned long long tot = 0;
-    if (st == BRX_OK) {
-        e = hipMemcpyAsync(&tot, d_total, 8, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            set_error("synth: %s", hipGetErrorString(e));
-            st = BRX_ERR_HIP;
-        }
+    BRX_HIP(hipMemcpyAsync(&tot, d_total, 8, hipMemcpyDeviceToHost, s));
+    BRX_HIP(hipStreamSynchronize(s));
+    *total = tot;
+    if (!d_bases || bases_cap < tot) {
+        set_error("synth reads need %llu bytes, buffer has %llu", tot, (unsigned long long)bases_cap);
+        return BRX_ERR_OVERFLOW;
     }
-    if (st == BRX_OK) {
-        *total = tot;
-        if (!d_bases || bases_cap < tot) {
-            set_error("synth reads need %llu bytes, buffer has %llu", tot, (unsigned long long)bases_cap);
-            st = BRX_ERR_OVERFLOW;
-        }
-    }
-    if (st == BRX_OK) {
-        read_write_kernel<<<(n_reads + 63) / 64, 64, 0, s>>>(*cfg, d_genome, first_read, n_reads, d_offsets, d_bases);
-        e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            set_error("synth write: %s", hipGetErrorString(e));
-            st = BRX_ERR_HIP;
-        }
-    }
-    (void)hipFree(d_lens);
-    (void)hipFree(d_tmp);
-    return st;
+    read_write_kernel<<<(n_reads + 63) / 64, 64, 0, s>>>(*cfg, d_genome, first_read, n_reads, d_offsets, d_bases);
+    BRX_HIP(hipStreamSynchronize(s));
+    return BRX_OK;
 }
 
 } // extern "C"
