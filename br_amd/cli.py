@@ -30,7 +30,9 @@ Not in the reference, like `--device` (include/brx.h "coverage"; a base is cover
     --save-counts PATH         with `fasta` or `count`: write the k-mer counts as a key file with a count byte per key;
                                `count -i PATH` loads it again (the magic is sniffed after decompression; anything else is
                                still read as a pcon count table) and -a or a threshold selector follow as usual.  `fasta`
-                               then counts into the hash table whatever the k, as with --abundance-report: the same set
+                               at 15 <= k <= 21 keeps its partitioned counter and saves that one's count view (measured
+                               faster than the table's count + list + sort: tools/partition_keyfile_bench.py); at any other
+                               k, and with --abundance-report, it counts into the hash table: the same set, the same file
     --save-min-count N         keep only the k-mers counted at least N times (default 1) in --save-counts.  A counter loaded
                                from such a file no longer knows the rarer k-mers: thresholds below N - 1 are refused
     --second-pass MODE         reverse (default: the reference's second scan, reads reversed and not complemented),
@@ -170,7 +172,8 @@ def parser() -> argparse.ArgumentParser:
                         "(not in the reference)")
     p.add_argument("--save-counts", default=None, metavar="PATH",
                    help="write the k-mer counts as a key file; with `fasta` or `count` only; `count -i PATH` loads it.  `fasta` "
-                        "then counts into the hash table (BRX_COUNT_TABLE) whatever the k (not in the reference)")
+                        "then counts into the hash table (BRX_COUNT_TABLE), except at 15 <= k <= 21 without --abundance-report, "
+                        "where its partitioned counter saves its count view (not in the reference)")
     p.add_argument("--save-min-count", type=u8, default=None, metavar="N",
                    help="keep only the k-mers counted at least N times in --save-counts (default 1)")
     sub = p.add_subparsers(dest="subcommand", required=True)
@@ -240,14 +243,17 @@ def build_set(args, keep: Optional[dict] = None) -> Pcon:
     """keep (a dict, --abundance-report / --save-counts): the counter is left in it, and `fasta` counts into the hash table, whose counts
     can be looked up at every k.  (The partitioned counter of 15 <= k <= 21 answers too once Counter.prepare_lookup has
     built its count view, but count + view + lookup measured slower there than the table's count + lookup: DESIGN.md
-    section 10.11, tools/partition_lookup_bench.py)"""
+    section 10.11, tools/partition_lookup_bench.py.)  --save-counts alone at 15 <= k <= 21 keeps the partitioned counter:
+    its count + view + compaction measured faster than the table's count + list + sort at k = 19 and k = 21 (DESIGN.md
+    section 4, tools/partition_keyfile_bench.py), and main() builds the view before it saves"""
     dev = args.device
     if args.subcommand == "fasta":
         k = fasta_kmer_size(args.kmer_size)
         if args.abundance is None and args.abundance_selection is None:
             raise SystemExit("Error: You must provide an abundance method or an abundance threshold")  # main.rs:109
         # (the table takes odd k from 5; below that the dense u8 table is the default anyway and can be looked up too)
-        cnt = Counter(k, dev) if keep is None else Counter(k, dev, _lib.COUNT_TABLE if k >= 5 else _lib.COUNT_DENSE)
+        view_save = keep is not None and args.abundance_report is None and 15 <= k <= 21
+        cnt = Counter(k, dev) if keep is None or view_save else Counter(k, dev, _lib.COUNT_TABLE if k >= 5 else _lib.COUNT_DENSE)
         for path in args.sub_inputs:
             with open_input(path) as f:
                 cnt.count_fasta(f)
@@ -336,6 +342,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         kmer_set = build_set(args, kept)
         if counts_path is not None:
             try:
+                if not kept["counter"].lookup_ready:  # the partitioned counter (build_set): its count file is its count view
+                    kept["counter"].prepare_lookup()
                 with open(counts_path, "wb") as f:
                     kept["counter"].save(f, 1 if args.save_min_count is None else args.save_min_count)
             except _lib.BrxError as e:

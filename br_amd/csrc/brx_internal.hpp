@@ -236,11 +236,13 @@ bool tab_merged(const brx_counter *c, int *world, int *rank);
 int tab_reset(brx_counter *c, hipStream_t s);
 int tab_spectrum(brx_counter *c, hipStream_t s, unsigned long long *d_hist);
 // count view of a BRX_COUNT_SORTED counter (brx_partbuild.hip); the callers hold the counter's lock.  part_lookup_view:
-// false = no valid view; true with *keys == nullptr = nothing was counted
+// false = no valid view; true with *keys == nullptr = nothing was counted.  part_lookup_shape: the buckets the offsets
+// delimit and the positions behind them (brx_keyfile.hip walks the whole view to save it)
 int part_lookup_prepare(brx_counter *c, hipStream_t s);
 void part_lookup_drop(brx_counter *c);
 bool part_lookup_ready(const brx_counter *c);
 bool part_lookup_view(const brx_counter *c, const uint16_t **keys, const uint8_t **counts, const uint64_t **off);
+bool part_lookup_shape(const brx_counter *c, uint64_t *n_buckets, uint64_t *n_positions);
 // k-mer abundance of reads (brx_abundance.hip); the callers (brx_api.hip) hold the counter's lock.  abund_batch enqueues on
 // `s` and returns after its kernels have completed
 int abund_batch(const brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,

@@ -3,7 +3,9 @@
 //
 //   list     a table counter: table_list_kernel, one pass over the slots like table_select_kernel, but with the keepers of
 //            4096 slots placed by a block scan and one atomic per block trip; keys with min(255, count) >= min_count and
-//            their count bytes; the counter is only read.  A set: its key
+//            their count bytes; the counter is only read.  A partitioned counter: its count view compacted in place
+//            order (view_count_kernel, a scan, view_write_kernel) -- sorted already, the sort below finds nothing to do
+//            and is not called.  A set: its key
 //            list as it is, the lines of its chained table (the same kernel, no counts), or the bits (brx_set_extract_keys_device).
 //   sort     stable LSD radix sort of (u64 key, optional u8 payload), 8-bit digits, ceil(key_bits / 8) passes between two
 //            buffers.  A pass is three steps, each its own launches: digit histograms per tile of 4096 keys, an exclusive
@@ -185,6 +187,163 @@ __global__ __launch_bounds__(256) void table_list_kernel(const uint64_t *__restr
                 pos++;
             }
         __syncthreads(); // (sh_base is written again in the next trip)
+    }
+}
+
+// ---- list of a partitioned counter: its count view, compacted --------------------------------------------------------------
+// The count view (brx_partbuild.hip: final_view_kernel) holds, per last-level bucket of 2^VIEW_KEY_BITS hashes, the distinct
+// keys in rising order at the front of the bucket's range, VIEW_PAD behind them, and min(255, count) at the same index; the
+// buckets follow each other in hash order.  The entries with count >= floor, read position by position, are the file's
+// content in the file's order: nothing is sorted, and a keeper's place is the number of keepers before it.
+//   view_count_kernel   sums[w] = keepers of wave chunk w (per_wave consecutive buckets): one flat walk over the chunk's
+//                       positions, the buckets' borders do not matter to a count
+//   scan_exclusive      of the sums; the total sizes the two output arrays
+//   view_write_kernel   the chunk again in groups of up to 63 buckets from ONE load of 64 offsets (lane l: where bucket
+//                       g0 + l starts); a position finds its bucket by a binary search over the lanes' offsets (6 shuffles)
+// Both walk 256 positions a trip, four neighbouring ones per lane from one 8-byte and one 4-byte load, whatever the shape:
+// 2^29 buckets of two positions (k = 21), 32 buckets of 9 300 (k = 9), or a range of 70 000 positions behind one key --
+// padding is read like a key and kept by nobody, which costs its 3 bytes and no round trip.  Places inside a trip: lane
+// order, then the lane's own four -- four ballots and the lanes below.  No LDS, no barrier, no atomics: a wave owns its
+// chunk in both passes.  Positions and places are 64-bit; only the distances inside a group are kept in 32 bits for the
+// search, and a group that spans 2^32 positions or more is walked bucket by bucket instead, no search needed.
+constexpr uint32_t VIEW_KEY_BITS = 12, VIEW_PAD = 0xFFFFu; // (F_BITS and VIEW_PAD of brx_partbuild.hip)
+constexpr uint32_t VC_GROUP = 63, VC_MAX_GROUPS = 16, VC_TRIP = 256;
+
+// the four positions at .. at + 3 (at % 4 == 0) of the view, those inside [lo, hi) only: bit q of the result = position
+// at + q is kept.  (The quad that holds hi - 1 may reach 3 entries past hi: both arrays are allocated 64 entries longer.)
+__device__ __forceinline__ uint32_t view_quad(const uint16_t *__restrict__ vkeys, const uint8_t *__restrict__ vcnts, uint64_t at, uint64_t lo,
+                                              uint64_t hi, uint32_t floor, uint32_t key[4], uint32_t cnt[4])
+{
+    uint32_t keep = 0;
+    if (at < hi) {
+        const uint2 kv = *reinterpret_cast<const uint2 *>(vkeys + at);
+        const uint32_t cv = *reinterpret_cast<const uint32_t *>(vcnts + at);
+        key[0] = kv.x & 0xFFFFu;
+        key[1] = kv.x >> 16;
+        key[2] = kv.y & 0xFFFFu;
+        key[3] = kv.y >> 16;
+        for (uint32_t q = 0; q < 4u; q++) {
+            cnt[q] = (cv >> (8u * q)) & 0xFFu;
+            if (at + q >= lo && at + q < hi && key[q] != VIEW_PAD && cnt[q] >= floor)
+                keep |= 1u << q;
+        }
+    }
+    return keep;
+}
+
+__global__ __launch_bounds__(256) void view_count_kernel(const uint16_t *__restrict__ vkeys, const uint8_t *__restrict__ vcnts,
+                                                         const uint64_t *__restrict__ off, uint64_t n_buckets, uint32_t per_wave,
+                                                         uint64_t n_wchunks, uint32_t floor, u64 *__restrict__ sums)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t n_bchunks = (n_wchunks + 3ull) / 4ull;
+    for (uint64_t bc = blockIdx.x; bc < n_bchunks; bc += gridDim.x) {
+        const uint64_t w = bc * 4ull + wave;
+        if (w >= n_wchunks)
+            continue; // wave-uniform
+        const uint64_t b_lo = w * per_wave;
+        const uint64_t b_hi = b_lo + per_wave < n_buckets ? b_lo + per_wave : n_buckets;
+        const uint64_t lo = off[b_lo], hi = off[b_hi];
+        uint32_t key[4], cnt[4];
+        u64 mine = 0;
+        for (uint64_t q0 = lo & ~3ull; q0 < hi; q0 += VC_TRIP) // wave-uniform
+            mine += (u64)__popc(view_quad(vkeys, vcnts, q0 + 4ull * lane, lo, hi, floor, key, cnt));
+        for (int o = 32; o > 0; o >>= 1)
+            mine += __shfl_xor(mine, o);
+        if (lane == 0u)
+            sums[w] = mine;
+    }
+}
+
+// sums: scanned.  walk: positions [lo, hi) of the view from place `run` on; SEARCH: they lie in buckets g0 .. g0 + gcount - 1,
+// lane l <= gcount holding in rel where bucket g0 + l starts behind `lo` (lane gcount: hi - lo, below 2^32); otherwise all
+// in bucket g0.  Returns the place behind the last keeper.
+template <bool SEARCH>
+__device__ __forceinline__ u64 view_write_walk(const uint16_t *__restrict__ vkeys, const uint8_t *__restrict__ vcnts, uint64_t lo, uint64_t hi,
+                                               uint64_t g0, uint32_t gcount, uint32_t rel, uint32_t floor, u64 run,
+                                               uint64_t *__restrict__ keys, uint8_t *__restrict__ cnts, uint64_t cap, uint32_t lane)
+{
+    for (uint64_t q0 = lo & ~3ull; q0 < hi; q0 += VC_TRIP) { // wave-uniform
+        const uint64_t at = q0 + 4ull * lane;
+        uint32_t key[4], cnt[4];
+        const uint32_t keep = view_quad(vkeys, vcnts, at, lo, hi, floor, key, cnt);
+        uint32_t before = 0, total = 0;
+        for (uint32_t q = 0; q < 4u; q++) {
+            const u64 m = __ballot((keep >> q) & 1u);
+            before += __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); // kept in the lanes below
+            total += (uint32_t)__popcll(m);
+        }
+        if (!total)
+            continue; // wave-uniform
+        uint32_t bucket[4] = {0u, 0u, 0u, 0u};
+        if (SEARCH)
+            for (uint32_t q = 0; q < 4u; q++) { // every lane takes part in the shuffles
+                const uint32_t p = (uint32_t)(at + q - lo); // (of a kept position: inside [0, hi - lo))
+                uint32_t j = 0;
+                for (uint32_t step = 32u; step; step >>= 1) {
+                    const uint32_t cand = j + step; // <= 63
+                    const uint32_t r = __shfl(rel, (int)cand);
+                    if (cand < gcount && r <= p)
+                        j = cand;
+                }
+                bucket[q] = j; // the last bucket that starts at or before p: the empty ones before it start there too
+            }
+        uint64_t pos = run + before;
+        for (uint32_t q = 0; q < 4u; q++)
+            if ((keep >> q) & 1u) {
+                if (pos < cap) { // (always: the sums were taken over the same view)
+                    keys[pos] = ((g0 + bucket[q]) << VIEW_KEY_BITS) | (uint64_t)key[q];
+                    cnts[pos] = (uint8_t)cnt[q];
+                }
+                pos++;
+            }
+        run += total;
+    }
+    return run;
+}
+
+__global__ __launch_bounds__(256) void view_write_kernel(const uint16_t *__restrict__ vkeys, const uint8_t *__restrict__ vcnts,
+                                                         const uint64_t *__restrict__ off, uint64_t n_buckets, uint32_t per_wave,
+                                                         uint64_t n_wchunks, uint32_t floor, uint64_t wide_span,
+                                                         const u64 *__restrict__ sums, uint64_t *__restrict__ keys,
+                                                         uint8_t *__restrict__ cnts, uint64_t cap)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t n_bchunks = (n_wchunks + 3ull) / 4ull;
+    for (uint64_t bc = blockIdx.x; bc < n_bchunks; bc += gridDim.x) {
+        const uint64_t w = bc * 4ull + wave;
+        if (w >= n_wchunks)
+            continue; // wave-uniform
+        const uint64_t b_lo = w * per_wave;
+        const uint64_t b_hi = b_lo + per_wave < n_buckets ? b_lo + per_wave : n_buckets;
+        if (off[b_lo] == off[b_hi])
+            continue; // nothing but empty buckets (most chunks of a small input at large k)
+        u64 run = sums[w]; // keepers of the whole view before the next one
+        for (uint64_t g0 = b_lo; g0 < b_hi; g0 += VC_GROUP) {
+            const uint32_t gcount = b_hi - g0 < VC_GROUP ? (uint32_t)(b_hi - g0) : VC_GROUP;
+            const uint64_t oi = g0 + lane;
+            const uint64_t offv = off[oi <= n_buckets ? oi : n_buckets];
+            const uint32_t off_lo = (uint32_t)offv, off_hi = (uint32_t)(offv >> 32);
+            // (readlane returns a signed int: without the casts an offset with bit 31 set sign-extends)
+            const uint64_t gs = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)off_hi, 0) << 32) |
+                                (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)off_lo, 0);
+            const uint64_t ge = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)off_hi, (int)gcount) << 32) |
+                                (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)off_lo, (int)gcount);
+            if (ge == gs)
+                continue;
+            if (ge - gs < wide_span) { // (at most 2^32)
+                const uint32_t rel = lane <= gcount ? (uint32_t)(offv - gs) : 0xFFFFFFFFu;
+                run = view_write_walk<true>(vkeys, vcnts, gs, ge, g0, gcount, rel, floor, run, keys, cnts, cap, lane);
+            } else { // 2^32 positions in 63 buckets: bucket by bucket, no distance to keep in 32 bits
+                for (uint32_t j = 0; j < gcount; j++) {
+                    const uint64_t s = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)off_hi, (int)j) << 32) |
+                                       (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)off_lo, (int)j);
+                    const uint64_t e = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)off_hi, (int)j + 1) << 32) |
+                                       (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)off_lo, (int)j + 1);
+                    run = view_write_walk<false>(vkeys, vcnts, s, e, g0 + j, 1u, 0u, floor, run, keys, cnts, cap, lane);
+                }
+            }
+        }
     }
 }
 
@@ -933,6 +1092,72 @@ int table_counter_only(const char *me, brx_counter *c)
     return BRX_OK;
 }
 
+// The count view of a partitioned counter (the caller holds its lock and has seen part_lookup_ready) compacted into two
+// arrays out of `ws`: the keys counted at least `floor` times, rising, and their count bytes; *n_out of them (none: the
+// arrays stay null).  The view is only read.  Returns after `s` has been synchronised.
+int list_view(const brx_counter *c, uint8_t floor, hipStream_t s, DevScratch &ws, uint64_t **d_keys, uint8_t **d_cnts, uint64_t *n_out)
+{
+    const char *me = "brx_counter_save_fd";
+    *d_keys = nullptr;
+    *d_cnts = nullptr;
+    *n_out = 0;
+    const uint16_t *vkeys = nullptr;
+    const uint8_t *vcnts = nullptr;
+    const uint64_t *voff = nullptr;
+    uint64_t n_buckets = 0, n_pos = 0;
+    if (!part_lookup_view(c, &vkeys, &vcnts, &voff) || !part_lookup_shape(c, &n_buckets, &n_pos)) {
+        set_error("%s: the count view is gone", me);
+        return BRX_ERR_HIP;
+    }
+    if (!vkeys || !n_pos || !n_buckets)
+        return BRX_OK; // nothing was counted
+    if (((uintptr_t)vkeys & 7u) || ((uintptr_t)vcnts & 3u)) { // (the pool hands out aligned blocks: four positions per load)
+        set_error("%s: the count view is not aligned", me);
+        return BRX_ERR_HIP;
+    }
+    // buckets per wave: enough wave chunks to fill the device where there are few buckets (k = 9: 32 of them), whole
+    // groups and 16 offset loads per chunk where there are many (k = 21: 2^29 buckets, 532 611 sums to scan)
+    uint64_t per_wave = (n_buckets + 16383ull) / 16384ull;
+    if (per_wave > VC_GROUP)
+        per_wave = (per_wave + VC_GROUP - 1) / VC_GROUP * VC_GROUP;
+    if (per_wave > VC_GROUP * VC_MAX_GROUPS)
+        per_wave = VC_GROUP * VC_MAX_GROUPS;
+    const uint64_t n_wchunks = (n_buckets + per_wave - 1) / per_wave;
+    const uint64_t n_sums = (n_wchunks + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    u64 *d_part = nullptr, *d_sums = nullptr;
+    BRX_TRY(ws.get(&d_part, n_wchunks));
+    BRX_TRY(ws.get(&d_sums, n_sums + 1));
+    const uint32_t grid = read_grid((n_wchunks + 3ull) / 4ull, 256u * 16u);
+    {
+        KernelTimer kt("key_list", s);
+        view_count_kernel<<<grid, 256, 0, s>>>(vkeys, vcnts, voff, n_buckets, (uint32_t)per_wave, n_wchunks, floor, d_part);
+        BRX_HIP(hipGetLastError());
+        BRX_TRY(scan_exclusive(d_part, n_wchunks, d_sums, s));
+    }
+    u64 total = 0;
+    BRX_HIP(hipMemcpyAsync(&total, d_sums + n_sums, 8, hipMemcpyDeviceToHost, s));
+    BRX_HIP(hipStreamSynchronize(s));
+    if (total > n_pos) {
+        set_error("%s: %llu entries kept from a count view of %llu positions", me, total, (u64)n_pos);
+        return BRX_ERR_HIP;
+    }
+    if (!total)
+        return BRX_OK;
+    BRX_TRY(ws.get(d_keys, total));
+    BRX_TRY(ws.get(d_cnts, total));
+    {
+        KernelTimer kt("key_list", s);
+        // (BRX_VIEW_WIDE_SPAN, read per call: the tests send small groups down the path of a group that spans 2^32 positions)
+        const uint32_t e_span = env_u32("BRX_VIEW_WIDE_SPAN", 0u);
+        view_write_kernel<<<grid, 256, 0, s>>>(vkeys, vcnts, voff, n_buckets, (uint32_t)per_wave, n_wchunks, floor,
+                                               e_span ? (uint64_t)e_span : 1ull << 32, d_part, *d_keys, *d_cnts, total);
+        BRX_HIP(hipGetLastError());
+    }
+    BRX_HIP(hipStreamSynchronize(s));
+    *n_out = total;
+    return BRX_OK;
+}
+
 // the keys of a set, whatever holds it, into d_out; a lazy bit vector stays lazy
 int list_set(const brx_set *cset, hipStream_t s, DevBuf<uint64_t> &d_out, uint64_t *n_out)
 {
@@ -1034,6 +1259,31 @@ int brx_counter_save_fd(brx_counter_t *c, uint8_t min_count, int out_fd, uint64_
     auto t0 = Clock::now();
     BRX_TRY(use_device(c->device));
     std::lock_guard<std::mutex> g(c->mu);
+    if (c->strategy == BRX_COUNT_SORTED) {
+        // the count view is the file's content in the file's order: compacted, packed, written; never floored
+        if (!part_lookup_ready(c)) {
+            set_error("%s: a partitioned counter saves its count view: build it first (brx_counter_lookup_prepare; every call that "
+                      "counts, finishes or resets drops it), or count with the table count strategy (BRX_COUNT_TABLE)", me);
+            return BRX_ERR_UNSUPPORTED;
+        }
+        hipStream_t s = c->stream;
+        BRX_HIP(counter_join(c, c->stream));
+        const uint8_t floor = min_count < 1 ? 1 : min_count;
+        DevScratch ws;
+        uint64_t *d_keys = nullptr;
+        uint8_t *d_cnts = nullptr;
+        uint64_t n = 0;
+        auto t1 = Clock::now();
+        BRX_TRY(list_view(c, floor, s, ws, &d_keys, &d_cnts, &n));
+        st8[4] = ns_since(t1);
+        uint8_t one = 0; // (as below: an empty count file still carries the flag)
+        const int st = pack_and_write(c->k, d_keys, n ? d_cnts : &one, n, floor, out_fd, s, st8);
+        st8[0] = n;
+        st8[7] = ns_since(t0);
+        if (stats8)
+            memcpy(stats8, st8, sizeof st8);
+        return st;
+    }
     BRX_TRY(table_counter_only(me, c));
     hipStream_t s = c->stream;
     BRX_HIP(counter_join(c, c->stream));

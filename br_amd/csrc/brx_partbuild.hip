@@ -2451,4 +2451,18 @@ bool part_lookup_view(const brx_counter *c, const uint16_t **keys, const uint8_t
     return true;
 }
 
+// how far the view reaches: *n_buckets last-level buckets (off holds one entry more), *n_positions = off[*n_buckets]
+bool part_lookup_shape(const brx_counter *c, uint64_t *n_buckets, uint64_t *n_positions)
+{
+    const PartState *st = c->part;
+    if (!st || !st->view_valid)
+        return false;
+    uint64_t total = 0;
+    for (auto &b : st->batches)
+        total += b.n;
+    *n_buckets = st->pl.nchild[st->pl.nlev - 1];
+    *n_positions = st->view_empty ? 0 : total;
+    return true;
+}
+
 } // namespace brx

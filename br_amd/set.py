@@ -389,7 +389,9 @@ class Counter:
     # ---- key files (include/brx.h "key files", br_amd/keyfile.py) -----------------------------------------------------
     def save(self, f, min_count: int = 1) -> dict:
         """write the k-mers counted at least min_count times, with min(255, count), as a key file to the binary file object
-        `f` (brx_counter_save_fd: table strategy).  The counter is left as it was"""
+        `f` (brx_counter_save_fd).  A table counter saves at any time; a partitioned one saves its count view, so call
+        prepare_lookup() first (and again after anything that drops the view) -- nothing prepares it implicitly.  Dense
+        counters are refused.  The counter, and a partitioned counter's view, are left as they were"""
         from . import hostio
         _check_u8(min_count, "min_count")
         st = (C.c_uint64 * 8)()

@@ -331,7 +331,8 @@ int brx_counter_get_counts(brx_counter_t *c, const uint64_t *forward_kmers, uint
  * the partition workspace: add_batch[_device], add_partitioned_device, finish / finish_into, spectrum, reset, l1_view
  * and the brx_exchange_* entries each drop it first, and abundance / get_counts refuse again until the next prepare
  * (prepare after the threshold is chosen and the set finished).  The counter itself is left as it was: spectrum and
- * finish with any threshold still follow and give what they gave before.
+ * finish with any threshold still follow and give what they gave before.  brx_counter_save_fd (key files, below) reads
+ * the view too -- it is the count file in the file's order -- needs it like a lookup does, and leaves it valid.
  * state: *state = 1 if abundance / get_counts would answer (always for dense / table), 0 if they would refuse.
  * drop: frees the view's count array; state 0 for a partitioned counter, nothing to do for the others.
  * All three take the counter's lock.                                                                                    */
@@ -362,13 +363,21 @@ int brx_counter_lookup_drop(brx_counter_t *c);
 int brx_sort_keys_device(uint64_t *d_keys, uint8_t *d_payload /* may be NULL */, uint64_t n, uint32_t key_bits, void *stream);
 /* The count file of a BRX_COUNT_TABLE counter: every k-mer with min(255, count) >= max(min_count, 1, the counter's floor),
  * with that count.  The counter is only read: spectrum, finish, abundance and get_counts answer afterwards what they did
- * before.  Dense and partitioned counters, and a counter merged across ranks (brx_counter_merge_state world != 0), return
+ * before.  A partitioned counter (BRX_COUNT_SORTED, odd k from 7) saves its COUNT VIEW: read bucket by bucket the view is
+ * the file's content in the file's order, so the entries with count >= max(min_count, 1) are compacted in place order --
+ * a count, a scan and a write under "key_list", nothing under "key_sort" -- and packed ([4] of stats8: ns of the
+ * compaction; such a counter is never floored; the same bytes as the table counter's file of the same reads).  The save
+ * needs the view and never builds it: without one it returns BRX_ERR_UNSUPPORTED and names brx_counter_lookup_prepare.  It
+ * only reads the view and leaves it: brx_counter_lookup_state stays 1, and abundance, get_counts, spectrum and finish answer
+ * what they answered before.  A counter that counted nothing writes the header alone, counts flag set, from either
+ * strategy.  Dense counters, and a counter merged across ranks (brx_counter_merge_state world != 0), return
  * BRX_ERR_UNSUPPORTED.  Takes the counter's lock and works on the counter's own stream.                                    */
 int brx_counter_save_fd(brx_counter_t *c, uint8_t min_count /* 0 means 1 */, int out_fd, uint64_t *stats8);
 /* ADDS the counts of a count file to a BRX_COUNT_TABLE counter of the same k (BRX_ERR_ARG otherwise): the table is regrown
  * for the k-mers it holds plus the file's, counts add and saturate at 255 -- loading the files of shards counted separately
  * gives the counter of all their reads, as brx_exchange_table_merge does across GPUs.  A set file (no counts) is
- * BRX_ERR_FORMAT; strategies and merged counters as for save.  A file saved with min_count f > 1 no longer knows the
+ * BRX_ERR_FORMAT; dense, partitioned (it holds occurrences, not counts to add to) and merged counters are
+ * BRX_ERR_UNSUPPORTED.  A file saved with min_count f > 1 no longer knows the
  * k-mers seen fewer than f times: it loads only into an EMPTY counter (BRX_ERR_ARG otherwise), which is then FLOORED at f
  * until brx_counter_reset -- brx_set_count_finish[_into] with abundance < f - 1 (the set would miss members),
  * add_batch[_device] and a further load return BRX_ERR_ARG, spectrum bins 1..f-1 read 0, a save writes floor max(f,
