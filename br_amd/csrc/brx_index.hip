@@ -2,28 +2,42 @@
 #include "brx_internal.hpp"
 #include "brx_index.hpp"
 
+#include <stdio.h>
 #include <stdlib.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
 
 using namespace brx;
 
 namespace {
 
+// the line a key's minimizer addresses (key = canonical >> 1, as the key lists hold it)
+__device__ __forceinline__ uint32_t key_home_line(uint64_t h, uint32_t line_shift, uint32_t m, uint32_t w, int k)
+{
+    const uint64_t canon = (h << 1) | (uint64_t)(popc64(h) & 1); // even popcount (brx_kmer.hpp)
+    return index_line_of(minimizer_of(canon, revcomp(canon, k), m, w), line_shift);
+}
+
 // one key per thread: claim a slot of the key's line; a full line is flagged as overflowed and the key is
 // left to the bit vector (CHAIN = false) or goes on to the next line (CHAIN = true: sparse sets)
+// `cont_lines` (with the number of keys in *n_dev, at most n): the keys whose chain left its region in index_lines_kernel
+// go on at the line given there; they were counted, and left their signature, before they left
 template <bool CHAIN>
 __global__ __launch_bounds__(256) void index_insert_kernel(const uint64_t *__restrict__ keys, uint64_t n, uint64_t *__restrict__ lines,
                                                            uint32_t line_shift, uint32_t m, uint32_t w, int k,
-                                                           unsigned long long *__restrict__ n_overflow, uint32_t *__restrict__ line_bits)
+                                                           unsigned long long *__restrict__ n_overflow, uint32_t *__restrict__ line_bits,
+                                                           const uint32_t *__restrict__ cont_lines = nullptr,
+                                                           const unsigned long long *__restrict__ n_dev = nullptr)
 {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     const uint32_t line_mask = 0xffffffffu >> line_shift;
     uint32_t lost = 0;
+    if (n_dev && *n_dev < n)
+        n = *n_dev;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const uint64_t h = keys[i];
-        const uint64_t canon = (h << 1) | (uint64_t)(popc64(h) & 1); // even popcount (brx_kmer.hpp)
-        const uint64_t rc = revcomp(canon, k);
-        uint32_t line = index_line_of(minimizer_of(canon, rc, m, w), line_shift);
-        bool counted = false;
+        uint32_t line = cont_lines ? cont_lines[i] : key_home_line(h, line_shift, m, w, k);
+        bool counted = cont_lines != nullptr;
         // a chained walk visits at most every line once (the host checks that the table has room for its keys;
         // this bound keeps a mis-sized table from spinning the GPU for ever: the key is then simply lost and counted)
         for (uint32_t walked = 0; walked <= line_mask; walked++) {
@@ -51,6 +65,155 @@ __global__ __launch_bounds__(256) void index_insert_kernel(const uint64_t *__res
                 break;
             line = (line + 1u) & line_mask; // the table has more slots than keys: this ends
         }
+    }
+    for (int d = 32; d > 0; d >>= 1)
+        lost += __shfl_down(lost, d);
+    if ((threadIdx.x & 63) == 0 && lost)
+        atomicAdd(n_overflow, (unsigned long long)lost);
+}
+
+// ---- the build by regions: keys ordered by region, every region's lines put together in LDS and written once -----------
+// A region is a run of 2^region_log consecutive lines (a smaller table is one region).
+#ifndef BRX_INDEX_REGION_LOG
+#define BRX_INDEX_REGION_LOG 10 // 1024 lines: 64 KiB of LDS, two blocks per CU
+#endif
+#ifndef BRX_INDEX_LINES_THREADS
+#define BRX_INDEX_LINES_THREADS 512
+#endif
+#ifndef BRX_INDEX_ORDER_PAIRS
+#define BRX_INDEX_ORDER_PAIRS 0 // 1: (region, key) pairs also where the region fits above the key (the measured comparison)
+#endif
+#ifndef BRX_INDEX_NT_STORE
+#define BRX_INDEX_NT_STORE 1 // the lines go out with non-temporal stores: nobody reads them before the table is whole (0.455 against 0.494 ms)
+#endif
+constexpr uint32_t IDX_REGION_LOG = BRX_INDEX_REGION_LOG;
+constexpr uint32_t IDX_LINES_THREADS = BRX_INDEX_LINES_THREADS;
+static_assert(IDX_REGION_LOG >= 6 && IDX_REGION_LOG <= 11, "a region's image must fit the LDS of a CU");
+static_assert(IDX_LINES_THREADS % 64 == 0 && IDX_LINES_THREADS <= 1024, "whole waves");
+
+// What the sort orders by: the region of every key's home line.  Where the key's 2k - 1 bits leave room in the word, the
+// region goes on top of the key (`packed`, key_bits up) and the sort moves one 8-byte word per key; else it is a 32-bit
+// sort key of its own (`region_of`) and the key travels as the pair's value, 12 bytes per key.
+__global__ __launch_bounds__(256) void index_region_of_kernel(const uint64_t *__restrict__ keys, uint32_t n, uint32_t line_shift, uint32_t m,
+                                                              uint32_t w, int k, uint32_t region_log, uint32_t *__restrict__ region_of,
+                                                              uint64_t *__restrict__ packed, uint32_t key_bits)
+{
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t h = keys[i];
+        const uint32_t region = key_home_line(h, line_shift, m, w, k) >> region_log;
+        if (packed)
+            packed[i] = ((uint64_t)region << key_bits) | (h & ((1ull << key_bits) - 1ull));
+        else
+            region_of[i] = region;
+    }
+}
+
+// first[r] = index of the first key of region r in the sorted list, first[n_regions] = n (neither list: one region)
+__global__ __launch_bounds__(256) void index_region_first_kernel(const uint32_t *__restrict__ sorted, const uint64_t *__restrict__ packed,
+                                                                 uint32_t key_bits, uint32_t n, uint32_t n_regions,
+                                                                 uint32_t *__restrict__ first)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    auto region_at = [&](uint64_t i) { return packed ? (uint32_t)(packed[i] >> key_bits) : (sorted ? sorted[i] : 0u); };
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += stride) {
+        const uint32_t lo = i == 0 ? 0u : region_at(i - 1) + 1u;
+        uint32_t hi = i == n ? n_regions : region_at(i);
+        if (hi > n_regions) // (cannot be: a line number has log2(lines) bits)
+            hi = n_regions;
+        for (uint32_t r = lo; r <= hi; r++)
+            first[r] = (uint32_t)i;
+    }
+}
+
+// One block per region at a time.  index_insert_kernel's algorithm against the region's image in LDS, then the image
+// goes out in 16-byte stores and the region's occupancy bits with it: every byte of the table, of the bits and of the
+// spare bytes behind them is written exactly once, and nothing is read.  A chain that walks out of its region is handed to
+// index_insert_kernel<true> (cont_keys / cont_lines), which runs when the whole table stands.
+template <bool CHAIN>
+__global__ __launch_bounds__(IDX_LINES_THREADS) void index_lines_kernel(const uint64_t *__restrict__ keys, uint64_t key_mask,
+                                                                        const uint32_t *__restrict__ first, uint32_t n_regions, uint32_t region_log, uint64_t *__restrict__ lines,
+                                                                        uint32_t line_shift, uint32_t m, uint32_t w, int k,
+                                                                        unsigned long long *__restrict__ n_overflow,
+                                                                        uint32_t *__restrict__ line_bits, uint64_t *__restrict__ cont_keys,
+                                                                        uint32_t *__restrict__ cont_lines, unsigned long long *__restrict__ n_cont,
+                                                                        uint64_t cont_cap)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned long long img[]; // 8 words per line of the region
+    const uint32_t rlines = 1u << region_log;
+    const uint32_t line_mask = 0xffffffffu >> line_shift;
+    uint4 *img4 = reinterpret_cast<uint4 *>(img);
+    uint32_t lost = 0;
+    for (uint32_t r = blockIdx.x; r < n_regions; r += gridDim.x) {
+        for (uint32_t i = threadIdx.x; i < rlines * 4u; i += IDX_LINES_THREADS)
+            img4[i] = make_uint4(0u, 0u, 0u, 0u);
+        __syncthreads();
+        const uint32_t base = r << region_log;
+        const uint32_t end = first[r + 1];
+        for (uint32_t i = first[r] + threadIdx.x; i < end; i += IDX_LINES_THREADS) {
+            const uint64_t h = keys[i] & key_mask; // (the ordered list may carry the region above the key)
+            uint32_t ll = (key_home_line(h, line_shift, m, w, k) - base) & (rlines - 1u); // (the mask: never outside the image)
+            bool counted = false;
+            for (;;) {
+                unsigned long long *L = img + ll * 8u;
+                const unsigned long long seen = __hip_atomic_load(L + 7, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                uint32_t slot = IDX_SLOTS;
+                if ((uint32_t)seen < (uint32_t)IDX_SLOTS)
+                    slot = (uint32_t)__hip_atomic_fetch_add(L + 7, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (slot < (uint32_t)IDX_SLOTS) {
+                    L[slot] = h + 1ull;
+                    break;
+                }
+                {
+                    const unsigned long long want = (unsigned long long)IDX_OVERFLOW | (counted ? 0ull : (unsigned long long)idx_sig_bit(h + 1ull));
+                    if ((seen & want) != want)
+                        (void)__hip_atomic_fetch_or(L + 7, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                if (!counted) {
+                    lost++;
+                    counted = true;
+                }
+                if (!CHAIN)
+                    break;
+                if (++ll == rlines) { // the chain leaves the region (the last line of the table goes on at line 0)
+                    const unsigned long long at = atomicAdd(n_cont, 1ull);
+                    if (at < cont_cap) { // (more than the list holds: the host sees the count and builds the old way)
+                        cont_keys[at] = h;
+                        cont_lines[at] = (base + rlines) & line_mask;
+                    }
+                    break;
+                }
+            }
+        }
+        __syncthreads();
+        uint4 *out = reinterpret_cast<uint4 *>(lines + (uint64_t)base * 8ull);
+        for (uint32_t i = threadIdx.x; i < rlines * 4u; i += IDX_LINES_THREADS) {
+#if BRX_INDEX_NT_STORE
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            __builtin_nontemporal_store(reinterpret_cast<const u32x4 *>(img4)[i], reinterpret_cast<u32x4 *>(out) + i);
+#else
+            out[i] = img4[i];
+#endif
+        }
+        // occupancy bits, one per line that holds a key: a wave's ballot is the bits of 64 lines
+        if (rlines >= 64u) {
+            for (uint32_t l = threadIdx.x; l < rlines; l += IDX_LINES_THREADS) { // (wave-uniform trip count)
+                const unsigned long long b = __ballot((uint32_t)img[l * 8u + 7u] != 0u);
+                if ((threadIdx.x & 63u) == 0u)
+                    reinterpret_cast<unsigned long long *>(line_bits)[(base + l) >> 6] = b;
+            }
+        } else if (threadIdx.x < 64u) { // a table of 16 or 32 lines (it is its only region)
+            const unsigned long long b = __ballot(threadIdx.x < rlines && (uint32_t)img[(threadIdx.x & (rlines - 1u)) * 8u + 7u] != 0u);
+            if (threadIdx.x == 0u) {
+                if (rlines == 32u)
+                    line_bits[0] = (uint32_t)b;
+                else
+                    reinterpret_cast<uint16_t *>(line_bits)[0] = (uint16_t)b;
+            }
+        }
+        if (r == n_regions - 1u && threadIdx.x < 64u) // the 64 spare bytes behind the bits
+            reinterpret_cast<uint8_t *>(line_bits)[(((uint64_t)line_mask + 1ull) >> 3) + threadIdx.x] = 0;
+        __syncthreads(); // the image is zeroed again for the block's next region
     }
     for (int d = 32; d > 0; d >>= 1)
         lost += __shfl_down(lost, d);
@@ -155,6 +318,108 @@ int index_auto_m(int k, uint64_t n_keys)
     return m < 3 ? 3 : m;
 }
 
+// The build by regions, queued on `s`: order the keys by the region of their home line, put every region's lines
+// together in LDS (index_lines_kernel), then place the few keys whose chain left its region.  `done` stays false, and
+// nothing is queued, when the scratch (16 bytes per key for the word that is sorted and the ordered list, 24 where the
+// region does not fit above the key; the sort's own workspace) cannot be had.  `scratch` must live until the stream
+// has run all this.  d_counts[0] gets the keys turned away by their home line, d_counts[1] the keys that left their
+// region: above `cont_cap` the list did not hold them all and the table is incomplete.
+// An error return may leave kernels queued that use `scratch` and d_counts: the caller waits for the stream before it
+// lets go of them.
+static int index_build_regions(const uint64_t *d_keys, uint64_t n, uint64_t *d_lines, int log_lines, uint32_t m, uint32_t w, int k, bool chain,
+                               unsigned long long *d_counts, hipStream_t s, DevBuf<uint8_t> &scratch, bool &done, uint64_t &cont_cap)
+{
+    done = false;
+    if (n >= (1ull << 31))
+        return BRX_OK; // 32-bit positions in the ordered list
+    const uint32_t line_shift = 32u - (uint32_t)log_lines;
+    const uint32_t region_log = (uint32_t)log_lines < IDX_REGION_LOG ? (uint32_t)log_lines : IDX_REGION_LOG;
+    const uint32_t sort_bits = (uint32_t)log_lines - region_log;
+    const uint32_t n_regions = 1u << sort_bits;
+    const uint64_t n_lines = 1ull << log_lines;
+    cont_cap = chain ? n / 8ull + 4096ull : 0ull;
+
+    const bool ordered = sort_bits && n;
+    const uint32_t key_bits = 2u * (uint32_t)k - 1u;
+    const bool pack = ordered && key_bits + sort_bits <= 64u && !BRX_INDEX_ORDER_PAIRS;
+    size_t sort_bytes = 0;
+    if (pack)
+        BRX_HIP(rocprim::radix_sort_keys(nullptr, sort_bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t)n, key_bits,
+                                         key_bits + sort_bits, s));
+    else if (ordered)
+        BRX_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, d_keys, (uint64_t *)nullptr,
+                                          (uint32_t)n, 0u, sort_bits, s));
+    auto up = [](uint64_t b) { return (b + 255ull) & ~255ull; };
+    const uint64_t o_first = 0, o_ckeys = o_first + up(((uint64_t)n_regions + 1ull) * 4ull), o_clines = o_ckeys + up(cont_cap * 8ull),
+                   o_sorted = o_clines + up(cont_cap * 4ull), o_rin = o_sorted + up(ordered ? n * 8ull : 0ull),
+                   o_rout = o_rin + up(!ordered ? 0ull : pack ? n * 8ull : n * 4ull), o_tmp = o_rout + up(ordered && !pack ? n * 4ull : 0ull),
+                   total = o_tmp + up(sort_bytes);
+    {
+        // BRX_INDEX_SCRATCH_PAD_GB (tests): ask for that much more than needed, so that the runtime really refuses the block
+        const uint64_t pad = (uint64_t)env_int("BRX_INDEX_SCRATCH_PAD_GB", 0) << 30;
+        void *p = nullptr;
+        if (dev_alloc(&p, total + pad) != hipSuccess) {
+            // not an error of this call: the build goes the old way.  The runtime keeps the refusal as the thread's last error
+            // until somebody reads it, and the next launch that asks hipGetLastError would take it for its own.
+            (void)hipGetLastError();
+            return BRX_OK;
+        }
+        scratch.adopt((uint8_t *)p, total + pad);
+    }
+    uint32_t *const first = (uint32_t *)(scratch + o_first);
+    uint64_t *const cont_keys = (uint64_t *)(scratch + o_ckeys);
+    uint32_t *const cont_lines = (uint32_t *)(scratch + o_clines);
+    uint64_t *const sorted = (uint64_t *)(scratch + o_sorted);
+    uint32_t *const rin = (uint32_t *)(scratch + o_rin), *const rout = (uint32_t *)(scratch + o_rout);
+    uint32_t *const line_bits = (uint32_t *)(d_lines + n_lines * 8ull);
+    {
+        KernelTimer t("index_sort", s);
+        if (ordered) {
+            uint32_t blocks = (uint32_t)((n + 255) / 256);
+            index_region_of_kernel<<<blocks > 4096u ? 4096u : blocks, 256, 0, s>>>(d_keys, (uint32_t)n, line_shift, m, w, k, region_log, rin,
+                                                                                   pack ? (uint64_t *)rin : nullptr, key_bits);
+            BRX_HIP(hipGetLastError());
+            if (pack) // (`rin` has 8 bytes per key then, and the ordered words land in `sorted`)
+                BRX_HIP(rocprim::radix_sort_keys(scratch + o_tmp, sort_bytes, (const uint64_t *)rin, sorted, (uint32_t)n, key_bits,
+                                                 key_bits + sort_bits, s));
+            else
+                BRX_HIP(rocprim::radix_sort_pairs(scratch + o_tmp, sort_bytes, (const uint32_t *)rin, rout, d_keys, sorted, (uint32_t)n, 0u,
+                                                  sort_bits, s));
+        }
+        uint32_t blocks = (uint32_t)((n + 256) / 256);
+        index_region_first_kernel<<<blocks > 4096u ? 4096u : blocks, 256, 0, s>>>(ordered && !pack ? rout : nullptr, pack ? sorted : nullptr,
+                                                                                  key_bits, (uint32_t)n, n_regions, first);
+        BRX_HIP(hipGetLastError());
+    }
+    {
+        KernelTimer t("index_lines", s);
+        const uint32_t lds = 64u << region_log;
+        const uint32_t grid = n_regions < 2048u ? n_regions : 2048u;
+        const uint64_t *const in = ordered ? sorted : d_keys;
+        const uint64_t key_mask = pack ? (1ull << key_bits) - 1ull : ~0ull;
+        if (lds > 65536u) {
+            BRX_HIP(hipFuncSetAttribute((const void *)index_lines_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            BRX_HIP(hipFuncSetAttribute((const void *)index_lines_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        }
+        if (chain)
+            index_lines_kernel<true><<<grid, IDX_LINES_THREADS, lds, s>>>(in, key_mask, first, n_regions, region_log, d_lines, line_shift, m, w, k, d_counts,
+                                                                         line_bits, cont_keys, cont_lines, d_counts + 1, cont_cap);
+        else
+            index_lines_kernel<false><<<grid, IDX_LINES_THREADS, lds, s>>>(in, key_mask, first, n_regions, region_log, d_lines, line_shift, m, w, k, d_counts,
+                                                                          line_bits, nullptr, nullptr, d_counts + 1, 0);
+        BRX_HIP(hipGetLastError());
+    }
+    if (chain && n) {
+        KernelTimer t("index_insert", s);
+        const uint64_t blocks = (cont_cap + 255) / 256;
+        index_insert_kernel<true><<<(int)(blocks > 1024 ? 1024 : blocks), 256, 0, s>>>(cont_keys, cont_cap, d_lines, line_shift, m, w, k, d_counts,
+                                                                                       line_bits, cont_lines, d_counts + 1);
+        BRX_HIP(hipGetLastError());
+    }
+    done = true;
+    return BRX_OK;
+}
+
 static int index_build_locked(brx_set *set, const uint64_t *d_keys, uint64_t n, int m, int log_lines, hipStream_t s)
 {
     const int k = set->k;
@@ -201,33 +466,57 @@ static int index_build_locked(brx_set *set, const uint64_t *d_keys, uint64_t n, 
         BRX_TRY(set->d_lines.reserve_bytes(n_lines * 64ull + n_lines / 8ull + 64ull, 0, "probe index")); // lines + occupancy bits
         set->lines_alloc = n_lines;
     }
-    DevBuf<unsigned long long> d_ovf;
-    BRX_TRY(d_ovf.reserve(1, 0, "probe index build"));
-    BRX_HIP(hipMemsetAsync(d_ovf, 0, 8, s));
-    {
-        KernelTimer t("index_zero", s);
-        BRX_HIP(hipMemsetAsync(set->d_lines, 0, n_lines * 64ull + n_lines / 8ull + 64ull, s));
+    DevBuf<unsigned long long> d_ovf; // [0] keys turned away by their home line, [1] keys whose chain left its region
+    BRX_TRY(d_ovf.reserve(2, 0, "probe index build"));
+    BRX_HIP(hipMemsetAsync(d_ovf, 0, 16, s));
+    uint32_t *const line_bits = (uint32_t *)(set->d_lines + n_lines * 8ull);
+    const uint32_t line_shift = 32u - (uint32_t)log_lines, w = (uint32_t)(k - m + 1);
+    unsigned long long ovf[2] = {0, 0};
+    bool by_regions = false;
+    uint64_t cont_cap = 0;
+    DevBuf<uint8_t> scratch; // (freed behind the synchronisation below)
+    const bool want_regions = env_int("BRX_INDEX_BUILD", 1) != 0;
+    if (want_regions) {
+        const int st = index_build_regions(d_keys, n, set->d_lines, log_lines, (uint32_t)m, w, k, no_bits(set), d_ovf, s, scratch, by_regions, cont_cap);
+        if (st != BRX_OK) {
+            (void)hipStreamSynchronize(s); // (kernels already queued may still use `scratch` and d_ovf)
+            return st;
+        }
     }
-    if (n) {
-        KernelTimer t("index_insert", s);
-        uint64_t blocks = (n + 255) / 256;
-        if (blocks > 256 * 16)
-            blocks = 256 * 16;
-        if (no_bits(set))
-            index_insert_kernel<true><<<(int)blocks, 256, 0, s>>>(d_keys, n, set->d_lines, 32u - (uint32_t)log_lines, (uint32_t)m,
-                                                                  (uint32_t)(k - m + 1), k, d_ovf, (uint32_t *)(set->d_lines + n_lines * 8ull));
-        else
-            index_insert_kernel<false><<<(int)blocks, 256, 0, s>>>(d_keys, n, set->d_lines, 32u - (uint32_t)log_lines, (uint32_t)m,
-                                                                   (uint32_t)(k - m + 1), k, d_ovf, (uint32_t *)(set->d_lines + n_lines * 8ull));
-        BRX_HIP(hipGetLastError());
+    if (by_regions) {
+        BRX_HIP(hipMemcpyAsync(ovf, d_ovf, 16, hipMemcpyDeviceToHost, s));
+        BRX_HIP(hipStreamSynchronize(s));
+        if (ovf[1] > cont_cap) { // more chains left their regions than the list holds: the table lacks those keys
+            by_regions = false;
+            BRX_HIP(hipMemsetAsync(d_ovf, 0, 16, s));
+        } else if (env_int("BRX_INDEX_TRACE", 0)) {
+            fprintf(stderr, "brx index build: 2^%d lines, %llu keys, %llu turned away by their home line, %llu left their region\n",
+                    log_lines, (unsigned long long)n, ovf[0], ovf[1]);
+        }
     }
-    unsigned long long ovf = 0;
-    BRX_HIP(hipMemcpyAsync(&ovf, d_ovf, 8, hipMemcpyDeviceToHost, s));
-    BRX_HIP(hipStreamSynchronize(s));
+    if (!by_regions) { // BRX_INDEX_BUILD=0, or no scratch for the ordered keys: clear the table, then one key at a time
+        {
+            KernelTimer t("index_zero", s);
+            BRX_HIP(hipMemsetAsync(set->d_lines, 0, n_lines * 64ull + n_lines / 8ull + 64ull, s));
+        }
+        if (n) {
+            KernelTimer t("index_insert", s);
+            uint64_t blocks = (n + 255) / 256;
+            if (blocks > 256 * 16)
+                blocks = 256 * 16;
+            if (no_bits(set))
+                index_insert_kernel<true><<<(int)blocks, 256, 0, s>>>(d_keys, n, set->d_lines, line_shift, (uint32_t)m, w, k, d_ovf, line_bits);
+            else
+                index_insert_kernel<false><<<(int)blocks, 256, 0, s>>>(d_keys, n, set->d_lines, line_shift, (uint32_t)m, w, k, d_ovf, line_bits);
+            BRX_HIP(hipGetLastError());
+        }
+        BRX_HIP(hipMemcpyAsync(ovf, d_ovf, 8, hipMemcpyDeviceToHost, s));
+        BRX_HIP(hipStreamSynchronize(s));
+    }
     set->idx_log_lines = (uint32_t)log_lines;
     set->idx_m = (uint32_t)m;
     set->idx_keys = n;
-    set->idx_overflow_keys = ovf;
+    set->idx_overflow_keys = ovf[0];
     set->idx_exact = no_bits(set);
     set->idx_open = false;
     set->idx_linebits = true; // this build filled the occupancy bits behind the lines

@@ -188,6 +188,8 @@ while time.time() < t_end:
     env["BRX_READ_GRID"] = str(xrng.choice(["", "1", "5"]))
     # trigger-free rounds of the 64-lane reverse scans in blocks through the occupancy bits (round 8): on (default) / off
     env["BRX_REV_BATCH"] = str(xrng.choice(["", "", "", "0"]))
+    # the probe index built by regions (round 9): on (default) / off = clear the table and insert key by key, the comparison
+    env["BRX_INDEX_BUILD"] = str(xrng.choice(["", "", "0"]))
     if focus == "walklane":
         names[-1] = str(frng.choice(["graph", "gap_size"]))
         env.update({"BRX_LANE": "", "BRX_LANE_WALK": "", "BRX_LANE_CHUNK": str(frng.choice(["64", "100"])),
