@@ -112,7 +112,10 @@ SIGNATURES = {
     "brx_counter_floor": (C.c_int, [_vp, _u8p]),
     "brx_set_save_fd": (C.c_int, [_vp, C.c_int, _u64p]),
     "brx_set_load_fd": (C.c_int, [C.c_int, C.c_int, _pp, _u64p]),
-    "brx_comm_unique_id": (C.c_int, [_vp]),
+    "brx_keys_combine_device": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_int, _vp, C.c_uint64, _u64p, _u64p, _vp]),
+    "brx_set_combine": (C.c_int, [_vp, _vp, C.c_int, _pp, _u64p]),
+    "brx_set_compare": (C.c_int, [_vp, _vp, _u64p]),
+    "brx_comm_unique_id":(C.c_int, [_vp]),
     "brx_comm_init": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _pp]),
     "brx_comm_init_all": (C.c_int, [C.c_int, C.POINTER(C.c_int), _pp]),
     "brx_comm_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -35,6 +35,14 @@ Not in the reference, like `--device` (include/brx.h "coverage"; a base is cover
                                k, and with --abundance-report, it counts into the hash table: the same set, the same file
     --save-min-count N         keep only the k-mers counted at least N times (default 1) in --save-counts.  A counter loaded
                                from such a file no longer knows the rarer k-mers: thresholds below N - 1 are refused
+    --set-or PATH | --set-and PATH | --set-minus PATH
+                               combine the set the sub-command built with the set in PATH -- add its k-mers, keep only the
+                               k-mers also in it, remove its k-mers (br_amd/setops.py) -- before --save-set and before the
+                               correction.  Each is repeatable; they are applied left to right in command-line order.  PATH is
+                               a key file (set or count file, the counts are ignored) or a .solid stream, gz / bz2 / xz
+                               sniffed, of the same k as the set in use:
+                                 python -m br_amd -i reads.fa -o corr.fa --set-or illumina.keys --set-minus mito.keys \
+                                     --save-set final.keys -c one fasta -i reads.fa -k 21 -a 3
     --second-pass MODE         reverse (default: the reference's second scan, reads reversed and not complemented),
                                revcomp (the second scan on the reverse complement: br_amd/strand.py) or none (= -s)
 """
@@ -122,6 +130,41 @@ def second_pass_of(args) -> str:
     return strand.resolve_second_pass(args.second_pass, args.two_side)
 
 
+SET_FLAGS = {"--set-or": "union", "--set-and": "intersection", "--set-minus": "difference"}
+
+
+class SetOpAction(argparse.Action):
+    """--set-or / --set-and / --set-minus PATH: (operation, flag, path) appended to ONE list, args.set_ops, so that the
+    order of the command line is the order they are applied in"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        ops = list(getattr(namespace, self.dest, None) or [])
+        ops.append((SET_FLAGS[option_string], option_string, values))
+        setattr(namespace, self.dest, ops)
+
+
+def load_operand(path: str, dev: int) -> Pcon:
+    """the set of a --set-* operand: a key file (told by its magic after decompression; the counts of a count file are
+    ignored) or else a .solid stream"""
+    with open_input(path) as f:
+        if keyfile.is_keyfile(f.peek(8)[:8]):
+            return Pcon.from_keyfile(f, dev)
+        return Pcon.from_pcon_solid(f.read(), dev)
+
+
+def apply_set_ops(kmer_set: Pcon, set_ops, dev: int) -> Pcon:
+    """the set in use combined with every operand, left to right"""
+    for name, flag, path in set_ops or []:
+        try:
+            other = load_operand(path, dev)
+            if other.k() != kmer_set.k():
+                raise SystemExit("Error: %s %s: k = %d, the set in use has k = %d" % (flag, path, other.k(), kmer_set.k()))
+            kmer_set = kmer_set.combine(other, name)
+        except (_lib.BrxError, OSError) as e:
+            raise SystemExit(f"Error: {flag} {path}: {e}")
+    return kmer_set
+
+
 def open_input(path: str) -> BinaryIO:
     """niffler::get_reader: sniff gz / bz2 / xz by magic bytes (src/cli.rs:209,269,404,415)."""
     raw = open(path, "rb")
@@ -170,6 +213,11 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--save-set", default=None, metavar="PATH",
                    help="write the set in use as a key file before the correction starts; `solid -i PATH -f keys` loads it "
                         "(not in the reference)")
+    for flag, what in (("--set-or", "add the k-mers of"), ("--set-and", "keep only the k-mers also in"),
+                       ("--set-minus", "remove the k-mers of")):
+        p.add_argument(flag, action=SetOpAction, dest="set_ops", default=None, metavar="PATH",
+                       help=what + " the set in PATH (a key file or a .solid stream of the same k) before --save-set and the "
+                            "correction; repeatable, applied in command-line order (not in the reference)")
     p.add_argument("--save-counts", default=None, metavar="PATH",
                    help="write the k-mer counts as a key file; with `fasta` or `count` only; `count -i PATH` loads it.  `fasta` "
                         "then counts into the hash table (BRX_COUNT_TABLE), except at 15 <= k <= 21 without --abundance-report, "
@@ -352,6 +400,8 @@ def main(argv: Optional[List[str]] = None) -> int:
             with open_input(src) as f, open(dst, "wb") as rep:
                 write_abundance_report(kept["counter"], kept["threshold"], f, rep, args.record_buffer or 8192)
         kept.clear()  # (the counter's memory goes back before the correction starts)
+    if args.set_ops:
+        kmer_set = apply_set_ops(kmer_set, args.set_ops, args.device)
     if args.save_set is not None:
         with open(args.save_set, "wb") as f:
             kmer_set.save_keys(f)

@@ -380,7 +380,7 @@ int tab_finish_into(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set *
                                                                          dst->d_bits, dst->nwords * 32);
         BRX_HIP(hipGetLastError());
     }
-    dst->keylist_valid = list; // (nothing counted: the empty list)
+    keylist_mark(dst, list); // (nothing counted: the empty list)
     trace_stage(s, "table select");
     return BRX_OK;
 }

@@ -598,7 +598,7 @@ int index_insert_reads(brx_set *set, const uint8_t *d_bases, const uint64_t *d_o
     set->idx_open = true;
     set->idx_valid = true;
     set->idx_gen++;
-    set->keylist_valid = false; // the table is the set now
+    keylist_mark(set, false); // the table is the set now
     return BRX_OK;
 }
 
@@ -699,7 +699,7 @@ int brx_set_index_build_from_keys_device(brx_set_t *set, const uint64_t *d_keys,
         return BRX_ERR_ARG;
     int st = index_build_from_keys(set, d_keys, n, m, log2_lines, (hipStream_t)stream);
     if (st == BRX_OK && no_bits(set) && d_keys != set->d_keylist)
-        set->keylist_valid = false; // without a bit vector the list just given IS the set now (multi-GPU exchange)
+        keylist_mark(set, false); // without a bit vector the list just given IS the set now (multi-GPU exchange)
     return st;
 }
 

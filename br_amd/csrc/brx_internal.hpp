@@ -125,6 +125,9 @@ struct brx_set {
     brx::DevBuf<uint64_t> d_keylist;             // (its cap(): entries)
     brx::DevBuf<unsigned long long> d_keylist_n; // device counter (may exceed the list's capacity: list truncated)
     bool keylist_valid;
+    // the valid key list is known to ascend strictly (it came from a key file or from set algebra): listing it needs no
+    // sort.  Written through keylist_mark alone, which every site that validates or drops the list calls.
+    bool keylist_sorted = false;
     std::mutex idx_mu;
 };
 
@@ -148,7 +151,9 @@ inline bool no_bits(const brx_set *set) { return set->sparse || set->bits_stale;
 int ensure_bits(const brx_set *set, hipStream_t s, const char *what);
 // builds the index from the bitset when the set has none (no-op for k outside the indexed range)
 int index_ensure(const brx_set *set, hipStream_t s);
-inline void index_invalidate(brx_set *set) { set->idx_valid = false; set->idx_declined = false; set->keylist_valid = false; }
+// the one place keylist_valid is written: a list is in order only where its writer says so
+inline void keylist_mark(brx_set *set, bool valid, bool sorted = false) { set->keylist_valid = valid; set->keylist_sorted = valid && sorted; }
+inline void index_invalidate(brx_set *set) { set->idx_valid = false; set->idx_declined = false; keylist_mark(set, false); }
 int index_auto_m(int k, uint64_t n_keys);
 bool index_wanted(int k);
 }
@@ -231,6 +236,18 @@ uint8_t tab_floor(const brx_counter *c);
 void tab_set_floor(brx_counter *c, uint8_t floor);
 int tab_info(brx_counter *c, uint64_t *info4, hipStream_t s);
 int set_alloc_unwritten(int k, int device, brx_set **out);
+// What set algebra (brx_setops.hip) shares with the key files (brx_keyfile.hip).  keys_scan_exclusive: d_data[0 .. n) in
+// place, d_sums holds keys_scan_sums(n) + 1 entries and the last one receives the total.  keys_sort: brx_sort_keys_device.
+// set_list_keys: the keys of a set, whatever holds it, into d_out, *sorted telling whether they are known to ascend (a key
+// list marked so); the set is only read, a lazy bit vector stays lazy.  set_build_from_keys: makes a set_alloc_unwritten set the closed set of n sorted keys -- d_keys (exactly n entries,
+// empty for n = 0) becomes its key list, a sparse set builds its chained index, the others write their bits and keep the
+// list where index_wanted(k); `me` names the entry in messages.  keys_sort and set_build_from_keys return after `s` has been
+// synchronised; set_list_keys leaves its copy queued on `s`.
+uint64_t keys_scan_sums(uint64_t n);
+int keys_scan_exclusive(unsigned long long *d_data, uint64_t n, unsigned long long *d_sums, hipStream_t s);
+int keys_sort(uint64_t *d_keys, uint8_t *d_pay, uint64_t n, uint32_t key_bits, hipStream_t s);
+int set_list_keys(const brx_set *set, hipStream_t s, DevBuf<uint64_t> &d_out, uint64_t *n_out, bool *sorted);
+int set_build_from_keys(brx_set *set, DevBuf<uint64_t> &d_keys, uint64_t n, hipStream_t s, const char *me);
 void tab_set_merged(brx_counter *c, int world, int rank);
 bool tab_merged(const brx_counter *c, int *world, int *rank);
 int tab_reset(brx_counter *c, hipStream_t s);

@@ -1158,12 +1158,15 @@ int list_view(const brx_counter *c, uint8_t floor, hipStream_t s, DevScratch &ws
     return BRX_OK;
 }
 
-// the keys of a set, whatever holds it, into d_out; a lazy bit vector stays lazy
-int list_set(const brx_set *cset, hipStream_t s, DevBuf<uint64_t> &d_out, uint64_t *n_out)
+// the keys of a set, whatever holds it, into d_out; a lazy bit vector stays lazy.  *sorted (may be null): the keys are known
+// to ascend strictly -- they are a key list that says so (brx_set::keylist_sorted)
+int list_set(const brx_set *cset, hipStream_t s, DevBuf<uint64_t> &d_out, uint64_t *n_out, bool *sorted = nullptr)
 {
     brx_set *set = const_cast<brx_set *>(cset);
     d_out.reset();
     *n_out = 0;
+    if (sorted)
+        *sorted = false;
     {
         std::lock_guard<std::mutex> g(set->idx_mu);
         if (set->keylist_valid) {
@@ -1171,6 +1174,8 @@ int list_set(const brx_set *cset, hipStream_t s, DevBuf<uint64_t> &d_out, uint64
             BRX_HIP(hipMemcpyAsync(&nl, set->d_keylist_n, 8, hipMemcpyDeviceToHost, s));
             BRX_HIP(hipStreamSynchronize(s));
             if (nl <= set->d_keylist.cap()) { // (a truncated list is no list)
+                if (sorted)
+                    *sorted = set->keylist_sorted;
                 if (nl) {
                     BRX_TRY(d_out.reserve(nl, 0, "keys of the set"));
                     KernelTimer kt("key_list", s);
@@ -1225,6 +1230,38 @@ int list_set(const brx_set *cset, hipStream_t s, DevBuf<uint64_t> &d_out, uint64
 }
 
 } // namespace
+
+// ---- what set algebra (brx_setops.hip) shares with the key files ------------------------------------------------------------
+namespace brx {
+
+uint64_t keys_scan_sums(uint64_t n) { return (n + SCAN_CHUNK - 1) / SCAN_CHUNK; }
+int keys_scan_exclusive(unsigned long long *d_data, uint64_t n, unsigned long long *d_sums, hipStream_t s) { return scan_exclusive(d_data, n, d_sums, s); }
+int keys_sort(uint64_t *d_keys, uint8_t *d_pay, uint64_t n, uint32_t key_bits, hipStream_t s) { return sort_pairs(d_keys, d_pay, n, key_bits, s); }
+int set_list_keys(const brx_set *set, hipStream_t s, DevBuf<uint64_t> &d_out, uint64_t *n_out, bool *sorted) { return list_set(set, s, d_out, n_out, sorted); }
+
+int set_build_from_keys(brx_set *set, DevBuf<uint64_t> &d_keys, uint64_t n_keys, hipStream_t s, const char *me)
+{
+    // the keys become the set's key list: what a finish leaves
+    BRX_TRY(set->d_keylist_n.reserve(1, 0, "key list counter"));
+    const u64 n = n_keys;
+    BRX_HIP(hipMemcpyAsync(set->d_keylist_n, &n, 8, hipMemcpyHostToDevice, s));
+    BRX_HIP(hipStreamSynchronize(s));
+    set->d_keylist = std::move(d_keys);
+    keylist_mark(set, true, true); // (in order: the next listing needs no sort)
+    if (set->sparse) {
+        BRX_TRY(index_build_from_keys(set, set->d_keylist, n_keys, 0, 0, s));
+    } else {
+        set->bits_stale = true; // (nothing written yet)
+        BRX_TRY(ensure_bits(set, s, me));
+        if (!index_wanted(set->k)) { // as after a finish at this k: the bits are the set
+            keylist_mark(set, false);
+            set->d_keylist.reset();
+        }
+    }
+    return BRX_OK;
+}
+
+} // namespace brx
 
 extern "C" {
 
@@ -1454,30 +1491,12 @@ int brx_set_load_fd(int in_fd, int device, brx_set_t **out, uint64_t *stats8)
     int st = read_blocks(in_fd, h, false, s, d_keys, d_cnts, st8); // (the counts of a count file are checked and dropped)
     if (st == BRX_OK)
         st = set_alloc_unwritten(h.k, device, &set);
-    auto build = [&]() -> int {
+    if (st == BRX_OK) {
         auto t1 = Clock::now();
-        // the keys become the set's key list: what a finish leaves
-        BRX_TRY(set->d_keylist_n.reserve(1, 0, "key list counter"));
-        const u64 n = h.n;
-        BRX_HIP(hipMemcpyAsync(set->d_keylist_n, &n, 8, hipMemcpyHostToDevice, s));
-        BRX_HIP(hipStreamSynchronize(s));
-        set->d_keylist = std::move(d_keys);
-        set->keylist_valid = true;
-        if (set->sparse) {
-            BRX_TRY(index_build_from_keys(set, set->d_keylist, h.n, 0, 0, s));
-        } else {
-            set->bits_stale = true; // (nothing written yet)
-            BRX_TRY(ensure_bits(set, s, me));
-            if (!index_wanted(set->k)) { // as after a finish at this k: the bits are the set
-                set->keylist_valid = false;
-                set->d_keylist.reset();
-            }
-        }
-        st8[4] = ns_since(t1);
-        return BRX_OK;
-    };
-    if (st == BRX_OK)
-        st = build();
+        st = set_build_from_keys(set, d_keys, h.n, s, me);
+        if (st == BRX_OK)
+            st8[4] = ns_since(t1);
+    }
     (void)hipStreamSynchronize(s);
     (void)hipStreamDestroy(s);
     if (st != BRX_OK) {

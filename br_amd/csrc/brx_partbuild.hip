@@ -2233,7 +2233,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
         if (dst->sparse) {
             BRX_TRY(dst->d_keylist_n.reserve(1, 0, "key list counter"));
             BRX_HIP(hipMemsetAsync(dst->d_keylist_n, 0, 8, s));
-            dst->keylist_valid = true; // the empty list
+            keylist_mark(dst, true); // the empty list
         } else {
             BRX_HIP(hipMemsetAsync(dst->d_bits, 0, dst->nwords * 4, s));
             dst->bits_stale = false;
@@ -2348,7 +2348,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
         }
         BRX_HIP(hipGetLastError());
         trace_stage(s, "hash final");
-        dst->keylist_valid = true;
+        keylist_mark(dst, true);
         dst->bits_stale = lazy;
         return BRX_OK;
     }
@@ -2394,7 +2394,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
     }
     BRX_HIP(hipGetLastError());
     trace_stage(s, "final count");
-    dst->keylist_valid = emit;
+    keylist_mark(dst, emit);
     dst->bits_stale = lazy;
     return BRX_OK;
 }

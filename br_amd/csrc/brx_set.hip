@@ -310,7 +310,7 @@ int alloc_set(int k, int device, bool zero, brx_set **out, bool sparse = false)
             delete s;
             return BRX_ERR_NOMEM;
         }
-        s->keylist_valid = true;
+        keylist_mark(s, true);
         *out = s;
         return BRX_OK;
     }

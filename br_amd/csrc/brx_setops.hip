@@ -1,0 +1,510 @@
+// Set algebra (include/brx.h "set algebra", br_amd/setops.py states it in numpy): union, intersection, difference and
+// symmetric difference of two strictly ascending lists of u64 keys, by merge path.
+//
+//   tiles    position d of the merged sequence (ties: the key of A before the equal key of B) is reached after a(d) keys of
+//            A and d - a(d) keys of B; a(d) is found by a binary search on the diagonal d.  A tile is MERGE_TILE consecutive
+//            positions; merge_split_kernel finds a() at every tile border, once, for both passes.  The search keeps
+//            max(0, d - nb) <= a <= min(d, na) whatever the keys hold, and every index it reads lies inside that bracket.
+//   a tile   its piece of A and its piece of B go to LDS with one key before and one key behind each (the halo).  Thread t
+//            finds a() of its own diagonal, MERGE_PER_THREAD * t positions into the tile, by the same search in LDS, and
+//            merges MERGE_PER_THREAD keys serially.
+//   members  with ties A-first, A[i] is in B iff the first unconsumed B[j] equals it (j may be the halo behind the piece),
+//            and B[j] is in A iff i > 0 and A[i - 1] equals it (i - 1 may be the halo before the piece): no thread asks
+//            another one.  An operation is a keep rule over those two bits (KEEP_A / KEEP_B below).
+//   pass 1   merge_count_kernel: kept keys per tile, |A n B| summed with one atomic per tile, and the contract checked --
+//            every neighbouring pair of either list, the halo pairs included, must ascend strictly, and the borders must not
+//            run backwards (they cannot over ascending lists); otherwise the error bit is set and nothing is written.
+//   scan     the existing exclusive scan turns the tile counts into offsets, its total is the size of the result.
+//   pass 2   merge_write_kernel: the same merge, the kept keys compacted in LDS by a block scan of the threads' counts,
+//            then stored as one contiguous run per tile, 256 neighbouring keys per step.
+// The three launches share the profile timer "set_merge".  Blocks loop over tiles; the grid cap is read_grid()'s.
+#include "brx_internal.hpp"
+
+#include <chrono>
+#include <string.h>
+
+using namespace brx;
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr uint32_t MERGE_PER_THREAD = 8;                   // (br_amd/setops.py PER_THREAD)
+constexpr uint32_t MERGE_TILE = 256u * MERGE_PER_THREAD;   // (br_amd/setops.py TILE)
+constexpr uint32_t ERR_ORDER = 1u;
+
+// bit 0: keep a key that the other list lacks, bit 1: keep a key that the other list holds too
+constexpr uint32_t KEEP_A[4] = {3u, 2u, 1u, 1u}; // union, intersection, difference, symmetric difference
+constexpr uint32_t KEEP_B[4] = {1u, 0u, 0u, 1u};
+
+typedef std::chrono::steady_clock Clock;
+uint64_t ns_since(Clock::time_point t0) { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - t0).count(); }
+
+// keys of `a` among the first d of the merge of a[0 .. na) and b[0 .. nb), d <= na + nb.  lo <= mid < hi <= min(d, na) and
+// 0 <= d - 1 - mid < nb hold from the bracket alone: nothing read decides where the next read goes beyond it.
+template <typename T> __device__ __forceinline__ T merge_split(const u64 *a, T na, const u64 *b, T nb, T d)
+{
+    T lo = d > nb ? d - nb : 0, hi = d < na ? d : na;
+    while (lo < hi) {
+        const T mid = lo + (hi - lo) / 2;
+        if (a[mid] <= b[d - 1 - mid])
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// split[t] = keys of A before tile t, t = 0 .. n_tiles (the last one: na)
+__global__ __launch_bounds__(256) void merge_split_kernel(const u64 *__restrict__ a, uint64_t na, const u64 *__restrict__ b, uint64_t nb,
+                                                          uint64_t n_tiles, u64 *__restrict__ split)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, n = na + nb;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t <= n_tiles; t += stride) {
+        const uint64_t d = t * MERGE_TILE < n ? t * MERGE_TILE : n;
+        split[t] = merge_split<uint64_t>(a, na, b, nb, d);
+    }
+}
+
+// The pieces of tile t in LDS and each thread's share of the merge.
+struct Tile {
+    uint64_t a0, b0;  // where the pieces start in A and B
+    uint32_t la, lb;  // their lengths, la + lb <= MERGE_TILE
+    bool ok;          // the borders run forward
+};
+
+// sa / sb: MERGE_TILE + 2 entries each; entry 1 + x = key x of the piece, entry 0 and entry 1 + length the halo (left
+// unwritten where the list ends there: the merge asks the global index before it reads them)
+__device__ __forceinline__ Tile tile_load(const u64 *__restrict__ a, uint64_t na, const u64 *__restrict__ b, uint64_t nb,
+                                          const u64 *__restrict__ split, uint64_t t, u64 *sa, u64 *sb)
+{
+    const uint64_t n = na + nb;
+    const uint64_t d0 = t * MERGE_TILE, d1 = d0 + MERGE_TILE < n ? d0 + MERGE_TILE : n; // (d0 < n: t < n_tiles)
+    const uint64_t a0 = split[t], a1 = split[t + 1];
+    Tile tl;
+    // (a0 <= d0 and a1 <= d1 by the search's bracket; over lists that do not ascend a border may still run backwards)
+    tl.ok = a0 <= d0 && a1 <= d1 && a0 <= na && a1 <= na && a1 >= a0 && d1 - a1 >= d0 - a0 && d1 - a1 <= nb;
+    tl.a0 = tl.ok ? a0 : 0;
+    tl.b0 = tl.ok ? d0 - a0 : 0;
+    tl.la = tl.ok ? (uint32_t)(a1 - a0) : 0u; // la + lb = d1 - d0 <= MERGE_TILE, both >= 0
+    tl.lb = tl.ok ? (uint32_t)((d1 - a1) - (d0 - a0)) : 0u;
+    if (tl.ok) {
+        for (uint32_t x = threadIdx.x; x < tl.la + 2u; x += 256u) {
+            const uint64_t i = tl.a0 + x; // global index + 1
+            if (i >= 1 && i <= na)
+                sa[x] = a[i - 1];
+        }
+        for (uint32_t x = threadIdx.x; x < tl.lb + 2u; x += 256u) {
+            const uint64_t j = tl.b0 + x;
+            if (j >= 1 && j <= nb)
+                sb[x] = b[j - 1];
+        }
+    }
+    __syncthreads();
+    return tl;
+}
+
+// Thread's MERGE_PER_THREAD positions of the tile: key[q], keep bit q of the result; *both = keys of A found in B.
+__device__ __forceinline__ uint32_t tile_merge(const Tile &tl, uint64_t na, uint64_t nb, const u64 *sa, const u64 *sb, uint32_t keep_a,
+                                               uint32_t keep_b, u64 key[MERGE_PER_THREAD], uint32_t *both)
+{
+    const uint32_t len = tl.la + tl.lb;
+    const uint32_t d = threadIdx.x * MERGE_PER_THREAD < len ? threadIdx.x * MERGE_PER_THREAD : len;
+    uint32_t i = merge_split<uint32_t>(sa + 1, tl.la, sb + 1, tl.lb, d), j = d - i;
+    uint32_t keep = 0, nboth = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < MERGE_PER_THREAD; q++) {
+        key[q] = 0;
+        if (d + q >= len)
+            continue;
+        // (i + j = d + q < la + lb: at least one piece has a key left)
+        const bool take_a = i < tl.la && (j >= tl.lb || sa[1 + i] <= sb[1 + j]);
+        if (take_a) {
+            const u64 x = sa[1 + i];
+            const bool in_b = tl.b0 + j < nb && sb[1 + j] == x; // (j == lb: the halo behind the piece)
+            key[q] = x;
+            keep |= ((keep_a >> (in_b ? 1u : 0u)) & 1u) << q;
+            nboth += in_b ? 1u : 0u;
+            i++;
+        } else {
+            const u64 x = sb[1 + j];
+            const bool in_a = tl.a0 + i > 0 && sa[i] == x; // (i == 0: the halo before the piece)
+            key[q] = x;
+            keep |= ((keep_b >> (in_a ? 1u : 0u)) & 1u) << q;
+            j++;
+        }
+    }
+    *both = nboth;
+    return keep;
+}
+
+// sum of x over the block into every thread; sh holds 4 entries
+__device__ __forceinline__ uint32_t block_sum(uint32_t x, uint32_t *sh)
+{
+    for (int o = 32; o > 0; o >>= 1)
+        x += __shfl_xor(x, o);
+    __syncthreads(); // (sh may still be read from the trip before)
+    if ((threadIdx.x & 63u) == 0u)
+        sh[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+// ctl[0] += |A n B| of the tile, ctl[1] |= ERR_ORDER
+__global__ __launch_bounds__(256) void merge_count_kernel(const u64 *__restrict__ a, uint64_t na, const u64 *__restrict__ b, uint64_t nb,
+                                                          const u64 *__restrict__ split, uint64_t n_tiles, uint32_t keep_a, uint32_t keep_b,
+                                                          u64 *__restrict__ counts, u64 *__restrict__ ctl)
+{
+    __shared__ u64 sa[MERGE_TILE + 2], sb[MERGE_TILE + 2];
+    __shared__ uint32_t sh[4];
+    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) { // block-uniform
+        const Tile tl = tile_load(a, na, b, nb, split, t, sa, sb);
+        uint32_t bad = tl.ok ? 0u : 1u;
+        for (uint32_t x = threadIdx.x; x < tl.la; x += 256u)
+            if (tl.a0 + x > 0 && sa[x] >= sa[1 + x]) // (x == 0: against the halo)
+                bad = 1u;
+        for (uint32_t x = threadIdx.x; x < tl.lb; x += 256u)
+            if (tl.b0 + x > 0 && sb[x] >= sb[1 + x])
+                bad = 1u;
+        u64 key[MERGE_PER_THREAD];
+        uint32_t both = 0;
+        const uint32_t keep = tile_merge(tl, na, nb, sa, sb, keep_a, keep_b, key, &both);
+        const uint32_t kept = block_sum((uint32_t)__popc(keep), sh);
+        const uint32_t n_both = block_sum(both, sh);
+        const uint32_t n_bad = block_sum(bad, sh);
+        if (threadIdx.x == 0) {
+            counts[t] = kept;
+            if (n_both)
+                atomicAdd(&ctl[0], (u64)n_both);
+            if (n_bad)
+                atomicOr(&ctl[1], (u64)ERR_ORDER);
+        }
+        __syncthreads(); // (the pieces are written again in the next trip)
+    }
+}
+
+// offs: the scanned counts.  Runs only after pass 1 has found both lists in order.
+__global__ __launch_bounds__(256) void merge_write_kernel(const u64 *__restrict__ a, uint64_t na, const u64 *__restrict__ b, uint64_t nb,
+                                                          const u64 *__restrict__ split, uint64_t n_tiles, uint32_t keep_a, uint32_t keep_b,
+                                                          const u64 *__restrict__ offs, u64 *__restrict__ out, uint64_t n_out)
+{
+    __shared__ u64 sa[MERGE_TILE + 2], sb[MERGE_TILE + 2], so[MERGE_TILE];
+    __shared__ uint32_t sh[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) { // block-uniform
+        const Tile tl = tile_load(a, na, b, nb, split, t, sa, sb);
+        u64 key[MERGE_PER_THREAD];
+        uint32_t both = 0;
+        const uint32_t keep = tile_merge(tl, na, nb, sa, sb, keep_a, keep_b, key, &both);
+        // the thread's place among the kept keys of the tile: a wave scan, then the waves before
+        const uint32_t mine = (uint32_t)__popc(keep);
+        uint32_t inc = mine;
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(inc, o);
+            if (lane >= (uint32_t)o)
+                inc += y;
+        }
+        if (lane == 63u)
+            sh[wave] = inc;
+        __syncthreads();
+        uint32_t at = inc - mine;
+        for (uint32_t w = 0; w < wave; w++)
+            at += sh[w];
+        const uint32_t total = sh[0] + sh[1] + sh[2] + sh[3]; // <= MERGE_TILE: a bit per position
+#pragma unroll
+        for (uint32_t q = 0; q < MERGE_PER_THREAD; q++)
+            if ((keep >> q) & 1u)
+                so[at++] = key[q];
+        __syncthreads();
+        const uint64_t base = offs[t];
+        for (uint32_t x = threadIdx.x; x < total; x += 256u)
+            if (base + x < n_out) // (always: the counts were taken over the same keys)
+                out[base + x] = so[x];
+        __syncthreads(); // (the pieces, so and sh are written again in the next trip)
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------
+// Pass 1 and the scan of one combine; the scratch lives until the plan goes.
+struct MergePlan {
+    DevScratch ws;
+    const u64 *d_a = nullptr, *d_b = nullptr;
+    uint64_t na = 0, nb = 0, n_tiles = 0, total = 0, both = 0;
+    int op = 0;
+    u64 *d_split = nullptr, *d_counts = nullptr;
+};
+
+// *plan: the size of the result and |A n B|; BRX_ERR_ARG when a list does not ascend strictly.  Returns after `s` has been
+// synchronised.
+int merge_count(const char *me, const uint64_t *d_a, uint64_t na, const uint64_t *d_b, uint64_t nb, int op, hipStream_t s, MergePlan *plan)
+{
+    if (op < 0 || op > 3) {
+        set_error("%s: op=%d (BRX_SETOP_UNION 0, INTERSECT 1, DIFFERENCE 2, SYMDIFF 3)", me, op);
+        return BRX_ERR_ARG;
+    }
+    if ((!d_a && na) || (!d_b && nb) || na > (1ull << 62) || nb > (1ull << 62)) {
+        set_error("%s: null keys, or more than 2^62 of them", me);
+        return BRX_ERR_ARG;
+    }
+    plan->d_a = (const u64 *)d_a;
+    plan->d_b = (const u64 *)d_b;
+    plan->na = na;
+    plan->nb = nb;
+    plan->op = op;
+    const uint64_t n_tiles = (na + nb + MERGE_TILE - 1) / MERGE_TILE;
+    plan->n_tiles = n_tiles;
+    if (!n_tiles)
+        return BRX_OK;
+    const uint64_t n_sums = keys_scan_sums(n_tiles);
+    u64 *d_sums = nullptr, *d_ctl = nullptr; // ctl: [0] |A n B|, [1] error bits
+    BRX_TRY(plan->ws.get(&plan->d_split, n_tiles + 1));
+    BRX_TRY(plan->ws.get(&plan->d_counts, n_tiles));
+    BRX_TRY(plan->ws.get(&d_sums, n_sums + 1));
+    BRX_TRY(plan->ws.get(&d_ctl, 2));
+    BRX_HIP(hipMemsetAsync(d_ctl, 0, 16, s));
+    u64 ctl[2] = {0, 0}, total = 0;
+    int st = BRX_OK;
+    hipError_t e = hipSuccess;
+    {
+        KernelTimer kt("set_merge", s);
+        merge_split_kernel<<<read_grid((n_tiles + 256) / 256, 256u * 16u), 256, 0, s>>>(plan->d_a, na, plan->d_b, nb, n_tiles, plan->d_split);
+        merge_count_kernel<<<read_grid(n_tiles, 256u * 16u), 256, 0, s>>>(plan->d_a, na, plan->d_b, nb, plan->d_split, n_tiles, KEEP_A[op],
+                                                                         KEEP_B[op], plan->d_counts, d_ctl);
+        if ((e = hipGetLastError()) == hipSuccess)
+            st = keys_scan_exclusive(plan->d_counts, n_tiles, d_sums, s);
+    }
+    if (st == BRX_OK && e == hipSuccess && (e = hipMemcpyAsync(ctl, d_ctl, 16, hipMemcpyDeviceToHost, s)) == hipSuccess)
+        e = hipMemcpyAsync(&total, d_sums + n_sums, 8, hipMemcpyDeviceToHost, s);
+    const hipError_t e2 = hipStreamSynchronize(s); // the scratch may go back to the pool when the caller drops the plan
+    if (st != BRX_OK)
+        return st;
+    if (e != hipSuccess || e2 != hipSuccess) {
+        set_error("%s: merge, pass 1: %s", me, hipGetErrorString(e != hipSuccess ? e : e2));
+        return BRX_ERR_HIP;
+    }
+    if (ctl[1]) {
+        set_error("%s: the keys of an input do not ascend strictly (unordered or repeated keys)", me);
+        return BRX_ERR_ARG;
+    }
+    // the four sizes follow from |A|, |B| and |A n B|: what the scan found must agree
+    const uint64_t both = ctl[0];
+    uint64_t want = both; // intersection
+    if (op == BRX_SETOP_UNION)
+        want = na + nb - both;
+    else if (op == BRX_SETOP_DIFFERENCE)
+        want = na - both;
+    else if (op == BRX_SETOP_SYMDIFF)
+        want = na + nb - 2 * both;
+    if (both > na || both > nb || total != want) {
+        set_error("%s: merge, pass 1: %llu keys kept, |A|=%llu |B|=%llu |A n B|=%llu", me, total, (u64)na, (u64)nb, (u64)both);
+        return BRX_ERR_HIP;
+    }
+    plan->total = total;
+    plan->both = both;
+    return BRX_OK;
+}
+
+// pass 2 into d_out (plan->total entries); returns after `s` has been synchronised
+int merge_write(const char *me, const MergePlan &plan, uint64_t *d_out, hipStream_t s)
+{
+    if (!plan.total)
+        return BRX_OK;
+    {
+        KernelTimer kt("set_merge", s);
+        merge_write_kernel<<<read_grid(plan.n_tiles, 256u * 16u), 256, 0, s>>>(plan.d_a, plan.na, plan.d_b, plan.nb, plan.d_split, plan.n_tiles,
+                                                                              KEEP_A[plan.op], KEEP_B[plan.op], plan.d_counts, (u64 *)d_out,
+                                                                              plan.total);
+    }
+    const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(s);
+    if (e1 != hipSuccess || e2 != hipSuccess) {
+        set_error("%s: merge, pass 2: %s", me, hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+        return BRX_ERR_HIP;
+    }
+    return BRX_OK;
+}
+
+bool overlap(const void *p, uint64_t pn, const void *q, uint64_t qn)
+{
+    const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
+    return p && q && pn && qn && p0 < q0 + qn * 8 && q0 < p0 + pn * 8;
+}
+
+int operands_ok(const char *me, const brx_set *a, const brx_set *b)
+{
+    if (!a || !b) {
+        set_error("%s: null set", me);
+        return BRX_ERR_ARG;
+    }
+    if (a->k != b->k || a->device != b->device) {
+        set_error("%s: the operands differ: a has k = %d on device %d, b has k = %d on device %d", me, a->k, a->device, b->k, b->device);
+        return BRX_ERR_ARG;
+    }
+    if (!(a->k & 1) || a->k < 5 || a->k > 31) {
+        set_error("%s: set algebra works on the keys of odd k from 5 to 31 (k=%d)", me, a->k);
+        return BRX_ERR_UNSUPPORTED;
+    }
+    return BRX_OK;
+}
+
+// the sorted keys of both operands (one list when they are one set)
+struct Operands {
+    DevBuf<uint64_t> keys_a, keys_b;
+    const uint64_t *d_a = nullptr, *d_b = nullptr;
+    uint64_t na = 0, nb = 0;
+};
+
+int operands_list(const brx_set *a, const brx_set *b, hipStream_t s, Operands *o)
+{
+    // (a key list that came from a key file or from set algebra says that it is in order: no sort.  Pass 1 checks the
+    // order of whatever it is given, so a wrong flag would be refused, not merged.)
+    const uint32_t key_bits = (uint32_t)(2 * a->k - 1);
+    bool sorted = false;
+    BRX_TRY(set_list_keys(a, s, o->keys_a, &o->na, &sorted));
+    if (!sorted)
+        BRX_TRY(keys_sort(o->keys_a, nullptr, o->na, key_bits, s));
+    o->d_a = o->keys_a;
+    if (a == b) {
+        o->d_b = o->d_a;
+        o->nb = o->na;
+        return BRX_OK;
+    }
+    BRX_TRY(set_list_keys(b, s, o->keys_b, &o->nb, &sorted));
+    if (!sorted)
+        BRX_TRY(keys_sort(o->keys_b, nullptr, o->nb, key_bits, s));
+    o->d_b = o->keys_b;
+    return BRX_OK;
+}
+
+struct OwnStream {
+    hipStream_t s = nullptr;
+    ~OwnStream()
+    {
+        if (s) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamDestroy(s);
+        }
+    }
+};
+
+} // namespace
+
+extern "C" {
+
+int brx_keys_combine_device(const uint64_t *d_a, uint64_t na, const uint64_t *d_b, uint64_t nb, int op, uint64_t *d_out, uint64_t cap,
+                            uint64_t *n_out, uint64_t *sizes3, void *stream)
+{
+    const char *me = "brx_keys_combine_device";
+    if (!n_out || (!d_out && cap)) {
+        set_error("%s: null n_out, or a capacity without an output array", me);
+        return BRX_ERR_ARG;
+    }
+    *n_out = 0;
+    if (overlap(d_out, cap, d_a, na) || overlap(d_out, cap, d_b, nb)) {
+        set_error("%s: the output array overlaps an input", me);
+        return BRX_ERR_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    MergePlan plan;
+    BRX_TRY(merge_count(me, d_a, na, d_b, nb, op, s, &plan));
+    *n_out = plan.total;
+    if (sizes3) {
+        sizes3[0] = na;
+        sizes3[1] = nb;
+        sizes3[2] = plan.both;
+    }
+    if (!d_out && !cap)
+        return BRX_OK; // the sizes only
+    if (cap < plan.total) {
+        set_error("%s: the result holds %llu keys, the output array %llu", me, (u64)plan.total, (u64)cap);
+        return BRX_ERR_ARG;
+    }
+    return merge_write(me, plan, d_out, s);
+}
+
+int brx_set_combine(const brx_set_t *a, const brx_set_t *b, int op, brx_set_t **out, uint64_t *stats8)
+{
+    const char *me = "brx_set_combine";
+    if (!out) {
+        set_error("%s: null out", me);
+        return BRX_ERR_ARG;
+    }
+    *out = nullptr;
+    BRX_TRY(operands_ok(me, a, b));
+    if (op < 0 || op > 3) {
+        set_error("%s: op=%d (BRX_SETOP_UNION 0, INTERSECT 1, DIFFERENCE 2, SYMDIFF 3)", me, op);
+        return BRX_ERR_ARG;
+    }
+    uint64_t st8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto t0 = Clock::now();
+    BRX_TRY(use_device(a->device));
+    OwnStream own;
+    BRX_HIP(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
+    hipStream_t s = own.s;
+    Operands o;
+    BRX_TRY(operands_list(a, b, s, &o));
+    st8[4] = ns_since(t0);
+    auto t1 = Clock::now();
+    DevBuf<uint64_t> d_res;
+    {
+        MergePlan plan;
+        BRX_TRY(merge_count(me, o.d_a, o.na, o.d_b, o.nb, op, s, &plan));
+        if (plan.total > set_nbits(a->k)) {
+            set_error("%s: %llu keys in the result, only %llu exist at k=%d", me, (u64)plan.total, (u64)set_nbits(a->k), a->k);
+            return BRX_ERR_HIP;
+        }
+        if (plan.total)
+            BRX_TRY(d_res.reserve(plan.total, 0, "keys of the combined set"));
+        BRX_TRY(merge_write(me, plan, d_res, s));
+        st8[0] = o.na;
+        st8[1] = o.nb;
+        st8[2] = plan.both;
+        st8[3] = plan.total;
+    }
+    o.keys_a.reset(); // (the operands' lists go back before the result's index is built)
+    o.keys_b.reset();
+    st8[5] = ns_since(t1);
+    auto t2 = Clock::now();
+    brx_set *set = nullptr;
+    int st = set_alloc_unwritten(a->k, a->device, &set);
+    if (st == BRX_OK)
+        st = set_build_from_keys(set, d_res, st8[3], s, me);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (st == BRX_OK && e != hipSuccess) {
+        set_error("%s: building the set: %s", me, hipGetErrorString(e));
+        st = BRX_ERR_HIP;
+    }
+    if (st != BRX_OK) {
+        if (set)
+            brx_set_free(set);
+        return st;
+    }
+    st8[6] = ns_since(t2);
+    st8[7] = ns_since(t0);
+    *out = set;
+    if (stats8)
+        memcpy(stats8, st8, sizeof st8);
+    return BRX_OK;
+}
+
+int brx_set_compare(const brx_set_t *a, const brx_set_t *b, uint64_t *sizes3)
+{
+    const char *me = "brx_set_compare";
+    if (!sizes3) {
+        set_error("%s: null sizes3", me);
+        return BRX_ERR_ARG;
+    }
+    BRX_TRY(operands_ok(me, a, b));
+    BRX_TRY(use_device(a->device));
+    OwnStream own;
+    BRX_HIP(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
+    Operands o;
+    BRX_TRY(operands_list(a, b, own.s, &o));
+    MergePlan plan;
+    BRX_TRY(merge_count(me, o.d_a, o.na, o.d_b, o.nb, BRX_SETOP_INTERSECT, own.s, &plan));
+    sizes3[0] = o.na;
+    sizes3[1] = o.nb;
+    sizes3[2] = plan.both;
+    return BRX_OK;
+}
+
+} // extern "C"

@@ -49,6 +49,23 @@ def sort_keys_device(d_keys: int, d_payload: Optional[int], n: int, key_bits: in
     _lib.check(_lib.lib().brx_sort_keys_device(d_keys, d_payload, n, key_bits, stream))
 
 
+def combine_keys_device(d_a: Optional[int], na: int, d_b: Optional[int], nb: int, op, d_out: Optional[int], cap: int,
+                        stream: Optional[int] = None) -> Tuple[int, Tuple[int, int, int]]:
+    """(size of the result, (|A|, |B|, |A n B|)) of two strictly ascending u64 key arrays on the device combined by `op`
+    (a name of setops.OPS or a BRX_SETOP_* number) into d_out, which holds `cap` keys; d_out None with cap 0 asks for the
+    sizes only (brx_keys_combine_device).  A BrxError carries `needed` where the library said how many keys there are"""
+    from . import setops
+    n, s3 = C.c_uint64(0), (C.c_uint64 * 3)()
+    st = _lib.lib().brx_keys_combine_device(d_a, na, d_b, nb, setops.op_id(op) if isinstance(op, str) else int(op), d_out, cap,
+                                            C.byref(n), s3, stream)
+    try:
+        _lib.check(st)
+    except _lib.BrxError as e:
+        e.needed = int(n.value)
+        raise
+    return int(n.value), (int(s3[0]), int(s3[1]), int(s3[2]))
+
+
 class KmerSet:
     """trait KmerSet (src/set.rs:17-21)."""
 
@@ -154,6 +171,53 @@ class Pcon(KmerSet):
         with hostio.output_fd(f) as fd:
             _lib.check(_lib.lib().brx_set_save_fd(self._h, fd, st))
         return _keyfile_stats(st)
+
+    # ---- set algebra (include/brx.h "set algebra", br_amd/setops.py) --------------------------------------------------
+    def combine(self, other: "Pcon", op) -> "Pcon":
+        """a new closed set, `self op other` (op: a name of setops.OPS or a BRX_SETOP_* number): same k and device, sets
+        held in any form; both operands are only read (brx_set_combine)"""
+        from . import setops
+        if not isinstance(other, Pcon):
+            raise TypeError("set algebra needs two Pcon sets")
+        h = C.c_void_p()
+        st = (C.c_uint64 * 8)()
+        _lib.check(_lib.lib().brx_set_combine(self._h, other._h, setops.op_id(op), C.byref(h), st))
+        s = Pcon(h.value, self.device)
+        s.combine_stats = {"a": int(st[0]), "b": int(st[1]), "both": int(st[2]), "keys": int(st[3]), "ns_list_sort": int(st[4]),
+                           "ns_merge": int(st[5]), "ns_build": int(st[6]), "ns_wall": int(st[7])}
+        return s
+
+    def union(self, other: "Pcon") -> "Pcon":
+        return self.combine(other, "union")
+
+    def intersection(self, other: "Pcon") -> "Pcon":
+        return self.combine(other, "intersection")
+
+    def difference(self, other: "Pcon") -> "Pcon":
+        return self.combine(other, "difference")
+
+    def symmetric_difference(self, other: "Pcon") -> "Pcon":
+        return self.combine(other, "symmetric_difference")
+
+    def _operator(name):
+        def op(self, other):
+            return self.combine(other, name) if isinstance(other, Pcon) else NotImplemented
+        return op
+
+    __or__, __and__ = _operator("union"), _operator("intersection")
+    __sub__, __xor__ = _operator("difference"), _operator("symmetric_difference")
+    del _operator
+
+    def compare(self, other: "Pcon") -> dict:
+        """{"a": |self|, "b": |other|, "both": |self n other|, "jaccard": both / |self u other|, 1.0 for two empty sets}:
+        the keys of both listed, sorted and walked once, nothing built (brx_set_compare)"""
+        from . import setops
+        if not isinstance(other, Pcon):
+            raise TypeError("set algebra needs two Pcon sets")
+        s3 = (C.c_uint64 * 3)()
+        _lib.check(_lib.lib().brx_set_compare(self._h, other._h, s3))
+        na, nb, both = int(s3[0]), int(s3[1]), int(s3[2])
+        return {"a": na, "b": nb, "both": both, "jaccard": setops.jaccard(na, nb, both)}
 
     # ---- KmerSet ----------------------------------------------------------------------
     def get(self, kmer: int) -> bool:

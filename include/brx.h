@@ -96,7 +96,7 @@ int brx_set_insert_batch(brx_set_t *set, const uint8_t *bases, const uint64_t *o
  *   - RESULTS are ready in the order of `stream` -- work queued on `stream` after the call sees them; the host sees them
  *     after it has synchronised `stream` -- or on return, where the entry says that it returns after its kernels have
  *     completed or after `stream` has been synchronised.  Values handed back through host pointers are valid on return.
- *   - a FRESHLY CREATED object (brx_set_new, brx_set_count_begin, brx_set_count_finish, brx_set_load_fd, brx_chain_new) may
+ *   - a FRESHLY CREATED object (brx_set_new, brx_set_count_begin, brx_set_count_finish, brx_set_load_fd, brx_set_combine, brx_chain_new) may
  *     be used on any stream at once: whatever its constructor zeroes or writes is complete when the constructor returns.
  *   - an entry WITHOUT a stream argument that changes an object (brx_set_count_add_batch, brx_counter_load_counts,
  *     brx_counter_load_fd, brx_count_fasta_fd) sees everything that earlier calls on the same object enqueued, whichever stream they named:
@@ -105,7 +105,7 @@ int brx_set_insert_batch(brx_set_t *set, const uint8_t *bases, const uint64_t *o
  *     leaves the finish queued on `s` its batches and workspace, for every count strategy.  The same holds for the counter's
  *     host-path lookups (brx_counter_abundance_batch, brx_counter_get_counts, brx_counter_save_fd).
  *   - the host-path READERS of a set -- brx_set_get, get_batch, get_batch_indexed, popcount, export_solid_bytes, set,
- *     brx_set_save_fd -- work on the null stream and do NOT wait for a non-blocking stream: after an asynchronous device
+ *     brx_set_save_fd, brx_set_combine, brx_set_compare -- work on the null stream or one of their own and do NOT wait for a non-blocking stream: after an asynchronous device
  *     entry that wrote the set (insert_batch_device, or_keys_device, count_finish_into) the ordering is the CALLER's:
  *     synchronise that stream first.  Pointers handed out (brx_set_device_bits, brx_set_keylist_device,
  *     brx_counter_device_counts, brx_counter_l1_view) are the caller's to order likewise.
@@ -396,6 +396,40 @@ int brx_set_save_fd(const brx_set_t *set, int out_fd, uint64_t *stats8);
  * k <= 19: the key list attached as after a counted finish (k >= 15) and the bit vector written.  get, get_batch,
  * popcount, fingerprint, .solid export (k <= 19), cover and correction answer as for the set that was saved.               */
 int brx_set_load_fd(int in_fd, int device, brx_set_t **out, uint64_t *stats8);
+
+/* ---- set algebra: union, intersection, difference of solid sets at any odd k.  No counterpart in the reference -------------
+ * br_amd/setops.py states the operations in numpy.  The hot path is a merge of two strictly ascending lists of u64 keys by
+ * merge path (br_amd/csrc/brx_setops.hip): tiles of 2048 positions of the merged sequence, their borders found by a binary
+ * search on the diagonal (ties: A first), both pieces in LDS with one key of halo each side, 8 keys per thread merged
+ * serially.  Whether a key is in the other list is read off its neighbour there, so no thread or tile asks another.  Pass 1
+ * counts the kept keys per tile, sums |A n B| and checks that both lists ascend strictly; a scan turns the counts into
+ * offsets; pass 2 merges again, compacts in LDS and writes whole runs.  One profile timer, "set_merge".                     */
+#define BRX_SETOP_UNION 0
+#define BRX_SETOP_INTERSECT 1
+#define BRX_SETOP_DIFFERENCE 2 /* A minus B */
+#define BRX_SETOP_SYMDIFF 3
+/* The raw operation, the counterpart of brx_sort_keys_device: d_a[0 .. na) and d_b[0 .. nb), each strictly ascending (either
+ * may be empty, the two may be the same array), combined by `op` into d_out[0 .. *n_out), strictly ascending.  The inputs are
+ * read in the order of `stream`; returns after `stream` has been synchronised.  sizes3 (may be NULL) receives |A|, |B|,
+ * |A n B|.  d_out == NULL with cap == 0 asks for *n_out and sizes3 only.  A cap smaller than the result is BRX_ERR_ARG with
+ * *n_out set to what is needed; unordered or repeated keys in an input, a bad op and a d_out that overlaps an input are
+ * BRX_ERR_ARG with *n_out = 0; d_out is untouched in all these cases.  Scratch (two u64 per tile) comes from the device pool.  */
+int brx_keys_combine_device(const uint64_t *d_a, uint64_t na, const uint64_t *d_b, uint64_t nb, int op, uint64_t *d_out,
+                            uint64_t cap, uint64_t *n_out, uint64_t *sizes3 /* may be NULL */, void *stream);
+/* A new closed set on the operands' device: the keys of both are listed and sorted as brx_set_save_fd does (a key list that
+ * came from brx_set_load_fd or from this call is known to be in order and is not sorted again, until something rewrites or
+ * drops it), merged, and the result is exactly the set
+ * brx_set_load_fd makes from those keys -- k >= 21: sparse, key list attached, chained index built; k <= 19: the bit vector
+ * written, the key list kept for k >= 15; an empty result is a valid empty set.  Both sets must have the same k and device
+ * (BRX_ERR_ARG, the message names both), odd k from 5 to 31 (BRX_ERR_UNSUPPORTED otherwise), and may be held in any form;
+ * a == b is allowed.  Both are only read: a lazy bit vector stays lazy, index and key list stay.  The call works on a stream of
+ * its own and returns complete (a freshly created object, see "streams"); like brx_set_save_fd it is a host-path READER of
+ * its operands and does not wait for a caller's non-blocking stream that still writes them.
+ * stats8 (may be NULL): [0] |A|, [1] |B|, [2] |A n B|, [3] |result|, [4] ns listing + sorting, [5] ns merging, [6] ns
+ * building the set, [7] ns wall.                                                                                             */
+int brx_set_combine(const brx_set_t *a, const brx_set_t *b, int op, brx_set_t **out, uint64_t *stats8);
+/* sizes3 = |A|, |B|, |A n B| of two sets under the same rules: listing, sorting and pass 1 alone, nothing is built          */
+int brx_set_compare(const brx_set_t *a, const brx_set_t *b, uint64_t *sizes3);
 
 /* ---- multi-GPU: reads shard over the GPUs, the set is exchanged ONCE -----------------------------
  * The reference is one process with rayon threads over shared memory (src/main.rs:30-33, src/lib.rs:72-139); on N
