@@ -2,12 +2,14 @@
 all ranks on ONE card: the library's librccl calls are served by tests/libfake_rccl.so (selected through BRX_RCCL_PATH
 by the test that starts this process), everything above those ten entry points is the product's code, and every
 kernel is the product's.  The communicator id travels through a file: no torch.distributed anywhere.
-usage: python abi_exchange_worker.py RANK WORLD K ABUNDANCE N_READS OUT_PREFIX part|dense"""
+usage: python abi_exchange_worker.py RANK WORLD K ABUNDANCE N_READS OUT_PREFIX part|dense [CUTS]
+  CUTS  WORLD + 1 comma-separated cut points: rank r takes reads [CUTS[r], CUTS[r + 1]); default br_amd.dist.shard_range"""
 import os
 import pickle
 import sys
 import time
 
+T_START = time.time()
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 rank, world, k, a, n_reads = (int(x) for x in sys.argv[1:6])
@@ -18,9 +20,20 @@ import br_amd
 from br_amd import _lib, fasta
 from br_amd import dist as bd
 
+
+def phase(what):
+    """to stderr, which the runner keeps per rank: where the time of a slow or a hung world went"""
+    print("rank %d: %s at %.2f s" % (rank, what, time.time() - T_START), file=sys.stderr, flush=True)
+
+
+phase("imports done")
 with open(os.path.join(ROOT, "tests", "golden", "raw.fasta"), "rb") as f:
     reads = [seq for _, _, seq in fasta.read_records(f)][:n_reads]
 lo, hi = bd.shard_range(len(reads), world, rank)
+if len(sys.argv) > 8:
+    cuts = [int(x) for x in sys.argv[8].split(",")]
+    assert len(cuts) == world + 1 and cuts[0] == 0 and cuts[-1] == len(reads)
+    lo, hi = cuts[rank], cuts[rank + 1]
 mine = reads[lo:hi]                                   # may be empty: that rank still joins every collective
 
 id_path = out_prefix + ".id"
@@ -37,7 +50,9 @@ else:
         time.sleep(0.05)
     with open(id_path, "rb") as f:
         ident = f.read()
+phase("communicator id in hand")
 ex = bd.AbiExchange(world, rank, 0, ident=ident)
+phase("communicator up")
 result = {"n_mine": len(mine)}
 if strategy == "part":
     counter = br_amd.Counter(k, 0, _lib.COUNT_SORTED)
@@ -45,17 +60,23 @@ if strategy == "part":
     for rep in range(2):                              # twice: the bench resets and re-uses the same objects every step
         if mine:
             counter.add_reads(mine)
+        phase("shard counted (%d)" % rep)
         ex.build_partitioned(counter, solid, a, None)
+        phase("set built (%d)" % rep)
         result["stats_%d" % rep] = ex.last_stats()
         chain = br_amd.Chain(solid, [("one", 5, 7), ("graph", 5, 7)], two_side=False)
         result["corrected_%d" % rep] = chain.correct_reads(mine) if mine else []
         del chain
+        phase("shard corrected (%d)" % rep)
     result["index"] = solid.index_info()
+    result["n_buckets"] = counter.l1_view()[2]        # the first digits the owners divide (the counter is empty again)
 else:
     counter = br_amd.Counter(k, 0, _lib.COUNT_DENSE)
     if mine:
         counter.add_reads(mine)
+    phase("shard counted")
     ex.reduce_counts(counter, a, None)
+    phase("counts reduced")
     solid = counter.finish(a)
 result["popcount"] = solid.popcount()
 if k <= 15:
@@ -69,5 +90,6 @@ else:  # 2^(2k-4) bytes per rank is too much to ship: membership of every third 
     result["sample"] = sample
     result["members"] = [bool(x) for x in solid.get_many(sample)]
 ex.close()
+phase("communicator closed")
 with open("%s.rank%d.pkl" % (out_prefix, rank), "wb") as f:
     pickle.dump(result, f)

@@ -10,6 +10,7 @@ import pickle
 import sys
 import time
 
+T_START = time.time()
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 rank, world, k, a, n_reads = (int(x) for x in sys.argv[1:6])
@@ -20,6 +21,13 @@ import br_amd
 from br_amd import _lib, fasta
 from br_amd import dist as bd
 
+
+def phase(what):
+    """to stderr, which the runner keeps per rank: where the time of a slow or a hung world went"""
+    print("rank %d: %s at %.2f s" % (rank, what, time.time() - T_START), file=sys.stderr, flush=True)
+
+
+phase("imports done")
 if mode == "sat":
     reads = [b"A" * (k + 199), b"C" * (k + 59)] * 2
 else:
@@ -42,7 +50,9 @@ else:
         time.sleep(0.05)
     with open(id_path, "rb") as f:
         ident = f.read()
+phase("communicator id in hand")
 ex = bd.AbiExchange(world, rank, 0, ident=ident)
+phase("communicator up")
 result = {"n_mine": len(mine)}
 counter = br_amd.Counter(k, 0, _lib.COUNT_TABLE)
 half = (len(mine) + 1) // 2
@@ -50,11 +60,14 @@ for part in (mine[:half], mine[half:]):               # any number of batches: t
     if part:
         counter.add_reads(part)
 result["state_before"] = counter.merge_state()
+phase("shard counted")
 ex.merge_table(counter)
+phase("merged")
 result["state_after"] = counter.merge_state()
 result["stats_merge"] = ex.last_stats()
 result["keys"] = counter.table_info()["keys"]
 result["spectrum"] = ex.spectrum(counter)
+phase("spectrum")
 solid = br_amd.Pcon.new(k)
 if mode == "sat":
     probes = [br_amd.seq2bit(b"A" * k), br_amd.seq2bit(b"C" * k)]
@@ -63,9 +76,11 @@ if mode == "sat":
     for thr in (254, 255, 119, 120):
         ex.finish_table(counter, solid, thr)
         result["finish"][thr] = ([bool(x) for x in solid.get_many(probes)], solid.fingerprint())
+        phase("finished at threshold %d" % thr)
     result["state_end"] = counter.merge_state()
 else:
     ex.finish_table(counter, solid, a)
+    phase("finished")
     result["stats"] = ex.last_stats()
     result["popcount"] = solid.popcount()
     result["fingerprint"] = solid.fingerprint()
@@ -84,6 +99,8 @@ else:
     chain = br_amd.Chain(solid, [("one", 5, 7), ("graph", 5, 7)], two_side=False)
     result["corrected"] = chain.correct_reads(mine) if mine else []
     del chain
+    phase("shard corrected")
 ex.close()
+phase("communicator closed")
 with open("%s.rank%d.pkl" % (out_prefix, rank), "wb") as f:
     pickle.dump(result, f)

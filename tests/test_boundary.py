@@ -200,8 +200,8 @@ def _plan(tables, world, nb, rank):
     return st, bound, sc, rc, seg.reshape(world, T), int(big.value)
 
 
-@pytest.mark.parametrize("world", [1, 2, 3, 5, 8])
-@pytest.mark.parametrize("nb", [4, 13, 512])
+@pytest.mark.parametrize("world", [1, 2, 3, 5, 7, 8])
+@pytest.mark.parametrize("nb", [4, 13, 128, 512])
 def test_exchange_plan_layout(world, nb):
     """brx_exchange_plan, the pure host arithmetic of brx_exchange_build_partitioned (owner bounds, per-peer counts,
     clamped + rebased segment tables, the job's largest message), against a direct numpy statement on synthetic
@@ -211,7 +211,9 @@ def test_exchange_plan_layout(world, nb):
     rng = np.random.default_rng(world * 1000 + nb)
     counts = rng.integers(0, 50, size=(world, nb)).astype(np.uint64)
     if world > 1:
-        counts[1] = 0                                           # a rank that counted nothing
+        counts[1] = 0                                           # a rank that counted nothing: its row of the table is all zeros
+    if world > 4:
+        counts[world - 1] = 0                                   # and the last one (worlds 5, 7, 8)
     if world > 2:
         counts[2] = 0
         counts[2, nb - 1] = 12345                               # everything in the last digit

@@ -132,7 +132,7 @@ def _part_worker(rank, world, port, k, abundance, q):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world", [2, 3])
+@pytest.mark.parametrize("world", [2, 3, 5])
 def test_partitioned_key_exchange_matches_single(world):
     k, abundance = 9, 1
     ctx = mp.get_context("spawn")

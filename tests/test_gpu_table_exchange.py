@@ -1,14 +1,12 @@
 """Counted sets across ranks at any odd k up to 31: the counting tables of the ranks merged by owner
 (br_amd/csrc/brx_exchange.hip brx_exchange_table_merge / _spectrum / _table_finish, the split and merge kernels of
-brx_counttable.hip), run with world 2 and 3 for real in the manner of test_gpu_exchange_abi.py: `world` fresh processes
-(tests/table_exchange_worker.py) share the one card, the library's librccl entry points are served by
-tests/libfake_rccl.so.  Expected values: the CPU oracle's sets and corrections, and a table counter of this process
-that counted all the reads at once -- what the ranks together must reproduce bin for bin.
+brx_counttable.hip), run with world 2, 3, 5, 7 and 8 for real in the manner of test_gpu_exchange_abi.py: `world` fresh
+processes (tests/table_exchange_worker.py) share the one card, the library's librccl entry points are served by
+tests/libfake_rccl.so.  Expected values: the CPU oracle's sets and corrections, the owners br_amd.dist.table_owner names, and
+a table counter of this process that counted all the reads at once -- what the ranks together must reproduce bin for bin.
+That the inputs do what they are for is asserted first, on the CPU (the tests without the gpu mark; tests/world_runner.py).
 Reference: no counterpart (one process, src/main.rs:30-33); src/lib.rs:72-139 is the loop being sharded."""
 import os
-import pickle
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,13 +15,18 @@ import br_amd
 from br_amd import _lib, synth
 from br_amd import dist as D
 from oracle import oracle as O
+from tests import world_runner as WR
 
-pytestmark = pytest.mark.gpu
+gpu = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-FAKE = os.path.join(HERE, "libfake_rccl.so")
 WORKER = os.path.join(HERE, "table_exchange_worker.py")
 TABLE = _lib.COUNT_TABLE
+
+LARGE_K_SMALL = [(2, 23), (3, 25), (3, 31)]        # 150 reads, BRX_A2A_CHUNK 30000
+LARGE_K_LARGE = [(5, 23), (8, 25), (7, 31)]        # 150 reads, BRX_A2A_CHUNK 8000: a third of the smallest of their largest messages
+LARGE_K_READS = 150
+EMPTY_8 = (8, 23, 0, 3)                            # world, k, a, reads
 
 _cache = {}
 
@@ -36,32 +39,60 @@ def _ref_set(k, reads, n, a):
     return _cache[key]
 
 
-def _run_world(tmp_path, world, k, a, n_reads, mode, extra_env=None):
-    assert os.path.exists(FAKE), "tests/libfake_rccl.so not built: __graft_entry__.build()"
-    assert world + 1 <= 4                                         # processes that hold the GPU at once, this one included
-    prefix = str(tmp_path / "x")
-    env = dict(os.environ)
-    env["BRX_RCCL_PATH"] = FAKE
-    env["FAKE_RCCL_DIR"] = str(tmp_path)
-    env["FAKE_RCCL_STATS"] = prefix + ".traffic"
-    env.update(extra_env or {})
-    procs = [subprocess.Popen([sys.executable, WORKER, str(r), str(world), str(k), str(a), str(n_reads), prefix, mode], env=env)
-             for r in range(world)]
-    try:
-        codes = [p.wait(timeout=280) for p in procs]
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    assert codes == [0] * world
-    out = []
-    for r in range(world):
-        with open("%s.rank%d.pkl" % (prefix, r), "rb") as f:
-            out.append(pickle.load(f))
-        with open("%s.traffic.rank%d" % (prefix, r)) as f:
-            out[-1]["msgs"], out[-1]["bytes"] = (int(x) for x in f.read().split())
-    return out
+def _large_k_chunk(world, k):
+    return 8000 if (world, k) in LARGE_K_LARGE else 30000
 
+
+def _run_world(tmp_path, world, k, a, n_reads, mode, extra_env=None):
+    assert os.path.exists(WR.FAKE), "tests/libfake_rccl.so not built: __graft_entry__.build()"
+    return WR.run_world(tmp_path, WORKER, world, [k, a, n_reads, mode], extra_env)
+
+
+# ---- CPU: the inputs do what they are for ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("world,k", LARGE_K_LARGE)
+def test_large_worlds_take_several_rounds(world, k):
+    """the largest per-peer message (entries) is at least 3 x BRX_A2A_CHUNK; every rank has reads and entries for every owner"""
+    m = WR.table_messages(k, LARGE_K_READS, world)
+    assert m.shape == (world, world) and m.min() > 0
+    assert m.max() >= 3 * _large_k_chunk(world, k), (m.max(), _large_k_chunk(world, k))
+
+
+@pytest.mark.parametrize("world,k", LARGE_K_LARGE)
+def test_large_worlds_figures_are_their_own(world, k):
+    """the exact per-rank key counts the GPU test asserts are not those of world - 1 owners, for any rank; and where the
+    reads do not divide evenly the messages are not those of a sharding other than shard_range"""
+    right = WR.table_keys_per_owner(k, LARGE_K_READS, world)
+    fewer = WR.table_keys_per_owner(k, LARGE_K_READS, world - 1)
+    assert right.sum() == fewer.sum() and all(right[r] != fewer[r] for r in range(world - 1))
+    assert right.sum() == np.unique(np.concatenate(WR.read_hashes(k, LARGE_K_READS))).size
+    if LARGE_K_READS % world:
+        other = WR.table_messages(k, LARGE_K_READS, world, cuts=WR.even_cuts(LARGE_K_READS, world))
+        assert not np.array_equal(WR.table_messages(k, LARGE_K_READS, world), other)
+    else:
+        assert (world, k) == (5, 23)                                                   # 150 = 5 x 30: only the owners tell
+
+
+def test_three_reads_leave_five_ranks_without_any():
+    world, k, _, n_reads = EMPTY_8
+    cuts = WR.shard_cuts(n_reads, world)
+    assert [hi - lo for lo, hi in zip(cuts, cuts[1:])] == [0, 0, 1, 0, 0, 1, 0, 1]
+    m = WR.table_messages(k, n_reads, world)
+    assert [int(x) for x in np.flatnonzero(m.sum(axis=1) == 0)] == [0, 1, 3, 4, 6]
+    assert WR.table_keys_per_owner(k, n_reads, world).min() > 0                       # every rank owns k-mers all the same
+
+
+def test_three_reads_figures_are_their_own():
+    """the exact per-rank figures of the 3-read job are not those of 7 owners, for any rank"""
+    world, k, _, n_reads = EMPTY_8
+    right, fewer = WR.table_keys_per_owner(k, n_reads, world), WR.table_keys_per_owner(k, n_reads, world - 1)
+    assert right.sum() == fewer.sum() and all(right[r] != fewer[r] for r in range(world - 1))
+    m, mf = WR.table_messages(k, n_reads, world), WR.table_messages(k, n_reads, world, owners=world - 1)
+    assert all(m[:, r].sum() != mf[:, r].sum() for r in range(world - 1))
+    assert not np.array_equal(m, WR.table_messages(k, n_reads, world, cuts=WR.even_cuts(n_reads, world)))
+
+
+# ---- GPU ------------------------------------------------------------------------------------------------------------
 
 def _check_job(res, world, k, a, reads, several_rounds):
     """everything the ranks of one job must reproduce: the single process's counter, the oracle's set and corrections"""
@@ -103,15 +134,36 @@ def _check_job(res, world, k, a, reads, several_rounds):
     return res
 
 
-@pytest.mark.parametrize("world,k", [(2, 23), (3, 25), (3, 31)])
+def _check_owners(res, world, k, a, n_reads):
+    """the CPU's statement of who owns what, exactly: the keys of every merged counter, its solid ones, the merge's traffic"""
+    keys = WR.table_keys_per_owner(k, n_reads, world)
+    solid = WR.table_keys_per_owner(k, n_reads, world, a)
+    m = WR.table_messages(k, n_reads, world)
+    for r, x in enumerate(res):
+        sm = x["stats_merge"]
+        assert x["keys"] == keys[r], r                                                 # table_owner(h, world) == r and no others
+        assert x["stats"]["solid_here"] == solid[r], r
+        assert sm["keys_counted_here"] == m[:, r].sum(), r                             # one entry per source that has the key
+        assert sm["key_bytes_sent"] == 9 * (m[r].sum() - m[r, r]), r
+        assert sm["key_bytes_received"] == 9 * (m[:, r].sum() - m[r, r]), r
+        assert sm["largest_message_keys"] == m.max(), r                                # the same on every rank: it sets the rounds
+    return m
+
+
+@gpu
+@pytest.mark.parametrize("world,k", LARGE_K_SMALL + LARGE_K_LARGE)
 def test_table_exchange_large_k(tmp_path, raw_reads, world, k):
-    """the feature: a counted set at k >= 23 over 2 / 3 ranks, several capped rounds of the pair all-to-all"""
-    reads = raw_reads[:150]
-    res = _run_world(tmp_path, world, k, 1, 150, "raw", {"BRX_A2A_CHUNK": "30000"})
+    """the feature: a counted set at k >= 23 over 2 / 3 / 5 / 7 / 8 ranks, several capped rounds of the pair all-to-all"""
+    reads = raw_reads[:LARGE_K_READS]
+    chunk = _large_k_chunk(world, k)
+    res = _run_world(tmp_path, world, k, 1, LARGE_K_READS, "raw", {"BRX_A2A_CHUNK": str(chunk)})
     _check_job(res, world, k, 1, reads, True)
     assert res[0]["popcount"] > 1000
+    m = _check_owners(res, world, k, 1, LARGE_K_READS)
+    assert m.max() >= (3 * chunk if (world, k) in LARGE_K_LARGE else chunk // 2)
 
 
+@gpu
 @pytest.mark.parametrize("world,k", [(2, 15), (2, 21)])
 def test_table_exchange_bit_vector_and_smallest_sparse_k(tmp_path, raw_reads, world, k):
     """a destination with a bit vector (k = 15: to_solid_bytes against the dense oracle) and the smallest sparse k"""
@@ -120,6 +172,7 @@ def test_table_exchange_bit_vector_and_smallest_sparse_k(tmp_path, raw_reads, wo
     _check_job(res, world, k, 2, reads, False)
 
 
+@gpu
 def test_table_exchange_sums_and_saturation(tmp_path):
     """each of two ranks counts poly-A 200 times and poly-C 60 times: the owner reads min(255, 400) and 120, the other
     rank 0; four thresholds on the same merged counter"""
@@ -140,6 +193,7 @@ def test_table_exchange_sums_and_saturation(tmp_path):
     assert sum(x["keys"] for x in res) == 2
 
 
+@gpu
 def test_table_exchange_with_an_empty_shard(tmp_path, raw_reads):
     """2 reads over 3 ranks: rank 0 counts nothing, joins every collective, owns its share and ends with the whole set"""
     k, a = 23, 0
@@ -151,6 +205,22 @@ def test_table_exchange_with_an_empty_shard(tmp_path, raw_reads):
     assert res[0]["stats"]["solid_here"] > 0
 
 
+@gpu
+def test_table_exchange_world_8_with_three_reads(tmp_path, raw_reads):
+    """3 reads over 8 ranks: five ranks count nothing, join every collective, own their share and end with the whole set"""
+    world, k, a, n_reads = EMPTY_8
+    res = _run_world(tmp_path, world, k, a, n_reads, "raw")
+    assert [x["n_mine"] for x in res] == [0, 0, 1, 0, 0, 1, 0, 1]
+    _check_job(res, world, k, a, raw_reads[:n_reads], False)
+    _check_owners(res, world, k, a, n_reads)
+    for x in res:
+        sm = x["stats_merge"]
+        if not x["n_mine"]:
+            assert sm["key_bytes_sent"] == 0 and sm["keys_counted_here"] > 0 and x["keys"] > 0
+        assert x["stats"]["solid_here"] > 0
+
+
+@gpu
 def test_table_exchange_world_one_through_librccl():
     """merge, spectrum and finish through REAL librccl (world 1 is all a one-GPU box can give it: every entry takes the
     split -> copy -> merge path), and the state rules of a merged counter"""
