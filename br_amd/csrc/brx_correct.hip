@@ -161,12 +161,6 @@ __device__ __forceinline__ GreedyLds greedy_carve(uint8_t *base, uint32_t dim)
     return L;
 }
 
-__host__ __device__ inline uint32_t greedy_lds_bytes(uint32_t dim)
-{
-    const uint32_t a = (dim + 15u) & ~15u;
-    return 13u * a + ((2u * dim * dim + 15u) & ~15u);
-}
-
 template <int G>
 __device__ bool greedy_align(const GreedyLds &L, int gl, int m, int n, int nb, int &off_out)
 {
@@ -2371,104 +2365,20 @@ __global__ __launch_bounds__(256) void compact_kernel(const uint8_t *__restrict_
     }
 }
 
-// headroom of the chain's byte-sized workspaces
-inline uint64_t ws_headroom(uint64_t need) { return need / 8 + 256; }
-
-constexpr uint64_t RESIDENT_LANES = 256ull * 4ull * 6ull * 64ull; // CUs x SIMDs x waves x lanes at occupancy 6
-
-int group_width(bool reverse_pass = false, bool indexed = false, uint32_t n_reads = 0xffffffffu)
-{
-    // lanes per read; BRX_GROUP / BRX_GROUP_REV override (read on every launch so tests can sweep them).
-    // The reverse pass of run_correction (src/lib.rs:48-55) sees almost only non-solid k-mers and hardly
-    // ever triggers, so wide groups waste nothing there and save rounds.
-    const char *e = getenv(reverse_pass ? "BRX_GROUP_REV" : "BRX_GROUP");
-    if (!e && reverse_pass)
-        e = getenv("BRX_GROUP");
-    // measured (tools/ab_correct.py): bitset probes 16/64 (+3 % over 16/16); with the probe index the shared
-    // probe code is the larger part of a round and 8 groups per wave amortise it better: 8/64 (+5 % over 16/64)
-    const int dflt = reverse_pass ? 64 : (indexed ? 8 : 16);
-    int g = e ? atoi(e) : dflt;
-    if (!e) {
-        // small batches (the reference's 8192 records): with fewer reads than resident groups the GPU idles and
-        // the time is one read's chain of rounds -- wider groups advance further per round
-        while (g < 64 && (uint64_t)n_reads * (uint64_t)g * 2u <= RESIDENT_LANES)
-            g *= 2;
-    }
-    return (g == 4 || g == 8 || g == 16 || g == 32 || g == 64) ? g : dflt;
-}
-
-constexpr uint32_t MAX_BLOCKS = 256u * 8u;
-// Visited lists a chain always has, however few reads its batch holds: one block of the narrowest kernel that indexes them
-// by its global group number (4-lane groups: 64 a block).  The list and verify launches size their grids from the lists
-// the chain has (sized_path_lists), never from a width of their own.
-constexpr uint32_t MIN_PATH_LISTS = 64u;
-
-// lanes per read of Graph's and GapSize's forward passes (BRX_GROUP_WALK = 4 / 8 / 16)
-int walk_group()
-{
-    // measured at 1 Gbp, k = 19 (fwd+rev ms, tools/method_bench.py): 16 lanes + bit vector 135 / 158 (graph / gap_size),
-    // 8 lanes + bit vector 140 / 145, 8 lanes + probe index 120 / 142, 4 lanes + probe index 123 / 151
-    const char *e = getenv("BRX_GROUP_WALK"); // (read on every use: the fuzzers sweep it)
-    const int v = e ? atoi(e) : 8;
-    return (v == 4 || v == 8 || v == 16) ? v : 8;
-}
-
-uint32_t pass_blocks(uint32_t n_reads, int G, bool balanced = false)
-{
-    const uint32_t groups_per_block = 256u / (uint32_t)G;
-    // persistent-ish grid: enough groups to fill the chip, reads pulled from a work counter
-    uint64_t want = ((uint64_t)n_reads + groups_per_block - 1) / groups_per_block;
-    if (balanced) {
-        // Reads of a batch take about the same time, and a wave costs the same instructions whether 8 of its groups
-        // are busy or 3: 100 000 reads over 49 152 resident 8-lane groups is two reads each and a third for a few,
-        // i.e. a last third of the kernel run by mostly idle waves.  Fewer groups with the same whole number of reads
-        // each end together.
-        // Measured (profiles/r2_one_kernel_ab.txt): NOT a win -- 4 168 waves instead of 8 192 leave the SIMDs waiting on
-        // memory (VALU busy 65 % instead of 79 %, 32.6 ms against 27.2); kept behind BRX_BALANCE=1 for the record.
-        static const bool on = [] { const char *e = getenv("BRX_BALANCE"); return e && *e == '1'; }();
-        const uint64_t resident_blocks = 256ull * 7; // CUs x (waves per SIMD x 4 SIMDs / 4 waves per block): one_kernel runs 7 per SIMD
-        const uint64_t resident_groups = resident_blocks * groups_per_block;
-        if (on && (uint64_t)n_reads > resident_groups) {
-            const uint64_t per_group = ((uint64_t)n_reads + resident_groups - 1) / resident_groups;
-            const uint64_t groups = ((uint64_t)n_reads + per_group - 1) / per_group;
-            want = (groups + groups_per_block - 1) / groups_per_block;
-        }
-    }
-    if (want > MAX_BLOCKS)
-        want = MAX_BLOCKS;
-    if (want < 1)
-        want = 1;
-    return (uint32_t)want;
-}
-
-// visited lists of a chain for a batch of n_reads (the walking methods' group kernels index them by global group number)
-uint64_t sized_path_lists(uint32_t n_reads)
-{
-    const uint64_t g = (uint64_t)pass_blocks(n_reads, walk_group()) * (256u / (uint32_t)walk_group());
-    return g < MIN_PATH_LISTS ? MIN_PATH_LISTS : g;
-}
-
 template <int G>
 void launch_one(const PassParams &p, uint32_t blocks, hipStream_t s)
 {
-    if (p.k == 19)
-        one_kernel<G, 19><<<blocks, 256, 0, s>>>(p);
-    else if (p.k == 21)
-        one_kernel<G, 21><<<blocks, 256, 0, s>>>(p);
-    else
-        one_kernel<G, 0><<<blocks, 256, 0, s>>>(p);
+    dispatch_k(p.k, [&](auto K) { one_kernel<G, decltype(K)::value><<<blocks, 256, 0, s>>>(p); });
 }
 
 } // namespace
 
 namespace brx {
 // Graph's / GapSize's group kernel over the reads p.only[0 .. *p.only_n) (8-lane groups; the visited lists of the chain
-// are sized for pass_blocks(n_reads, walk_group()) blocks of groups at least as wide, so the grid stays inside them)
-int launch_walk_list(const PassParams &p, int method, hipStream_t s)
+// are sized for blocks of groups at least as wide (sized_path_lists), so the grid stays inside them)
+int launch_walk_list(const PassParams &p, int method, uint64_t path_lists, hipStream_t s)
 {
-    const uint64_t sized_groups = sized_path_lists(p.n_reads);
-    uint32_t bl = (uint32_t)(sized_groups / 32u); // 32 eight-lane groups per block (the chain sizes at least 64 lists)
-    bl = bl < 1u ? 1u : (bl > 128u ? 128u : bl);
+    const uint32_t bl = list_grid(path_lists, 32u, 128u); // 32 eight-lane groups per block (the chain sizes at least 64 lists)
     if (method == BRX_GRAPH)
         correct_kernel<8, BRX_GRAPH, 1><<<bl, 256, 0, s>>>(p);
     else
@@ -2481,12 +2391,7 @@ int launch_walk_list(const PassParams &p, int method, hipStream_t s)
 int launch_one_list(const PassParams &p, hipStream_t s)
 {
     const uint32_t blocks = 128; // 4096 eight-lane groups; the list is a few reads, and the grid loops over it
-    if (p.k == 19)
-        one_kernel<8, 19, true><<<blocks, 256, 0, s>>>(p);
-    else if (p.k == 21)
-        one_kernel<8, 21, true><<<blocks, 256, 0, s>>>(p);
-    else
-        one_kernel<8, 0, true><<<blocks, 256, 0, s>>>(p);
+    dispatch_k(p.k, [&](auto K) { one_kernel<8, decltype(K)::value, true><<<blocks, 256, 0, s>>>(p); });
     BRX_HIP(hipGetLastError());
     return BRX_OK;
 }
@@ -2494,16 +2399,13 @@ int launch_one_list(const PassParams &p, hipStream_t s)
 
 namespace {
 
-// lanes per open trigger of the verify pass (BRX_REV_VERIFY_G = 4 / 8)
-int verify_group()
-{
-    const char *e = getenv("BRX_REV_VERIFY_G"); // (read on every use: the fuzzers sweep it)
-    return e && atoi(e) == 4 ? 4 : 8;
-}
-
+// Method M's group kernel as planned: over the whole batch (PASS_GROUP), or, after a lean reverse scan, over the triggers
+// it left open (p.trig) and over the reads it handed back (p.only)
 template <int M>
-int launch_method(const PassParams &p, int G, uint32_t blocks, size_t lds, hipStream_t s)
+int launch_method(const PassParams &p, const PassPlan &pl, uint32_t blocks, hipStream_t s)
 {
+    const int G = pl.width;
+    const size_t lds = pl.lds;
     if constexpr (M == BRX_ONE) {
         if (p.trig) { // the triggers One's lean reverse pass left open (BRX_REV_LEAN_ONE), one 8-lane group each
             correct_kernel<8, BRX_ONE, 2><<<blocks, 256, lds, s>>>(p);
@@ -2512,26 +2414,21 @@ int launch_method(const PassParams &p, int G, uint32_t blocks, size_t lds, hipSt
         if (p.only)
             return launch_one_list(p, s);
     }
-    if (M == BRX_ONE && G != 32) {
-        // (4-lane groups exist in this form only)
-        // BRX_ONE_V1=1: the first form of the kernel (A/B runs; results are identical)
-        static const bool v1 = [] { const char *e = getenv("BRX_ONE_V1"); return e && *e == '1'; }();
-        if (!v1) {
-            if (G == 4)
-                launch_one<4>(p, blocks, s);
-            else if (G == 8)
-                launch_one<8>(p, blocks, s);
-            else if (G == 16)
-                launch_one<16>(p, blocks, s);
-            else
-                launch_one<64>(p, blocks, s);
-            return BRX_OK;
-        }
+    if (M == BRX_ONE && pl.one_kernel) {
+        if (G == 4)
+            launch_one<4>(p, blocks, s);
+        else if (G == 8)
+            launch_one<8>(p, blocks, s);
+        else if (G == 16)
+            launch_one<16>(p, blocks, s);
+        else
+            launch_one<64>(p, blocks, s);
+        return BRX_OK;
     }
     if constexpr (M == BRX_GRAPH || M == BRX_GAP_SIZE) {
         if (p.trig) {
             // the triggers a lean reverse pass left open, one narrow group each (a walk step is four probes)
-            if (verify_group() == 4)
+            if (pl.verify_width == 4)
                 correct_kernel<4, M, 2><<<blocks, 256, lds, s>>>(p);
             else
                 correct_kernel<8, M, 2><<<blocks, 256, lds, s>>>(p);
@@ -2563,93 +2460,36 @@ int launch_method(const PassParams &p, int G, uint32_t blocks, size_t lds, hipSt
     return BRX_OK;
 }
 
-// Greedy needs LDS for the alignment back pointers: pick the narrowest group width that fits
-int greedy_group(int G, int k, int max_search, uint32_t *dim, uint32_t *per_group)
+// one launch of the group kernels, under `timer`; BRX_TUNE and max_search are for these kernels alone
+int launch_group(PassParams p, const PassPlan &pl, const brx_method_t &md, uint32_t blocks, const char *timer, hipStream_t s)
 {
-    *dim = (uint32_t)(k + max_search + 2);
-    *per_group = greedy_lds_bytes(*dim);
-    for (; G <= 64; G *= 2)
-        if ((uint64_t)(256 / G) * *per_group <= 160u * 1024u)
-            return G;
-    return 0;
-}
-
-int launch_pass(PassParams p, const brx_method_t &md, int G, hipStream_t s)
-{
-    static const char *names[5] = {"correct_pass", "correct_pass_two", "correct_pass_graph", "correct_pass_greedy",
-                                   "correct_pass_gap_size"};
-    const int method = md.method;
-    size_t lds = 0;
     p.max_search = md.max_search;
-    {
-        const char *e = getenv("BRX_TUNE");
-        p.flags = e ? (uint32_t)atoi(e) : 0u;
-    }
-    p.g_dim = 0;
-    p.g_lds_bytes = 0;
-    if (method == BRX_GREEDY) {
-        G = greedy_group(G, p.k, md.max_search, &p.g_dim, &p.g_lds_bytes);
-        if (!G) {
-            set_error("greedy: k=%d with max_search=%d needs a %u x %u alignment table that does not fit LDS", p.k,
-                      (int)md.max_search, p.g_dim, p.g_dim);
-            return BRX_ERR_UNSUPPORTED;
-        }
-        lds = (size_t)(256 / G) * p.g_lds_bytes;
-    }
-    uint32_t blocks = pass_blocks(p.n_reads, G, method == BRX_ONE);
-    if (p.only || p.trig) {
-        // a list is a few reads and the grid loops over it (the open triggers are many: as many groups as the visited lists
-        // the chain has sized allow); stay inside those lists (see launch_walk_list)
-        const uint64_t sized_groups = sized_path_lists(p.n_reads);
-        const uint32_t per_block = p.trig ? 256u / (uint32_t)verify_group() : 4u; // (narrow groups for the triggers, 64-lane groups for the reads)
-        blocks = (uint32_t)(sized_groups / per_block);
-        blocks = blocks < 1u ? 1u : (blocks > MAX_BLOCKS ? MAX_BLOCKS : blocks);
-    }
-    KernelTimer t(p.trig ? "rev_verify" : (p.only ? "rev_redo" : names[method]), s);
-    switch (method) {
-    case BRX_ONE: BRX_TRY(launch_method<BRX_ONE>(p, G, blocks, lds, s)); break;
-    case BRX_TWO: BRX_TRY(launch_method<BRX_TWO>(p, G, blocks, lds, s)); break;
-    case BRX_GRAPH: BRX_TRY(launch_method<BRX_GRAPH>(p, G, blocks, lds, s)); break;
-    case BRX_GREEDY: BRX_TRY(launch_method<BRX_GREEDY>(p, G, blocks, lds, s)); break;
-    case BRX_GAP_SIZE: BRX_TRY(launch_method<BRX_GAP_SIZE>(p, G, blocks, lds, s)); break;
+    p.flags = pl.flags;
+    p.g_dim = pl.g_dim;
+    p.g_lds_bytes = pl.g_lds_bytes;
+    KernelTimer t(timer, s);
+    switch (md.method) {
+    case BRX_ONE: BRX_TRY(launch_method<BRX_ONE>(p, pl, blocks, s)); break;
+    case BRX_TWO: BRX_TRY(launch_method<BRX_TWO>(p, pl, blocks, s)); break;
+    case BRX_GRAPH: BRX_TRY(launch_method<BRX_GRAPH>(p, pl, blocks, s)); break;
+    case BRX_GREEDY: BRX_TRY(launch_method<BRX_GREEDY>(p, pl, blocks, s)); break;
+    case BRX_GAP_SIZE: BRX_TRY(launch_method<BRX_GAP_SIZE>(p, pl, blocks, s)); break;
     default: break;
     }
     BRX_HIP(hipGetLastError());
     return BRX_OK;
 }
 
-// BRX_REV_LEAN=0: reverse passes of Graph / GapSize through the 64-lane group kernel as before (A/B runs,
-// and the fuzzer sweeps it)
-bool rev_lean_on()
-{
-    const char *e = getenv("BRX_REV_LEAN");
-    return !(e && *e == '0');
-}
-
-// BRX_REV_BATCH=0: the reverse scans' trigger-free rounds one at a time, as before rev_block_rounds (A/B runs, and the
-// fuzzer sweeps it)
-bool rev_batch_on()
-{
-    const char *e = getenv("BRX_REV_BATCH");
-    return !(e && *e == '0');
-}
-
 template <int M>
 void launch_rev_scan(const PassParams &p, uint32_t *list, uint32_t *flag, TrigRec *trig, uint32_t trig_cap, uint32_t blocks, hipStream_t s)
 {
-    if (p.k == 19)
-        rev_scan_kernel<19, M><<<blocks, 256, 0, s>>>(p, list, flag, trig, trig_cap);
-    else if (p.k == 21)
-        rev_scan_kernel<21, M><<<blocks, 256, 0, s>>>(p, list, flag, trig, trig_cap);
-    else
-        rev_scan_kernel<0, M><<<blocks, 256, 0, s>>>(p, list, flag, trig, trig_cap);
+    dispatch_k(p.k, [&](auto K) { rev_scan_kernel<decltype(K)::value, M><<<blocks, 256, 0, s>>>(p, list, flag, trig, trig_cap); });
 }
 
-// a reverse pass in lean form (rev_scan_kernel), then the group kernel over the reads it handed back
-int launch_rev_lean(brx_chain *ch, PassParams p, const brx_method_t &md, hipStream_t s)
+// a reverse pass in lean form (rev_scan_kernel), then the group kernel over the triggers it left open and over the reads
+// it handed back; both grids stay inside the visited lists the chain has sized (see launch_walk_list)
+int launch_rev_lean(brx_chain *ch, PassParams p, const PassPlan &pl, const brx_method_t &md, uint64_t path_lists, hipStream_t s)
 {
-    static const char *names[5] = {"correct_pass", "correct_pass_two", "correct_pass_graph", "correct_pass_greedy",
-                                   "correct_pass_gap_size"};
     // room for four open triggers per read on average (the bench's data: 1.2); a scan that finds no room hands its read back
     const uint64_t trig_cap64 = 4ull * p.n_reads + 4096ull;
     const uint32_t trig_cap = trig_cap64 > 0x7fffffffull ? 0x7fffffffu : (uint32_t)trig_cap64;
@@ -2662,16 +2502,20 @@ int launch_rev_lean(brx_chain *ch, PassParams p, const brx_method_t &md, hipStre
     BRX_HIP(hipMemsetAsync(ch->d_rev_flag, 0, (uint64_t)p.n_reads * 4ull, s));
     TrigRec *trig = (TrigRec *)ch->d_rev_trig.get();
     {
-        const uint32_t blocks = pass_blocks(p.n_reads, 64);
-        KernelTimer t(names[md.method], s);
+        KernelTimer t(pass_timer_name(md.method), s);
         switch (md.method) {
-        case BRX_ONE: launch_rev_scan<BRX_ONE>(p, ch->d_rev_list, ch->d_rev_flag, trig, trig_cap, blocks, s); break;
-        case BRX_GRAPH: launch_rev_scan<BRX_GRAPH>(p, ch->d_rev_list, ch->d_rev_flag, trig, trig_cap, blocks, s); break;
-        case BRX_GAP_SIZE: launch_rev_scan<BRX_GAP_SIZE>(p, ch->d_rev_list, ch->d_rev_flag, trig, trig_cap, blocks, s); break;
+        case BRX_ONE: launch_rev_scan<BRX_ONE>(p, ch->d_rev_list, ch->d_rev_flag, trig, trig_cap, pl.blocks, s); break;
+        case BRX_GRAPH: launch_rev_scan<BRX_GRAPH>(p, ch->d_rev_list, ch->d_rev_flag, trig, trig_cap, pl.blocks, s); break;
+        case BRX_GAP_SIZE: launch_rev_scan<BRX_GAP_SIZE>(p, ch->d_rev_list, ch->d_rev_flag, trig, trig_cap, pl.blocks, s); break;
         default: set_error("launch_rev_lean: method %u", md.method); return BRX_ERR_ARG;
         }
         BRX_HIP(hipGetLastError());
     }
+    // (a list is a few reads and the grid loops over it; the open triggers are many: as many groups as the lists allow)
+    const auto rest = [&](const PassParams &q, uint32_t groups_per_block, const char *timer) -> int {
+        BRX_HIP(hipMemsetAsync(q.ctrl + CTL_WORK, 0, 8, s));
+        return launch_group(q, pl, md, list_grid(path_lists, groups_per_block, MAX_BLOCKS), timer, s);
+    };
     // the open triggers, one narrow group each
     PassParams v = p;
     v.trig = trig;
@@ -2679,13 +2523,11 @@ int launch_rev_lean(brx_chain *ch, PassParams p, const brx_method_t &md, hipStre
     v.only_n = p.ctrl + CTL_REV_TRIGS;
     v.redo_list = ch->d_rev_list;
     v.redo_flag = ch->d_rev_flag;
-    BRX_HIP(hipMemsetAsync(p.ctrl + CTL_WORK, 0, 8, s));
-    BRX_TRY(launch_pass(v, md, 16, s));
+    BRX_TRY(rest(v, 256u / (uint32_t)pl.verify_grid_width, "rev_verify"));
     // ... and the reads whose trigger did not end in None (or that found no room for a note), from scratch
     p.only = ch->d_rev_list;
     p.only_n = p.ctrl + CTL_REV_HANDBACK;
-    BRX_HIP(hipMemsetAsync(p.ctrl + CTL_WORK, 0, 8, s));
-    return launch_pass(p, md, 16, s);
+    return rest(p, 4u, "rev_redo"); // (64-lane groups)
 }
 
 } // namespace
@@ -2710,6 +2552,14 @@ int brx_chain_second_pass(const brx_chain_t *ch)
 int brx_chain_new_pass(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, int second_pass,
                        brx_chain_t **out)
 {
+    return chain_new(set, methods, n_methods, second_pass, read_correct_tuning(), out);
+}
+
+} // extern "C"
+
+int brx::chain_new(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, int second_pass, const CorrectTuning &tuning,
+                   brx_chain_t **out)
+{
     if (!set || !out || (!methods && n_methods)) {
         set_error("null argument");
         return BRX_ERR_ARG;
@@ -2730,11 +2580,8 @@ int brx_chain_new_pass(const brx_set_t *set, const brx_method_t *methods, uint32
     ch->methods.assign(methods, methods + n_methods);
     ch->two_side = second_pass == BRX_PASS_NONE;
     ch->second_pass = second_pass;
-    if (const char *e = getenv("BRX_MAXPATH")) { // tests: a short visited list, so that walks outgrow it
-        const int v = atoi(e);
-        if (v >= 1 && v <= (1 << 20))
-            ch->maxpath_seen = (uint32_t)v;
-    }
+    if (tuning.maxpath) // (BRX_MAXPATH)
+        ch->maxpath_seen = tuning.maxpath;
     hipError_t e = hipStreamCreateWithFlags(&ch->stream, hipStreamNonBlocking);
     if (e == hipSuccess)
         e = ch->d_ctrl.reserve(CTL_N, 0, "chain control block") == BRX_OK ? hipSuccess : hipErrorOutOfMemory;
@@ -2749,6 +2596,8 @@ int brx_chain_new_pass(const brx_set_t *set, const brx_method_t *methods, uint32
     return BRX_OK;
 }
 
+extern "C" {
+
 // A handful of reads that outgrew their workspace -- a graph walk longer than the visited list (GapSize at BASELINE
 // configs[4]'s per-GPU share: 18 of 625 000) or a correction that grows the read beyond its output slot -- should not
 // cost the whole batch a second run.  Everything else of the batch is final and sits in its own slot of the last
@@ -2762,12 +2611,9 @@ struct SideRead {
     uint32_t r;
     std::vector<uint8_t> bytes;
 };
-static uint32_t redo_max_reads()
-{
-    const char *e = getenv("BRX_REDO_MAX"); // tests: 0 = never (read on every use: only overflowing batches get here)
-    return e ? (uint32_t)atoi(e) : 4096u;
-}
-static int redo_poisoned_reads(brx_chain *ch, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads,
+static int correct_batch_host(brx_chain_t *ch, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, const CorrectTuning &tuning,
+                              uint8_t **out_bases, uint64_t **out_offsets);
+static int redo_poisoned_reads(brx_chain *ch, const CorrectTuning &tuning, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads,
                                uint8_t *d_stage, uint32_t *d_lens, int stage_reversed, uint32_t slack, uint32_t sub_slack,
                                uint32_t maxpath, std::vector<SideRead> &side, hipStream_t s)
 {
@@ -2781,7 +2627,7 @@ static int redo_poisoned_reads(brx_chain *ch, const uint8_t *d_bases, const uint
     std::vector<uint32_t> ids;
     for (uint32_t r = 0; r < n_reads; r++)
         if (lens[r] == 0xffffffffu) {
-            if (ids.size() >= redo_max_reads())
+            if (ids.size() >= tuning.redo_max)
                 return BRX_ERR_UNSUPPORTED;
             ids.push_back(r);
         }
@@ -2797,7 +2643,7 @@ static int redo_poisoned_reads(brx_chain *ch, const uint8_t *d_bases, const uint
     BRX_HIP(hipStreamSynchronize(s));
     if (!ch->sub) {
         brx_chain *sub = nullptr;
-        BRX_TRY(brx_chain_new_pass(ch->set, ch->methods.data(), (uint32_t)ch->methods.size(), ch->second_pass, &sub));
+        BRX_TRY(chain_new(ch->set, ch->methods.data(), (uint32_t)ch->methods.size(), ch->second_pass, tuning, &sub));
         sub->is_sub = true;
         ch->sub = sub;
     }
@@ -2807,7 +2653,7 @@ static int redo_poisoned_reads(brx_chain *ch, const uint8_t *d_bases, const uint
         ch->sub->slack_seen = sub_slack;
     uint8_t *ob = nullptr;
     uint64_t *oo = nullptr;
-    BRX_TRY(brx_chain_correct_batch(ch->sub, mb.data(), moff.data(), (uint32_t)ids.size(), &ob, &oo));
+    BRX_TRY(correct_batch_host(ch->sub, mb.data(), moff.data(), (uint32_t)ids.size(), tuning, &ob, &oo)); // (the parent batch's switches)
     int st = BRX_OK;
     std::vector<uint8_t> rev;
     for (size_t j = 0; j < ids.size() && st == BRX_OK; j++) {
@@ -2854,7 +2700,7 @@ static int redo_poisoned_reads(brx_chain *ch, const uint8_t *d_bases, const uint
 
 // the batch entry proper; the caller holds ch->mu (a chain owns ONE workspace: staging buffers, control block, visited
 // lists -- two batches at once on one chain would share them)
-static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, const uint64_t *d_offsets,
+static int correct_batch_device_locked(brx_chain_t *ch, const CorrectTuning &tuning, const uint8_t *d_bases, const uint64_t *d_offsets,
                                        uint32_t n_reads, uint64_t total_bases, uint8_t *d_out, uint64_t out_cap,
                                        uint64_t *d_out_offsets, uint64_t *out_total, void *stream)
 {
@@ -2892,9 +2738,16 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
     if (ch->set->idx_valid && (index_wanted(k) || no_bits(ch->set)))
         idx = IdxView{ch->set->d_lines, 32u - ch->set->idx_log_lines, ch->set->idx_m, (uint32_t)k - ch->set->idx_m + 1u,
                       ch->set->idx_linebits ? (const uint32_t *)(ch->set->d_lines + (8ull << ch->set->idx_log_lines)) : nullptr};
-    if (const char *e = getenv("BRX_LINE_BITS")) // (A/B and fuzzers: 0 = do not consult the occupancy bits)
-        if (*e == '0')
-            idx.line_bits = nullptr;
+    if (!tuning.line_bits) // (BRX_LINE_BITS=0)
+        idx.line_bits = nullptr;
+    SetFacts facts;
+    facts.k = k;
+    facts.has_bits = !no_bits(ch->set);
+    facts.has_idx = idx.lines != nullptr;
+    facts.idx_log_lines = idx.lines ? 32u - idx.line_shift : 0u;
+    facts.idx_m = idx.m;
+    facts.idx_w = idx.w;
+    facts.has_line_bits = idx.line_bits != nullptr;
 
     const int n_dirs = ch->two_side ? 1 : 2;
     // BRX_PASS_REVCOMP: the second scan runs over the reverse complement of the first scan's output, materialised in the
@@ -2904,7 +2757,6 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
     const int n_methods = (int)ch->methods.size();
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::vector<SideRead> side; // redone reads that do not fit their staging slot (redo_poisoned_reads)
-    const int G = group_width(false, idx.lines != nullptr, n_reads); // forward width (8 exists for One only, else 16)
     bool needs_path = false;
     for (int m = 0; m < n_methods; m++)
         needs_path |= (ch->methods[m].method == BRX_GRAPH || ch->methods[m].method == BRX_GAP_SIZE ||
@@ -2916,12 +2768,13 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
             set_error("correction output / graph walks do not fit the workspace after 12 enlargements; giving up");
             return BRX_ERR_OVERFLOW;
         }
+        // (at least one block of the narrowest list / verify kernel); every list and verify grid of the attempt is cut from it
+        const uint64_t path_lists = sized_path_lists(tuning, n_reads);
         if (needs_path) {
-            // one visited list per group that can be resident: walking methods run 16-lane groups or wider, so a grid of
-            // pass_blocks(n_reads, 16) blocks of 16 groups bounds every width (a handful of redone reads needs a
-            // handful of lists, not 32768 of them)
-            const uint64_t n_groups = sized_path_lists(n_reads); // (at least one block of the narrowest list / verify kernel)
-            const uint64_t path_bytes = n_groups * maxpath * 8ull;
+            // one visited list per group that can be resident: walking methods run BRX_GROUP_WALK-lane groups or wider, so
+            // a grid of pass_blocks blocks of such groups bounds every width (a handful of redone reads needs a handful of
+            // lists, not 32768 of them)
+            const uint64_t path_bytes = path_lists * maxpath * 8ull;
             BRX_TRY(ch->d_path.reserve_bytes(path_bytes, ws_headroom(path_bytes), "workspace"));
         }
         const uint64_t stage_need = total_bases + (total_bases >> 2) * slack + 64ull * ((uint64_t)n_reads + 1) + 64;
@@ -2943,21 +2796,15 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
                 pp ^= 1;
             }
             for (int m = 0; m < n_methods; m++) {
+                const brx_method_t &md = ch->methods[m];
+                const uint64_t in_total_bound = cur_staged ? ch->d_stage[0].bytes() : total_bases;
+                const PassPlan plan = plan_pass(tuning, facts, md.method, md.confirm, md.max_search, dir, revcomp, cur_rev != dir, n_reads,
+                                                in_total_bound);
                 PassParams p;
-                p.bits = no_bits(ch->set) ? nullptr : ch->set->d_bits;
-                // the index pays where whole groups probe neighbouring k-mers: One's passes and the (nearly
-                // trigger-free) reverse scans of every method; walks probe 4 successors of one k-mer per round and
-                // gain nothing from shared lines.
-                const int mth = ch->methods[m].method;
-                // BRX_INDEX_FWD: bit mask (1 << method) of the methods whose FORWARD pass probes the index; measured per
-                // method (tools/method_bench.py, 1 Gbp): One 1.4x faster through it; Graph / GapSize 10-12 % faster with
-                // 8-lane groups (walk_group()); Two / Greedy (16-lane groups) see profiles/r2_one_kernel_ab.txt
-                const char *e_fwd = getenv("BRX_INDEX_FWD");
-                const unsigned idx_fwd = e_fwd ? (unsigned)atoi(e_fwd) : 29u; // One, Graph, Greedy, GapSize (Two: 69 ms through the bit vector, 72 through the index)
-                const bool use_idx = no_bits(ch->set) || ((idx_fwd >> mth) & 1u) || (dir == 1 && mth != BRX_GREEDY);
-                p.idx = use_idx ? idx : IdxView{nullptr, 0, 0, 0};
+                p.bits = facts.has_bits ? ch->set->d_bits.get() : nullptr;
+                p.idx = plan.use_idx ? idx : IdxView{nullptr, 0, 0, 0};
                 p.k = k;
-                p.c = ch->methods[m].confirm;
+                p.c = md.confirm;
                 p.n_reads = n_reads;
                 p.offsets = d_offsets;
                 p.in = cur;
@@ -2971,63 +2818,20 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
                 p.path_k = ch->d_path;
                 p.maxpath = maxpath;
                 BRX_HIP(hipMemsetAsync(ch->d_ctrl + CTL_WORK, 0, 8, s));
-                p.flags = 0;
-                // the reverse scans' trigger-free rounds in blocks (rev_block_rounds): the read runs back to front, not complemented
-                p.rev_batch = (dir == 1 && !revcomp && rev_batch_on() && rev_block_applies(p.idx)) ? 1 : 0;
+                p.flags = 0; // (BRX_TUNE and max_search: set by the group launches, for their kernels alone)
+                p.rev_batch = plan.rev_batch ? 1 : 0;
                 p.max_search = 0;
                 p.g_dim = 0;
                 p.g_lds_bytes = 0;
-                // BRX_LANE_REV (bit 0: Graph, bit 1: GapSize; default: by index size): REVERSE passes in lane form too.
-                // Their scan meets hardly a solid k-mer (the read is read back to front, not complemented), so over the
-                // solidity mask it is bit runs of sixteen positions a round -- but the rare trigger runs error_len to the
-                // END OF THE READ (hundreds of rounds of one lane, whose wave waits for it), and GapSize then walks a gap
-                // of thousands of fixed steps along the genome (a deep-coverage set has long unbranched paths), which no
-                // unit's edit list holds: the lanes hand the read back.  Measured (profiles/r4c_*, r4e_*):
-                //   2^25 lines (configs[1]'s set)     graph 65.6 -> 75.4 ms per Gbp fwd+rev, gap_size 92 -> 211 (1 845 reads redone)
-                //   2^28 lines (configs[4]'s share)   graph + gap_size 714 -> 1 598 ms per step with both (770 ms of redo)
-                //   2^29 lines, 8x coverage, -a 1     graph + gap_size 932 -> 748 ms per 8 Gbp (walks die young in a set
-                //                                     with holes: nothing is handed back)
-                //   2^28 lines (configs[4]'s share)   Graph alone in lane form: 836 -> 877 ms per step (r4f)
-                // Only the last case gains (its 64-lane group kernels take ~180 ms per 8 Gbp pass at 2^29 lines), and a
-                // deep-coverage set of that size would hand reads back like the second.  So the form is OFF unless asked
-                // for; the switch stays for measurements and for the fuzzer, which sweeps it.
-                const unsigned lane_rev_default = 0u;
-                const char *e_rev = getenv("BRX_LANE_REV");
-                const unsigned lane_rev = e_rev && *e_rev ? (unsigned)atoi(e_rev) : lane_rev_default;
-                const bool lane_dir = dir == 0 ? !p.flip
-                                               : ((mth == BRX_GRAPH && (lane_rev & 1u)) || (mth == BRX_GAP_SIZE && (lane_rev & 2u)));
-                if ((mth == BRX_ONE || mth == BRX_GRAPH || mth == BRX_GAP_SIZE) && lane_dir) {
-                    // forward passes of One, Graph and GapSize (and the reverse ones of the latter two): one lane per chunk
-                    // of a read (brx_onelane.hip) where that form applies
-                    const LanePassInfo info{cur_staged ? ch->d_stage[0].bytes() : total_bases, mth};
-                    const int lst = lane_pass(ch, p, info, s);
-                    if (lst != BRX_OK && lst != BRX_ERR_UNSUPPORTED)
-                        return lst;
-                    if (lst == BRX_OK) {
-                        cur = ch->d_stage[pp];
-                        cur_lens = ch->d_lens[pp];
-                        cur_staged = 1;
-                        cur_rev = dir;
-                        pp ^= 1;
-                        continue;
-                    }
+                switch (plan.form) {
+                case PASS_LANE: BRX_TRY(lane_pass(ch, p, plan, LanePassInfo{in_total_bound, md.method, path_lists}, s)); break;
+                case PASS_REV_LEAN: BRX_TRY(launch_rev_lean(ch, p, plan, md, path_lists, s)); break;
+                case PASS_GROUP: BRX_TRY(launch_group(p, plan, md, plan.blocks, pass_timer_name(md.method), s)); break;
+                case PASS_NO_LDS:
+                    set_error("greedy: k=%d with max_search=%d needs a %u x %u alignment table that does not fit LDS", k, (int)md.max_search,
+                              plan.g_dim, plan.g_dim);
+                    return BRX_ERR_UNSUPPORTED;
                 }
-                int gw = dir ? group_width(true, false, n_reads) : G;
-                if (gw < 16 && mth != BRX_ONE) {
-                    // the walking methods spend most of their rounds on one walk step = 4 probes: narrow groups keep the
-                    // lanes busy there (BRX_GROUP_WALK, default below); Two and Greedy need 16 lanes for their stage-1 probes
-                    gw = (mth == BRX_GRAPH || mth == BRX_GAP_SIZE) ? walk_group() : 16;
-                }
-                // (Two's and Greedy's reverse passes cost 4 ms per Gbp of their 55 / 69 in the group kernel: the lean form
-                // was measured for them, too, and bought nothing -- profiles/r4o_rev_lean_ab.txt)
-                // One's reverse pass in the same form: BRX_REV_LEAN_ONE=1 (measured: profiles/r4o_rev_lean_ab.txt)
-                const char *e_lo = getenv("BRX_REV_LEAN_ONE");
-                const bool lean_one = mth == BRX_ONE && e_lo && *e_lo == '1';
-                const bool lean = dir == 1 && (mth == BRX_GRAPH || mth == BRX_GAP_SIZE || lean_one) && gw == 64 && rev_lean_on();
-                if (lean)
-                    BRX_TRY(launch_rev_lean(ch, p, ch->methods[m], s));
-                else
-                    BRX_TRY(launch_pass(p, ch->methods[m], gw, s));
                 cur = ch->d_stage[pp];
                 cur_lens = ch->d_lens[pp];
                 cur_staged = 1;
@@ -3063,9 +2867,9 @@ static int correct_batch_device_locked(brx_chain_t *ch, const uint8_t *d_bases, 
             stats[5] += ch->h_ctrl[CTL_OVERFLOW]; // reads that outgrew their slot / walks that outgrew the list,
             stats[6] += ch->h_ctrl[CTL_PATHOVF];  // summed over the attempts that were thrown away or patched
             bool patched = false;
-            if (ch->h_ctrl[CTL_OVERFLOW] + ch->h_ctrl[CTL_PATHOVF] <= redo_max_reads()) {
+            if (ch->h_ctrl[CTL_OVERFLOW] + ch->h_ctrl[CTL_PATHOVF] <= tuning.redo_max) {
                 side.clear();
-                const int rst = redo_poisoned_reads(ch, d_bases, d_offsets, n_reads, const_cast<uint8_t *>(cur),
+                const int rst = redo_poisoned_reads(ch, tuning, d_bases, d_offsets, n_reads, const_cast<uint8_t *>(cur),
                                                     const_cast<uint32_t *>(cur_lens), cur_rev, slack,
                                                     ch->h_ctrl[CTL_OVERFLOW] ? slack * 4u : slack,
                                                     ch->h_ctrl[CTL_PATHOVF] ? maxpath * 8u : maxpath, side, s);
@@ -3142,18 +2946,37 @@ int brx_chain_correct_batch_device(brx_chain_t *ch, const uint8_t *d_bases, cons
                                    uint32_t n_reads, uint64_t total_bases, uint8_t *d_out, uint64_t out_cap,
                                    uint64_t *d_out_offsets, uint64_t *out_total, void *stream)
 {
+    return chain_correct_batch_device(ch, read_correct_tuning(), d_bases, d_offsets, n_reads, total_bases, d_out, out_cap, d_out_offsets,
+                                      out_total, stream);
+}
+
+} // extern "C"
+
+int brx::chain_correct_batch_device(brx_chain_t *ch, const CorrectTuning &tuning, const uint8_t *d_bases, const uint64_t *d_offsets,
+                                    uint32_t n_reads, uint64_t total_bases, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
+                                    uint64_t *out_total, void *stream)
+{
     if (!ch || !d_offsets || !d_out_offsets || !out_total || (!d_bases && total_bases) || (!d_out && out_cap)) {
         set_error("null argument");
         return BRX_ERR_ARG;
     }
     BRX_TRY(use_device(ch->device));
     std::lock_guard<std::mutex> g(ch->mu);
-    return correct_batch_device_locked(ch, d_bases, d_offsets, n_reads, total_bases, d_out, out_cap, d_out_offsets, out_total,
+    return correct_batch_device_locked(ch, tuning, d_bases, d_offsets, n_reads, total_bases, d_out, out_cap, d_out_offsets, out_total,
                                        stream);
 }
 
+extern "C" {
+
 int brx_chain_correct_batch(brx_chain_t *ch, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
                             uint8_t **out_bases, uint64_t **out_offsets)
+{
+    return correct_batch_host(ch, bases, offsets, n_reads, read_correct_tuning(), out_bases, out_offsets);
+}
+
+// a batch from host memory under the switches in `tuning` (read by the entry, on the caller's thread)
+static int correct_batch_host(brx_chain_t *ch, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, const CorrectTuning &tuning,
+                              uint8_t **out_bases, uint64_t **out_offsets)
 {
     if (!ch || !offsets || !out_bases || !out_offsets || (!bases && n_reads)) {
         set_error("null argument");
@@ -3205,7 +3028,7 @@ int brx_chain_correct_batch(brx_chain_t *ch, const uint8_t *bases, const uint64_
     uint64_t want = total + total / 16 + 4096;
     for (int attempt = 0; attempt < 3; attempt++) {
         BRX_TRY(ch->d_out.reserve(want, ws_headroom(want), "workspace"));
-        int st = correct_batch_device_locked(ch, ch->d_in, ch->d_off, n_reads, total, ch->d_out, ch->d_out.cap(), ch->d_out_off,
+        int st = correct_batch_device_locked(ch, tuning, ch->d_in, ch->d_off, n_reads, total, ch->d_out, ch->d_out.cap(), ch->d_out_off,
                                              &out_total, ch->stream);
         if (st == BRX_ERR_OVERFLOW && out_total > ch->d_out.cap()) {
             want = out_total + 64;
@@ -3276,8 +3099,9 @@ int brx_chain_correct_batch_async(brx_chain_t *ch, const uint8_t *bases, const u
     }
     AsyncJob *job = new AsyncJob();
     ch->async_job = job;
-    job->th = std::thread([ch, job, bases, offsets, n_reads] {
-        job->status = brx_chain_correct_batch(ch, bases, offsets, n_reads, &job->ob, &job->oo);
+    // (the switches are read here, on the caller's thread: the library's thread does not read them from the environment)
+    job->th = std::thread([ch, job, bases, offsets, n_reads, tuning = read_correct_tuning()] {
+        job->status = correct_batch_host(ch, bases, offsets, n_reads, tuning, &job->ob, &job->oo);
         if (job->status != BRX_OK)
             job->err = brx_last_error(); // (the message lives in this thread: carried over to the waiter)
     });

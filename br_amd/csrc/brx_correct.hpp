@@ -3,6 +3,9 @@
 #pragma once
 #include "brx_internal.hpp"
 #include "brx_index.hpp"
+#include "brx_plan.hpp"
+
+#include <type_traits>
 
 namespace brx {
 
@@ -69,7 +72,7 @@ struct PassParams {
     uint32_t *redo_list = nullptr;
     uint32_t *redo_flag = nullptr;
     // reverse scans: trigger-free rounds REV_BLOCK at a time through the occupancy bits (rev_block_rounds); set by the host
-    // only where rev_block_applies(idx)
+    // only where the index answers in that form (plan_pass, brx_plan.hpp)
     int rev_batch = 0;
 };
 
@@ -135,16 +138,9 @@ __device__ __forceinline__ uint64_t lane_kmer64_dpp(uint64_t carry, uint32_t cod
 #define BRX_REV_BLOCK 4 // rounds per block (tools/ab_build.sh sweeps 2 / 4 / 8)
 #endif
 constexpr int REV_BLOCK = BRX_REV_BLOCK;
-constexpr uint32_t REV_MAX_W = 8;   // windows the sliding minimum is unrolled for (m = 15: k <= 22)
+// (REV_MAX_W, the windows the sliding minimum is unrolled for, sits with the rule that admits an index: brx_plan.hpp)
 constexpr uint32_t REV_QUEUE = 128; // entries of a wave's queue
 static_assert(REV_BLOCK >= 1 && REV_BLOCK <= 16, "BRX_REV_BLOCK: 1 .. 16 rounds");
-
-// the set's index answers a reverse scan in block form (the rule lane_mask_kernel has for the occupancy bits, and a
-// window count the sliding minimum is instantiated for)
-inline bool rev_block_applies(const IdxView &v)
-{
-    return v.lines != nullptr && v.line_bits != nullptr && v.line_shift >= 6u && v.w >= 1u && v.w <= REV_MAX_W;
-}
 
 #if defined(__HIPCC__)
 // hash of the canonical form of an m-mer (f: its 2m bits, nothing above): window j = 0 of minimizer_hash_w
@@ -286,16 +282,27 @@ __device__ __forceinline__ uint32_t rev_block_rounds(const IdxView &idx, const u
 }
 #endif
 
+// the kernels specialised for k = 19 and k = 21 beside the general form: f(std::integral_constant<int, 19 / 21 / 0>)
+template <class F>
+void dispatch_k(int k, F f)
+{
+    if (k == 19)
+        f(std::integral_constant<int, 19>{});
+    else if (k == 21)
+        f(std::integral_constant<int, 21>{});
+    else
+        f(std::integral_constant<int, 0>{});
+}
+
 struct LanePassInfo {
     uint64_t in_total_bound; // upper bound of the pass's input bases (sizes the unit tables and the unit staging)
     int method;              // BRX_ONE, BRX_GRAPH or BRX_GAP_SIZE
+    uint64_t path_lists;     // visited lists the chain has sized for this attempt (the walk redo cuts its grid from them)
 };
-// One's forward pass, one lane per chunk of a read (brx_onelane.hip).  BRX_ERR_UNSUPPORTED: not applicable to this
-// pass (the caller runs the group kernel instead).
-int lane_pass(brx_chain *ch, const PassParams &p, const LanePassInfo &info, hipStream_t s);
+// A pass of One, Graph or GapSize with one lane per chunk of a read (brx_onelane.hip), as planned: plan.form is PASS_LANE.
+int lane_pass(brx_chain *ch, const PassParams &p, const PassPlan &plan, const LanePassInfo &info, hipStream_t s);
 void lane_ws_free(brx_chain *ch);
 // the group kernel over a list of reads (p.only / p.only_n), brx_correct.hip
 int launch_one_list(const PassParams &p, hipStream_t s);
-int launch_walk_list(const PassParams &p, int method, hipStream_t s);
-
+int launch_walk_list(const PassParams &p, int method, uint64_t path_lists, hipStream_t s);
 } // namespace brx

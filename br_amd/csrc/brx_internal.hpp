@@ -303,3 +303,14 @@ struct brx_chain {
     void *async_job = nullptr; // a batch in flight (brx_chain_correct_batch_async), owned by the chain
     std::mutex mu;
 };
+
+namespace brx {
+struct CorrectTuning; // the correction switches as one batch sees them (brx_plan.hpp)
+// the chain's entries under a tuning record the caller has read (brx_pipeline.hip reads one per run, on the calling
+// thread, and hands it to its workers): what brx_chain_new_pass and brx_chain_correct_batch_device do (brx_correct.hip)
+int chain_new(const brx_set_t *set, const brx_method_t *methods, uint32_t n_methods, int second_pass, const CorrectTuning &tuning,
+              brx_chain_t **out);
+int chain_correct_batch_device(brx_chain_t *ch, const CorrectTuning &tuning, const uint8_t *d_bases, const uint64_t *d_offsets,
+                               uint32_t n_reads, uint64_t total_bases, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
+                               uint64_t *out_total, void *stream);
+}

@@ -81,9 +81,7 @@ constexpr uint32_t LANE_GRAB = 64;           // units a wave draws from the glob
 // (Round 4 measured guided self-scheduling of the draws -- fewer units at a time as the pass runs out, so that no wave
 // sits on units another could take -- with finer units for the last reads of the batch: no change / 0.9 ms slower,
 // profiles/r4i_lane_tail_ab.txt.  The draws are a constant again; BRX_LANE_TAIL keeps the graded chunks for measurements.)
-#ifndef BRX_LANE_WAVES
-#define BRX_LANE_WAVES 7 // waves per SIMD the automaton is compiled for (tools/ab_build.sh sweeps it)
-#endif
+// (BRX_LANE_WAVES, the waves per SIMD the automaton is compiled for, has its default in brx_plan.hpp: the chunk rule uses it)
 
 struct UnitDesc;
 struct LaneArgs {
@@ -2150,23 +2148,13 @@ struct LaneWork {
 template <bool IDX, int M>
 void launch_lane_walk(const LaneArgs &a, uint32_t blocks, hipStream_t s)
 {
-    if (a.p.k == 19)
-        lane_walk_kernel<IDX, 19, M><<<blocks, 256, 0, s>>>(a);
-    else if (a.p.k == 21)
-        lane_walk_kernel<IDX, 21, M><<<blocks, 256, 0, s>>>(a);
-    else
-        lane_walk_kernel<IDX, 0, M><<<blocks, 256, 0, s>>>(a);
+    dispatch_k(a.p.k, [&](auto K) { lane_walk_kernel<IDX, decltype(K)::value, M><<<blocks, 256, 0, s>>>(a); });
 }
 
 template <bool IDX, bool MASK>
 void launch_lane(const LaneArgs &a, uint32_t blocks, hipStream_t s)
 {
-    if (a.p.k == 19)
-        lane_kernel<IDX, 19, MASK><<<blocks, 256, 0, s>>>(a);
-    else if (a.p.k == 21)
-        lane_kernel<IDX, 21, MASK><<<blocks, 256, 0, s>>>(a);
-    else
-        lane_kernel<IDX, 0, MASK><<<blocks, 256, 0, s>>>(a);
+    dispatch_k(a.p.k, [&](auto K) { lane_kernel<IDX, decltype(K)::value, MASK><<<blocks, 256, 0, s>>>(a); });
 }
 
 } // namespace
@@ -2185,61 +2173,20 @@ void lane_ws_free(brx_chain *ch)
     ch->lane_ws = nullptr;
 }
 
-int lane_pass(brx_chain *ch, const PassParams &p, const LanePassInfo &info, hipStream_t s)
+int lane_pass(brx_chain *ch, const PassParams &p, const PassPlan &plan, const LanePassInfo &info, hipStream_t s)
 {
-    // BRX_LANE=0: the group kernel only.  The window of a round shows 8 bases: look-aheads up to off + c + 1 <= 8.
+    // whether the form applies, and every choice below, is plan_pass's (brx_plan.hpp); this only executes the plan
     const bool walk = info.method != BRX_ONE;
-    if (env_u32("BRX_LANE", 1u) == 0u || p.k > 31 || p.n_reads == 0)
-        return BRX_ERR_UNSUPPORTED;
-    if (info.method != BRX_GRAPH && (p.c < 1 || p.c > 5)) // (Graph has no look-aheads; One and GapSize's One branch do)
-        return BRX_ERR_UNSUPPORTED;
-    if (walk && env_u32("BRX_LANE_WALK", 1u) == 0u)
-        return BRX_ERR_UNSUPPORTED;
-    // One against a LARGE index stays with the group kernel: every lane of a wave probes a line of a different read, 64
-    // unrelated pages per load, and past 2^26 lines (4 GiB) that costs more than the lanes save -- same box, correction of
-    // 2 / 3.5 / 6.25 Gbp against sets of 41 / 73 / 130 M k-mers (2^26 / 2^27 / 2^28 lines): lanes 56.6 / 132.5 / 256 ms,
-    // groups 61.0 / 107.9 / 197 ms.  (The walking methods gain at 2^28 lines all the same: their group kernels are
-    // latency-bound, BASELINE configs[4]'s share 5.1 -> 6.9 Gbases/s.)
-    if (!walk && p.idx.lines && 32u - p.idx.line_shift > env_u32("BRX_LANE_MAX_LOG_LINES", 26u))
-        return BRX_ERR_UNSUPPORTED;
     const bool idx = p.idx.lines != nullptr;
-    if (!idx && !p.bits)
-        return BRX_ERR_UNSUPPORTED;
-    // chunk length: enough units to keep ~4.6e5 lanes busy a few times over, not so short that the stretch a unit's
-    // predecessor re-scans in front of its sync point (a few dozen bases) becomes the larger part
-    constexpr uint64_t RESIDENT = 256ull * 4ull * BRX_LANE_WAVES * 64ull;
-    uint32_t C = env_u32("BRX_LANE_CHUNK", 0u);
-    if (C == 0u) {
-        // (measured at configs[1], same box: 256 -> 11.7 ms per launch, 512 -> 11.65, 768 -> 12.4, 1090 -> 12.6, 2048 -> 16.7:
-        // a lane should get about four units, or the lanes that got one more than the others run the tail alone)
-        const uint64_t want = info.in_total_bound / (4ull * RESIDENT);
-        C = want < 256ull ? 256u : (want > 2048ull ? 2048u : (uint32_t)want);
-    }
-    if (C < 64u)
-        C = 64u;
-    uint32_t R = env_u32("BRX_LANE_SYNC", 4u);
-    if (R < 1u)
-        R = 1u;
-    if (R > 32u)
-        R = 32u;
+    const uint32_t C = plan.chunk, R = plan.sync;
+    const uint64_t units_bound = plan.units_bound;
+    const bool use_mask = plan.use_mask;
 
     LaneWork *w = (LaneWork *)ch->lane_ws;
     if (!w) {
         w = new LaneWork();
         ch->lane_ws = w;
     }
-    // BRX_LANE_TAIL=1: the last fifth of the batch's reads is cut at C / 2, the last twentieth at C / 4 (chunk_of).  OFF by
-    // default: measured at configs[1] (profiles/r4i_lane_tail_ab.txt) the pass got 0.9 ms SLOWER (2.35 M units instead of
-    // 1.8 M: every unit start stalls its wave, and the sync / replay kernels grow with the units), as did guided draws
-    // (no change) -- the thinning tail of the launch is not where its time goes.
-    // (One only: a walking corrector's fix has to fit its unit's list, and short units hand more reads back)
-    const bool graded = !walk && env_u32("BRX_LANE_TAIL", 0u) != 0u && p.n_reads >= 64u;
-    const uint32_t r_half = graded ? p.n_reads - p.n_reads / 5u : 0xffffffffu;
-    const uint32_t r_quarter = graded ? p.n_reads - p.n_reads / 20u : 0xffffffffu;
-    const uint32_t c_min = graded ? ((C >> 2) < 64u ? 64u : (C >> 2)) : C;
-    const uint64_t units_bound = info.in_total_bound / c_min + (uint64_t)p.n_reads + 1ull;
-    if (units_bound >= 0xfffffff0ull)
-        return BRX_ERR_UNSUPPORTED;
     const uint64_t p_bound = (info.in_total_bound >> 4) + 5ull * p.n_reads + 16ull;                        // dwords
     const uint64_t e_bound = (info.in_total_bound >> 2) + 16ull * (units_bound + 2ull * p.n_reads) + 64ull; // entries
     const char *what = "lane pass workspace";
@@ -2268,8 +2215,8 @@ int lane_pass(brx_chain *ch, const PassParams &p, const LanePassInfo &info, hipS
     LaneArgs a;
     a.p = p;
     a.C = C;
-    a.r_half = r_half;
-    a.r_quarter = r_quarter;
+    a.r_half = plan.r_half;
+    a.r_quarter = plan.r_quarter;
     a.R = R;
     a.nu = w->nu;
     a.ubase = w->ubase;
@@ -2280,14 +2227,6 @@ int lane_pass(brx_chain *ch, const PassParams &p, const LanePassInfo &info, hipS
     a.u_desc = w->u_desc;
     a.u_in = w->u_in;
     a.P = w->P;
-    // BRX_LANE_MASK: the solidity mask of the original k-mers (lane_mask_kernel) -- 0: never, every SCAN / error_len
-    // position is probed; 1: for the walking correctors, whose error_len it shortens to a bit scan (rounds 1.97 G -> 0.96 G
-    // per Gbp for Graph; both launches 65.0 -> 52.6 ms with 10.2 ms of mask kernel to pay for it; BASELINE configs[4]'s
-    // share, 2^28 index lines: 6.58 -> 7.13 Gbases/s on one box); 2: for One as well (there the mask kernel costs what the
-    // shorter scan saves: rounds 1.24 G -> 0.59 G, launch 16 -> 12 ms, mask 8.7 ms).  Either way the index lines fetched
-    // are the same ones: the mask kernel fetches them for 64 neighbouring positions at a time instead of lane by lane.
-    const uint32_t mask_mode = env_u32("BRX_LANE_MASK", 1u);
-    const bool use_mask = walk ? mask_mode >= 1u : mask_mode >= 2u;
     a.M = use_mask ? w->M : nullptr;
     for (int d = 0; d < MAX_DEPTH; d++) {
         a.E[d] = w->E[d];
@@ -2307,7 +2246,7 @@ int lane_pass(brx_chain *ch, const PassParams &p, const LanePassInfo &info, hipS
         a.dbg = d_dbg;
     }
 #endif
-    if (walk && idx && env_u32("BRX_LANE_SUCC", 1u) != 0u) {
+    if (plan.use_succ) {
         // the successor table of the set's index: built the first time a walking corrector runs on it, again when the
         // index has changed since
         brx_set *set = const_cast<brx_set *>(ch->set);
@@ -2368,8 +2307,7 @@ int lane_pass(brx_chain *ch, const PassParams &p, const LanePassInfo &info, hipS
         lane_link_kernel<<<(uint32_t)(lb < 4096ull ? lb : 4096ull), 256, 0, s>>>(a);
     }
     {
-        static const char *names[5] = {"correct_pass", "correct_pass_two", "correct_pass_graph", "correct_pass_greedy", "correct_pass_gap_size"};
-        KernelTimer t(names[info.method], s);
+        KernelTimer t(pass_timer_name(info.method), s);
         const uint64_t want = (units_bound + 255ull) / 256ull;
         const uint64_t waves = walk ? (uint64_t)walk_waves(info.method) : (use_mask ? 6ull : (uint64_t)BRX_LANE_WAVES);
         const uint32_t blocks = (uint32_t)(want < 256ull * waves ? want : 256ull * waves);
@@ -2419,9 +2357,7 @@ int lane_pass(brx_chain *ch, const PassParams &p, const LanePassInfo &info, hipS
     }
     {
         KernelTimer t("lane_apply", s);
-        // (BRX_AP_GRID: blocks of the replay kernels; each block loops over reads)
-        const uint32_t gcap = env_u32("BRX_AP_GRID", 1u << 20);
-        const uint32_t grid = p.n_reads < gcap ? p.n_reads : gcap;
+        const uint32_t grid = p.n_reads < plan.ap_grid ? p.n_reads : plan.ap_grid; // (each block loops over reads)
         if (walk)
             lane_apply_walk_kernel<<<grid, 256, 0, s>>>(a);
         else
@@ -2435,7 +2371,7 @@ int lane_pass(brx_chain *ch, const PassParams &p, const LanePassInfo &info, hipS
         q.only_n = p.ctrl + CTL_LANE_FAIL;
         BRX_HIP(hipMemsetAsync(p.ctrl + CTL_WORK, 0, 8, s));
         if (walk)
-            BRX_TRY(launch_walk_list(q, info.method, s));
+            BRX_TRY(launch_walk_list(q, info.method, info.path_lists, s));
         else
             BRX_TRY(launch_one_list(q, s));
     }

@@ -12,6 +12,7 @@
 // Batches are larger than the reference's 8192 records (reads are independent units and the output keeps
 // the input order, so the batch size cannot change a byte); they are what fills the GPU.
 #include "brx_internal.hpp"
+#include "brx_plan.hpp"
 
 #include <algorithm>
 #include <condition_variable>
@@ -658,7 +659,7 @@ int cover_one_batch(const brx_set_t *set, const OutOpts &oo, DevBufs &dv, hipStr
     return BRX_OK;
 }
 
-int correct_one_batch(brx_chain_t *chain, DevBufs &dv, hipStream_t s, Batch &b, const OutOpts &oo)
+int correct_one_batch(brx_chain_t *chain, const CorrectTuning &tuning, DevBufs &dv, hipStream_t s, Batch &b, const OutOpts &oo)
 {
     const uint32_t n = b.n();
     b.text_len = 0;
@@ -676,12 +677,12 @@ int correct_one_batch(brx_chain_t *chain, DevBufs &dv, hipStream_t s, Batch &b, 
         BRX_HIP(hipStreamSynchronize(s));
     const double t2 = now_s();
     uint64_t out_total = 0;
-    int st = brx_chain_correct_batch_device(chain, dv.d_in, dv.d_off, n, b.total, dv.d_out, dv.d_out.cap(), dv.d_out_off,
-                                            &out_total, s);
+    int st = chain_correct_batch_device(chain, tuning, dv.d_in, dv.d_off, n, b.total, dv.d_out, dv.d_out.cap(), dv.d_out_off,
+                                        &out_total, s);
     if (st == BRX_ERR_OVERFLOW && out_total > dv.d_out.cap()) { // corrections grew the batch beyond the estimate
         BRX_TRY(dv.d_out.reserve(out_total + out_total / 16 + 4096, 0, "corrected batch"));
-        st = brx_chain_correct_batch_device(chain, dv.d_in, dv.d_off, n, b.total, dv.d_out, dv.d_out.cap(), dv.d_out_off,
-                                            &out_total, s);
+        st = chain_correct_batch_device(chain, tuning, dv.d_in, dv.d_off, n, b.total, dv.d_out, dv.d_out.cap(), dv.d_out_off,
+                                        &out_total, s);
     }
     BRX_TRY(st);
     b.out_total = out_total;
@@ -825,6 +826,9 @@ int run_correction_impl(const brx_set_t *set, const brx_method_t *methods, uint3
         BRX_TRY(write_all(oo.report_fd, head, sizeof head - 1));
     }
     const int device = set->device;
+    // the correction switches of the run, read once and here: the workers below are the library's threads and get
+    // them as a record, not from the environment
+    const CorrectTuning tuning = read_correct_tuning();
     const double t_start = now_s();
     std::vector<Batch> slots(N_SLOTS);
     Queue<Batch *> q_free, q_ready;
@@ -877,7 +881,7 @@ int run_correction_impl(const brx_set_t *set, const brx_method_t *methods, uint3
         DevBufs dv;
         int st = use_device(device);
         if (st == BRX_OK)
-            st = brx_chain_new_pass(set, methods, n_methods, second_pass, &chain);
+            st = chain_new(set, methods, n_methods, second_pass, tuning, &chain);
         if (st == BRX_OK && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) {
             set_error("hipStreamCreate failed");
             st = BRX_ERR_HIP;
@@ -888,7 +892,7 @@ int run_correction_impl(const brx_set_t *set, const brx_method_t *methods, uint3
         while (q_ready.pop(b)) {
             if (!sh.failed()) {
                 const double t0 = now_s();
-                st = correct_one_batch(chain, dv, s, *b, oo); // (leaves the batch's FASTA text in b->text)
+                st = correct_one_batch(chain, tuning, dv, s, *b, oo); // (leaves the batch's FASTA text in b->text)
                 const double dt = now_s() - t0;
                 if (st != BRX_OK)
                     sh.fail(st);
