@@ -8,7 +8,7 @@
 //   stats    = kmers, absent = hist[0], above = #(count > abundance), min, lower median, max, sum.
 //
 // One lookup per k-mer of the batch, asked the way cover_kernel (brx_cover.hip) asks: the batch is cut BY POSITION into a
-// work list of tiles (read, first position) built from the offsets, a wave takes a tile of ABUND_TILE positions and walks
+// work list of tiles (read, first position) built from the offsets, a wave takes a tile of READ_TILE positions (brx_tiles.hpp) and walks
 // it 64 neighbouring positions per step, so that neighbours share their table lines.  The k-mers come from the DPP scan
 // of brx_correct.hpp, indexed by their LAST base e: count[e-k+1].  A tile needs no look-behind (nothing is carried from
 // position to position but the k-mer itself): it starts its scan at its first base with an empty carry, skips the k-1
@@ -25,18 +25,11 @@
 // geometry or on timing.  abund_stats_kernel, a wave per read, turns the 256 bins into the statistics: a prefix sum over
 // the bins finds the median, no sort and no floating point.  The rows are the caller's d_hist, or scratch from the pool.
 #include "brx_correct.hpp"
+#include "brx_tiles.hpp"
 
 using namespace brx;
 
-namespace brx {
-uint64_t scan_tmp_bytes(uint32_t n);
-int exclusive_scan_lens(const uint32_t *d_lens, uint32_t n, uint64_t *d_tmp, uint64_t *d_out_offsets,
-                        unsigned long long *d_total, hipStream_t s);
-}
-
 namespace {
-
-constexpr uint32_t ABUND_TILE = 1024; // positions of a read per wave: 16 steps of 64, a 17th for the k-1 bases behind them
 
 enum { SRC_NONE = 0, SRC_DENSE = 1, SRC_TABLE = 2, SRC_PART = 3 }; // what answers: nothing counted yet, the u8 table, the counting table, a partitioned counter's view
 
@@ -55,34 +48,12 @@ struct AbundArgs {
     uint32_t n_reads;
     const uint8_t *bases;
     const uint64_t *offsets;
-    // work list
-    uint32_t *tiles_of;          // tiles per read              [n_reads]
-    uint64_t *tile_base;         // exclusive scan of tiles_of  [n_reads + 1]
-    uint32_t *tile_read;         // read of a tile              [tiles]
-    unsigned long long *n_tiles; // = tile_base[n_reads]
+    TileList tl; // work list (brx_tiles.hpp)
     // outputs, each may be null
     uint8_t *profile;
     uint32_t *hist; // 256 per read
     brx_abund_stats_t *stats;
 };
-
-__global__ __launch_bounds__(256) void abund_tiles_of_kernel(AbundArgs a)
-{
-    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-    if (r >= a.n_reads)
-        return;
-    const uint64_t n = a.offsets[r + 1] - a.offsets[r];
-    a.tiles_of[r] = (uint32_t)((n + ABUND_TILE - 1u) / ABUND_TILE);
-}
-
-__global__ __launch_bounds__(256) void abund_tile_list_kernel(AbundArgs a)
-{
-    for (uint32_t r = blockIdx.x; r < a.n_reads; r += gridDim.x) {
-        const uint64_t tb = a.tile_base[r], te = a.tile_base[r + 1];
-        for (uint64_t t = tb + threadIdx.x; t < te; t += 256)
-            a.tile_read[t] = r;
-    }
-}
 
 // the counter's value for one forward k-mer
 template <int SRC>
@@ -119,15 +90,13 @@ template <int SRC>
 __global__ __launch_bounds__(256) void abund_kernel(AbundArgs a)
 {
     __shared__ uint32_t bins[4][256];
-    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const unsigned long long tile = (unsigned long long)blockIdx.x * 4ull + wv;
-    if (tile >= *a.n_tiles)
+    TileView t;
+    unsigned long long tile;
+    if (!tile_view(a.tl, a.offsets, t, tile))
         return;
-    const uint32_t r = a.tile_read[tile];
-    const uint64_t o0 = a.offsets[r];
-    const uint32_t n = (uint32_t)(a.offsets[r + 1] - o0);
-    const uint32_t p0 = (uint32_t)(tile - a.tile_base[r]) * ABUND_TILE;
-    const uint32_t p1 = n - p0 < ABUND_TILE ? n : p0 + ABUND_TILE;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t r = t.r, n = t.n, p0 = t.p0, p1 = t.p1;
+    const uint64_t o0 = t.o0;
     const int lane = threadIdx.x & 63;
     const uint32_t k = (uint32_t)a.k;
     const uint64_t mask = kmask(a.k);
@@ -148,8 +117,7 @@ __global__ __launch_bounds__(256) void abund_kernel(AbundArgs a)
         const uint32_t e = eb + (uint32_t)lane;
         const uint8_t c = e < elim ? in[e] : (uint8_t)0;
         const uint64_t km = lane_kmer64_dpp(carry, (c >> 1) & 3u, lane, mask);
-        carry = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(km >> 32), 63) << 32) |
-                (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)km, 63);
+        carry = wave_carry(km);
         if (e < elim && e - p0 + 1u >= k) { // the k-mer is whole: it starts at e-k+1 >= p0
             const uint32_t cnt = abund_count<SRC>(a, km);
             if (a.profile)
@@ -289,27 +257,12 @@ int abund_enqueue(const brx_counter *c, AbundArgs &a, uint64_t total_bases, DevS
     int src = SRC_NONE;
     BRX_TRY(abund_view(c, "abundance", a, src));
     const uint32_t n_reads = a.n_reads;
-    const uint64_t tile_bound = total_bases / ABUND_TILE + n_reads;
-    if (tile_bound / 4ull + 1ull > 0x7fffffffull) {
-        set_error("abundance: batch of %llu bases in %u reads is too large for one call", (unsigned long long)total_bases, n_reads);
-        return BRX_ERR_ARG;
-    }
-    uint64_t *tmp = nullptr;
-    BRX_TRY(sc.get(&a.tiles_of, n_reads));
-    BRX_TRY(sc.get(&a.tile_base, (uint64_t)n_reads + 1));
-    BRX_TRY(sc.get(&a.tile_read, tile_bound));
-    BRX_TRY(sc.get(&a.n_tiles, 1));
-    BRX_TRY(sc.get(&tmp, scan_tmp_bytes(n_reads) / 8 + 1));
+    uint64_t tile_bound = 0;
+    BRX_TRY(tile_list_enqueue(a.tl, a.offsets, n_reads, total_bases, "abundance", "abund_tiles", sc, tile_bound, s));
     if (a.stats && !a.hist)
         BRX_TRY(sc.get(&a.hist, (uint64_t)n_reads * 256ull));
     if (a.hist)
         BRX_HIP(hipMemsetAsync(a.hist, 0, (uint64_t)n_reads * 1024ull, s));
-    {
-        KernelTimer t("abund_tiles", s);
-        abund_tiles_of_kernel<<<(n_reads + 255u) / 256u, 256, 0, s>>>(a);
-        BRX_TRY(exclusive_scan_lens(a.tiles_of, n_reads, tmp, a.tile_base, a.n_tiles, s));
-        abund_tile_list_kernel<<<read_grid(n_reads, 2048u), 256, 0, s>>>(a);
-    }
     {
         KernelTimer t("abund", s);
         const uint32_t grid = (uint32_t)((tile_bound + 3ull) / 4ull);

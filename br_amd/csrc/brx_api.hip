@@ -37,6 +37,33 @@ int use_device(int device)
     return BRX_OK;
 }
 
+int check_batch_args(const char *what, const void *bases, const uint64_t *offsets, uint32_t n_reads, uint64_t total_bases)
+{
+    if ((n_reads && !offsets) || (total_bases && !bases)) {
+        set_error("%s: null bases / offsets for %u reads, %llu bases", what, n_reads, (unsigned long long)total_bases);
+        return BRX_ERR_ARG;
+    }
+    if (total_bases && !n_reads) {
+        set_error("%s: %llu bases in no reads", what, (unsigned long long)total_bases);
+        return BRX_ERR_ARG;
+    }
+    return BRX_OK;
+}
+
+int check_offsets(const char *what, const uint64_t *offsets, uint32_t n_reads, bool strand_rule)
+{
+    const uint64_t longest = strand_rule ? 0xfffffffeull : 0xfffffff0ull;
+    for (uint32_t r = 0; r < n_reads; r++)
+        if (offsets[r + 1] < offsets[r] || offsets[r + 1] - offsets[r] > longest || (!strand_rule && r == 0 && offsets[0] != 0)) {
+            if (strand_rule)
+                set_error("%s: offsets must not decrease and a read holds fewer than 2^32 - 1 bases (read %u)", what, r);
+            else
+                set_error("%s: offsets must start at 0 and not decrease; a read holds fewer than 2^32 - 16 bases (read %u)", what, r);
+            return BRX_ERR_ARG;
+        }
+    return BRX_OK;
+}
+
 void trace_stage(hipStream_t s, const char *what)
 {
     static const bool on = [] { const char *e = getenv("BRX_TRACE"); return e && *e && *e != '0'; }();
@@ -321,15 +348,7 @@ static int abund_check(const char *what, const brx_counter_t *c, const void *bas
     }
     if (c->strategy == BRX_COUNT_SORTED && !part_lookup_ready(c))
         return abund_refuse_partitioned(what, c->k);
-    if ((n_reads && !offsets) || (total_bases && !bases)) {
-        set_error("%s: null bases / offsets for %u reads, %llu bases", what, n_reads, (unsigned long long)total_bases);
-        return BRX_ERR_ARG;
-    }
-    if (total_bases && !n_reads) {
-        set_error("%s: %llu bases in no reads", what, (unsigned long long)total_bases);
-        return BRX_ERR_ARG;
-    }
-    return BRX_OK;
+    return check_batch_args(what, bases, offsets, n_reads, total_bases);
 }
 
 // the body of both batch entries; the caller holds c->mu
@@ -371,11 +390,7 @@ int brx_counter_abundance_batch(brx_counter_t *c, const uint8_t *bases, const ui
     }
     const uint64_t total = n_reads ? offsets[n_reads] : 0;
     BRX_TRY(abund_check(me, c, bases, offsets, n_reads, total));
-    for (uint32_t r = 0; r < n_reads; r++)
-        if (offsets[r + 1] < offsets[r] || offsets[r + 1] - offsets[r] > 0xfffffff0ull || (r == 0 && offsets[0] != 0)) {
-            set_error("%s: offsets must start at 0 and not decrease; a read holds fewer than 2^32 - 16 bases (read %u)", me, r);
-            return BRX_ERR_ARG;
-        }
+    BRX_TRY(check_offsets(me, offsets, n_reads));
     BRX_TRY(use_device(c->device));
     if (!n_reads || (!profile && !hist && !stats))
         return BRX_OK;

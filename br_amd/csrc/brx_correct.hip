@@ -34,14 +34,6 @@
 
 using namespace brx;
 
-namespace brx {
-uint64_t scan_tmp_bytes(uint32_t n);
-int exclusive_scan_lens(const uint32_t *d_lens, uint32_t n, uint64_t *d_tmp, uint64_t *d_out_offsets,
-                        unsigned long long *d_total, hipStream_t s);
-int upload_batch(const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, DevBuf<uint8_t> &d_bases, DevBuf<uint64_t> &d_off,
-                 uint64_t *total, hipStream_t stream);
-}
-
 namespace {
 
 enum { ST_INIT = 0, ST_SCAN, ST_ERRLEN, ST_ALTS, ST_SCEN, ST_MORE, ST_WALK, ST_T1, ST_TSCORE, ST_TMORE, ST_GFOLLOW, ST_GVALID };
@@ -555,9 +547,9 @@ __global__ __launch_bounds__(256, (M == BRX_ONE ? (G == 64 ? 7 : 6)
                 if (HAS_ERRLEN && i + (uint32_t)lane < skip_until) {
                     // (known not solid: error_len asked about it behind the trigger that failed)
                 } else if (p.idx.lines) {
-                    // (an overflowed index line is settled by the lane that met it, index_get: leaving the round to the
+                    // (an overflowed index line is settled by the lane that met it, set_get: leaving the round to the
                     // general code and its re-run cost two full rounds of the group, ten times per 10 kb read)
-                    s1 = index_get(p.idx, p.bits, km, k);
+                    s1 = set_get<true, LINE_BITS_KEPT>(p.idx, p.bits, km, k);
                 } else {
                     s1 = probe(p.bits, km, k);
                 }
@@ -568,8 +560,7 @@ __global__ __launch_bounds__(256, (M == BRX_ONE ? (G == 64 ? 7 : 6)
                 out[olen + (uint32_t)lane] = c8; // mod.rs:100
                 olen += 64u;
                 i += 64u;
-                kmer = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(km >> 32), 63) << 32) |
-                       (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)km, 63);
+                kmer = wave_carry(km);
                 prev = (bs >> 63) & 1ull; // mod.rs:99
                 n_rounds += 1u;
                 n_probes += 64u;
@@ -583,11 +574,10 @@ __global__ __launch_bounds__(256, (M == BRX_ONE ? (G == 64 ? 7 : 6)
             while (HAS_ERRLEN && have && st == ST_ERRLEN && !slow && n - i > ej + 1u + 64u) {
                 const uint8_t c8 = ld(i + ej + 1u + (uint32_t)lane);
                 const uint64_t km = lane_kmer64_dpp(ek, (uint32_t)nuc2bit(c8), lane, mask);
-                const bool s1 = p.idx.lines ? index_get(p.idx, p.bits, km, k) : probe(p.bits, km, k);
+                const bool s1 = p.idx.lines ? set_get<true, LINE_BITS_KEPT>(p.idx, p.bits, km, k) : probe(p.bits, km, k);
                 if (__ballot(s1))
                     break;
-                ek = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(km >> 32), 63) << 32) |
-                     (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)km, 63);
+                ek = wave_carry(km);
                 ej += 64u;
                 n_rounds += 1u;
                 n_probes += 64u;
@@ -1639,8 +1629,8 @@ __global__ __launch_bounds__(256, (G == 64 ? BRX_ONE64_WAVES : 7)) void one_kern
                 const uint8_t c8 = ld(i + (uint32_t)lane);
                 uint32_t sc;
                 const uint64_t km = lane_kmer(kmer, (uint32_t)nuc2bit(c8), sc);
-                // (an overflowed index line is settled by the lane that met it, index_get)
-                const bool s1 = p.idx.lines ? index_get(p.idx, p.bits, km, k) : probe(p.bits, km, k);
+                // (an overflowed index line is settled by the lane that met it, set_get)
+                const bool s1 = p.idx.lines ? set_get<true, LINE_BITS_KEPT>(p.idx, p.bits, km, k) : probe(p.bits, km, k);
                 const uint64_t bs = __ballot(s1);
                 const uint64_t trig = ~bs & ((bs << 1) | (prev ? 1ull : 0ull)); // mod.rs:73
                 if (trig)
@@ -1648,8 +1638,7 @@ __global__ __launch_bounds__(256, (G == 64 ? BRX_ONE64_WAVES : 7)) void one_kern
                 out[olen + (uint32_t)lane] = c8; // mod.rs:100
                 olen += 64u;
                 i += 64u;
-                kmer = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(km >> 32), 63) << 32) |
-                       (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)km, 63);
+                kmer = wave_carry(km);
                 prev = (bs >> 63) & 1ull; // mod.rs:99
                 ev += ((lane == 0) ? 1u : 0u) + (1u << 8);
                 steps++;
@@ -2126,7 +2115,7 @@ __global__ __launch_bounds__(256, BRX_REV_WAVES) void rev_scan_kernel(const Pass
     // lines -- the next lines of the chain, while its wave waits.
     // (always_inline: left to itself the compiler CALLS the probe from the three places that ask -- s_swappc, registers saved
     // through lanes and scratch -- and the scan ran at 9.1 ms per Gbp where one_kernel<64>'s identical loop takes 5.7)
-    auto ask = [&](uint64_t km) __attribute__((always_inline)) -> bool { return idx.lines ? index_get(idx, bits, km, k) : probe(bits, km, k); };
+    auto ask = [&](uint64_t km) __attribute__((always_inline)) -> bool { return idx.lines ? set_get<true, LINE_BITS_KEPT>(idx, bits, km, k) : probe(bits, km, k); };
     auto last_of = [&](uint64_t km, uint32_t l) __attribute__((always_inline)) -> uint64_t {
         return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(km >> 32), (int)l) << 32) |
                (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)km, (int)l);
@@ -2734,12 +2723,7 @@ static int correct_batch_device_locked(brx_chain_t *ch, const CorrectTuning &tun
             }
     // probe index of the set (built here when the set has none yet, e.g. after a finish_into)
     BRX_TRY(index_ensure(ch->set, s));
-    IdxView idx{nullptr, 0, 0, 0};
-    if (ch->set->idx_valid && (index_wanted(k) || no_bits(ch->set)))
-        idx = IdxView{ch->set->d_lines, 32u - ch->set->idx_log_lines, ch->set->idx_m, (uint32_t)k - ch->set->idx_m + 1u,
-                      ch->set->idx_linebits ? (const uint32_t *)(ch->set->d_lines + (8ull << ch->set->idx_log_lines)) : nullptr};
-    if (!tuning.line_bits) // (BRX_LINE_BITS=0)
-        idx.line_bits = nullptr;
+    const IdxView idx = set_view(ch->set, tuning.line_bits).idx;
     SetFacts facts;
     facts.k = k;
     facts.has_bits = !no_bits(ch->set);

@@ -81,13 +81,6 @@ __host__ __device__ __forceinline__ uint64_t slot_of(uint64_t o, uint64_t r, uin
     return o + (o >> 2) * (uint64_t)slack + 64ull * r;
 }
 
-__device__ __forceinline__ bool probe(const uint32_t *__restrict__ bits, uint64_t fwd, int k)
-{
-    const uint64_t h = khash(fwd, k);
-    return (bits[h >> 5] >> (h & 31u)) & 1u;
-}
-
-
 #if defined(__HIPCC__)
 template <int D>
 __device__ __forceinline__ uint32_t dpp_row_shr(uint32_t v)
@@ -118,18 +111,24 @@ __device__ __forceinline__ uint64_t lane_kmer64_dpp(uint64_t carry, uint32_t cod
     const uint32_t jb = 2u * ((uint32_t)(lane & 15) + 1u);
     return (((((uint64_t)b2 << 32) | b1) << jb) | v) & mask; // jb <= 32
 }
+// the k-mer of lane 63, as a wave-uniform value: the next step's `carry`
+__device__ __forceinline__ uint64_t wave_carry(uint64_t km)
+{
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(km >> 32), 63) << 32) |
+           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)km, 63);
+}
 #endif
 
 // ----------------------------------------------------------------------------------------------------------------------
 // Trigger-free scan rounds of a reverse pass, REV_BLOCK at a time (one wave per read: one_kernel<64>, correct_kernel<64>,
 // rev_scan_kernel).  Nearly every k-mer of a reversed read is absent and four index lines in five are empty, so a round
-// of 64 positions, one index_get each, makes the whole wave pay for the key, the line fetch and the slot compares of
+// of 64 positions, one set_get each, makes the whole wave pay for the key, the line fetch and the slot compares of
 // the dozen lanes whose home line holds anything.  Here a round only FILTERS: the lane hashes the newest m-mer of its
 // k-mer, takes the minimum over itself and its w - 1 left neighbours (wave_shr DPP moves; the hashes in front of the
 // wave's span come from the carried k-mer, in scalar arithmetic), and loads the occupancy bit of that line.  Lanes whose bit is set queue
 // (k-mer, line, round << 6 | lane) in LDS; when the block's rounds are through -- or the queue has fewer than 64 places
 // left -- the queue is drained a wave at a time: reverse complement, key, index_probe_at, "cannot say" settled on the
-// spot as index_get does.  A solid k-mer ORs its bit into the block's answer words; the trigger test then runs over
+// spot as set_get does.  A solid k-mer ORs its bit into the block's answer words; the trigger test then runs over
 // those words as it does over a round's ballot.  Probes are pure, so only their order and grouping differ.
 // LDS per wave: 128 entries of 16 bytes + REV_BLOCK answer words + REV_BLOCK carried k-mers = 2 112 bytes at REV_BLOCK = 4,
 // 8 448 per block of 256: 28 waves of a CU (7 per SIMD) take 59 KB of its 160.
@@ -199,6 +198,7 @@ __device__ __forceinline__ uint32_t rev_block_rounds(const IdxView &idx, const u
             outp[64u * r + (uint32_t)ln] = c8; // mod.rs:100, ahead of the answer: a round that is not committed is written again
             if (ln == 63)
                 carry[r] = km;
+            // (wave_carry(km), written out: through the call every kernel that comes here is scheduled differently)
             cur_carry = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(km >> 32), 63) << 32) |
                         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)km, 63);
             const uint32_t h = mmer_hash((uint32_t)km & mm, m);
@@ -235,7 +235,7 @@ __device__ __forceinline__ uint32_t rev_block_rounds(const IdxView &idx, const u
                 const uint64_t rc = revcomp(fwd, k);
                 const uint64_t key = (((popc64(fwd) & 1) ? rc : fwd) >> 1) + 1ull;
                 int a = index_probe_at(idx, key, e.z, 0u);
-                if (a == 2) { // "cannot say": settled here, as index_get does
+                if (a == 2) { // "cannot say": settled here, as set_get does
                     if (bits) {
                         const uint64_t hh = key - 1ull; // khash(fwd, k)
                         a = (bits[hh >> 5] >> (hh & 31u)) & 1u;

@@ -9,8 +9,8 @@
 // One probe per k-mer of the batch, asked the way lane_mask_kernel (brx_onelane.hip) asks: 64 neighbouring positions of
 // one read per wave step, so that neighbours share their index lines, through whatever holds the set (bit vector; key
 // list + probe index, occupancy bits first; chained table).  Unlike that kernel this one reads the ASCII bytes of a plain
-// bases / offsets batch and is cut BY POSITION: a work list of tiles (read, first position) is built from the offsets,
-// a wave takes a tile of COVER_TILE positions, and a 62 163-base read keeps 61 waves busy while a 157-base read costs one.
+// bases / offsets batch and is cut BY POSITION: a wave takes a tile of READ_TILE positions from the work list of
+// brx_tiles.hpp.
 //
 // Inside a wave the k-mers are indexed by their LAST base e (the DPP scan of brx_correct.hpp builds them that way):
 // w[e] = solid[e-k+1].  Then covered[j] = OR of w[j .. j+k-1], which looks FORWARD: the ballot word of a step is held
@@ -26,22 +26,14 @@
 // batch belongs to the i-th start -- its end; runs of at least min_len bases are numbered and laid out by two more
 // scans, and a copy kernel moves them.  The order of the output is fixed by those scans, never by timing.
 #include "brx_correct.hpp"
+#include "brx_tiles.hpp"
 
-#include <stdlib.h>
 #include <algorithm>
 #include <vector>
 
 using namespace brx;
 
-namespace brx {
-uint64_t scan_tmp_bytes(uint32_t n);
-int exclusive_scan_lens(const uint32_t *d_lens, uint32_t n, uint64_t *d_tmp, uint64_t *d_out_offsets,
-                        unsigned long long *d_total, hipStream_t s);
-}
-
 namespace {
-
-constexpr uint32_t COVER_TILE = 1024; // positions of a read per wave: 16 steps of 64, a 17th for the k-1 k-mers behind them
 
 struct CoverArgs {
     const uint32_t *bits; // nullptr: the index is exact (lazy or sparse set)
@@ -50,11 +42,7 @@ struct CoverArgs {
     uint32_t n_reads;
     const uint8_t *bases;
     const uint64_t *offsets;
-    // work list
-    uint32_t *tiles_of;               // tiles per read                   [n_reads]
-    uint64_t *tile_base;              // exclusive scan of tiles_of       [n_reads + 1]
-    uint32_t *tile_read;              // read of a tile                   [tiles]
-    unsigned long long *n_tiles;      // = tile_base[n_reads]
+    TileList tl;                      // work list (brx_tiles.hpp)
     // outputs, each may be null
     uint8_t *flags;
     uint8_t *masked;
@@ -74,25 +62,10 @@ struct CoverArgs {
     uint64_t *piece_start;
 };
 
-__global__ __launch_bounds__(256) void cover_tiles_of_kernel(CoverArgs a)
-{
-    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-    if (r >= a.n_reads)
-        return;
-    const uint64_t n = a.offsets[r + 1] - a.offsets[r];
-    a.tiles_of[r] = (uint32_t)((n + COVER_TILE - 1u) / COVER_TILE);
-}
-
-__global__ __launch_bounds__(256) void cover_tile_list_kernel(CoverArgs a)
-{
-    for (uint32_t r = blockIdx.x; r < a.n_reads; r += gridDim.x) {
-        const uint64_t tb = a.tile_base[r], te = a.tile_base[r + 1];
-        for (uint64_t t = tb + threadIdx.x; t < te; t += 256)
-            a.tile_read[t] = r;
-    }
-}
-
-// KmerSet::get of one forward k-mer, whatever holds the set; as lane_mask_kernel asks (occupancy bit first)
+// set_get<IDX, LINE_BITS_IN_L2> (brx_index.hpp), kept written out for this one kernel: through the shared function
+// cover_kernel<true> measured 8.7 ms per Gbp against 8.0 (profiles/batch_query_refactor.json), with the same registers
+// and occupancy, where lane_mask_kernel, which asks the same way, did not change.  Same answers
+// (tests/test_gpu_get_routes.py); the chain walk is the one place this copy differs: it is not bounded by the table's size.
 template <bool IDX>
 __device__ __forceinline__ bool cover_get(const CoverArgs &a, uint64_t km, int k, bool filter)
 {
@@ -112,52 +85,27 @@ __device__ __forceinline__ bool cover_get(const CoverArgs &a, uint64_t km, int k
     return pr == 1;
 }
 
-// what a tile is: its read, the read's place and length, the tile's positions [p0, p1)
-struct TileView {
-    uint32_t r, n, p0, p1;
-    uint64_t o0;
-};
-__device__ __forceinline__ bool tile_view(const CoverArgs &a, TileView &t, unsigned long long &tile)
-{
-    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    tile = (unsigned long long)blockIdx.x * 4ull + wv;
-    if (tile >= *a.n_tiles)
-        return false;
-    t.r = a.tile_read[tile];
-    t.o0 = a.offsets[t.r];
-    t.n = (uint32_t)(a.offsets[t.r + 1] - t.o0);
-    t.p0 = (uint32_t)(tile - a.tile_base[t.r]) * COVER_TILE;
-    t.p1 = t.n - t.p0 < COVER_TILE ? t.n : t.p0 + COVER_TILE;
-    return true;
-}
-
-__device__ __forceinline__ uint64_t wave_carry(uint64_t km)
-{
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(km >> 32), 63) << 32) |
-           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)km, 63);
-}
-
 // A wave per tile.
 template <bool IDX>
 __global__ __launch_bounds__(256) void cover_kernel(CoverArgs a)
 {
     TileView t;
     unsigned long long tile;
-    if (!tile_view(a, t, tile))
+    if (!tile_view(a.tl, a.offsets, t, tile))
         return;
     const int lane = threadIdx.x & 63;
     const uint32_t k = (uint32_t)a.k;
     const uint64_t mask = kmask(a.k);
     const uint32_t n = t.n, p0 = t.p0, p1 = t.p1;
     const uint8_t *in = a.bases + t.o0;
-    const bool filter = IDX && a.idx.line_bits != nullptr && a.idx.line_shift >= 6u; // (as lane_mask_kernel)
+    const bool filter = IDX && a.idx.line_bits != nullptr && a.idx.line_shift >= 6u; // (LINE_BITS_IN_L2's rule)
     // the k-mers wanted END at e0 .. elim-1: from the base in front of the tile (is a run open there?) to the last
     // k-mer that reaches back into the tile
     const uint32_t e0 = p0 ? p0 - 1u : 0u;
     const uint32_t elim = n - p1 < k - 1u ? n : p1 + k - 1u;
     // the k-mer that ends in front of e0, from one step without probes
     uint64_t carry = 0;
-    if (e0) { // (p0 >= COVER_TILE: e0 - 64 lies inside the read)
+    if (e0) { // (p0 >= READ_TILE: e0 - 64 lies inside the read)
         const uint32_t code = (in[e0 - 64u + (uint32_t)lane] >> 1) & 3u;
         carry = wave_carry(lane_kmer64_dpp(0, code, lane, mask));
     }
@@ -232,7 +180,7 @@ __global__ __launch_bounds__(256) void cover_runs_kernel(CoverArgs a)
 {
     TileView t;
     unsigned long long tile;
-    if (!tile_view(a, t, tile))
+    if (!tile_view(a.tl, a.offsets, t, tile))
         return;
     const uint32_t lane = threadIdx.x & 63u;
     const uint8_t *fl = a.flags + t.o0;
@@ -306,14 +254,10 @@ int cover_view(const brx_set *set, hipStream_t s, CoverArgs &a)
 {
     BRX_TRY(index_ensure(set, s));
     a.k = set->k;
-    a.bits = no_bits(set) ? nullptr : set->d_bits;
-    a.idx = IdxView{nullptr, 0, 0, 0};
-    if (set->idx_valid && (index_wanted(set->k) || no_bits(set)))
-        a.idx = IdxView{set->d_lines, 32u - set->idx_log_lines, set->idx_m, (uint32_t)set->k - set->idx_m + 1u,
-                        set->idx_linebits ? (const uint32_t *)(set->d_lines + (8ull << set->idx_log_lines)) : nullptr};
-    if (const char *e = getenv("BRX_LINE_BITS")) // (A/B and fuzzers: 0 = do not consult the occupancy bits)
-        if (*e == '0')
-            a.idx.line_bits = nullptr;
+    // (BRX_LINE_BITS read per call -- A/B and fuzzers: 0 = do not consult the occupancy bits)
+    const SetView v = set_view(set, env_u32("BRX_LINE_BITS", 1u) != 0u);
+    a.bits = v.bits;
+    a.idx = v.idx;
     if (!a.bits && !a.idx.lines) {
         set_error("cover: the set (k=%d) has neither a bit vector nor an index", set->k);
         return BRX_ERR_ARG;
@@ -331,43 +275,18 @@ int check_batch(const char *what, const brx_set_t *set, const void *d_bases, con
         set_error("%s: k=%d (a k-mer must fit 62 bits)", what, set->k);
         return BRX_ERR_ARG;
     }
-    if ((n_reads && !d_offsets) || (total_bases && !d_bases)) {
-        set_error("%s: null bases / offsets for %u reads, %llu bases", what, n_reads, (unsigned long long)total_bases);
-        return BRX_ERR_ARG;
-    }
-    if (total_bases && !n_reads) {
-        set_error("%s: %llu bases in no reads", what, (unsigned long long)total_bases);
-        return BRX_ERR_ARG;
-    }
-    return BRX_OK;
+    return check_batch_args(what, d_bases, d_offsets, n_reads, total_bases);
 }
 
 // work list + cover kernel.  `tile_bound` tiles at most (known without asking the device)
 int cover_launch(const brx_set *set, CoverArgs &a, uint64_t total_bases, DevScratch &sc, uint64_t &tile_bound, hipStream_t s)
 {
     BRX_TRY(cover_view(set, s, a));
-    const uint32_t n_reads = a.n_reads;
-    tile_bound = total_bases / COVER_TILE + n_reads;
-    if (tile_bound / 4ull + 1ull > 0x7fffffffull) {
-        set_error("cover: batch of %llu bases in %u reads is too large for one call", (unsigned long long)total_bases, n_reads);
-        return BRX_ERR_ARG;
-    }
-    uint64_t *tmp = nullptr;
-    BRX_TRY(sc.get(&a.tiles_of, n_reads));
-    BRX_TRY(sc.get(&a.tile_base, (uint64_t)n_reads + 1));
-    BRX_TRY(sc.get(&a.tile_read, tile_bound));
-    BRX_TRY(sc.get(&a.n_tiles, 1));
-    BRX_TRY(sc.get(&tmp, scan_tmp_bytes(n_reads) / 8 + 1));
+    BRX_TRY(tile_list_enqueue(a.tl, a.offsets, a.n_reads, total_bases, "cover", "cover_tiles", sc, tile_bound, s));
     if (a.stats)
-        BRX_HIP(hipMemsetAsync(a.stats, 0, (uint64_t)n_reads * sizeof(brx_cover_stats_t), s));
+        BRX_HIP(hipMemsetAsync(a.stats, 0, (uint64_t)a.n_reads * sizeof(brx_cover_stats_t), s));
     if (a.tile_runs)
         BRX_HIP(hipMemsetAsync(a.tile_runs, 0, tile_bound * 4, s));
-    {
-        KernelTimer t("cover_tiles", s);
-        cover_tiles_of_kernel<<<(n_reads + 255u) / 256u, 256, 0, s>>>(a);
-        BRX_TRY(exclusive_scan_lens(a.tiles_of, n_reads, tmp, a.tile_base, a.n_tiles, s));
-        cover_tile_list_kernel<<<read_grid(n_reads, 2048u), 256, 0, s>>>(a);
-    }
     {
         KernelTimer t("cover", s);
         const uint32_t grid = (uint32_t)((tile_bound + 3ull) / 4ull);
@@ -420,11 +339,7 @@ int brx_set_cover_batch(const brx_set_t *set, const uint8_t *bases, const uint64
     }
     const uint64_t total = n_reads ? offsets[n_reads] : 0;
     BRX_TRY(check_batch("brx_set_cover_batch", set, bases, offsets, n_reads, total));
-    for (uint32_t r = 0; r < n_reads; r++)
-        if (offsets[r + 1] < offsets[r] || offsets[r + 1] - offsets[r] > 0xfffffff0ull || (r == 0 && offsets[0] != 0)) {
-            set_error("brx_set_cover_batch: offsets must start at 0 and not decrease; a read holds fewer than 2^32 - 16 bases (read %u)", r);
-            return BRX_ERR_ARG;
-        }
+    BRX_TRY(check_offsets("brx_set_cover_batch", offsets, n_reads));
     BRX_TRY(use_device(set->device));
     if (!n_reads || (!flags && !masked && !stats))
         return BRX_OK;
@@ -482,7 +397,7 @@ int brx_set_cover_split_batch_device(const brx_set_t *set, const uint8_t *d_base
     a.bases = d_bases;
     a.offsets = d_offsets;
     a.min_len = min_len;
-    uint64_t tile_bound = total_bases / COVER_TILE + n_reads;
+    uint64_t tile_bound = total_bases / READ_TILE + n_reads;
     uint64_t *run_base = nullptr, *tmp = nullptr;
     unsigned long long *d_totals = nullptr; // runs, pieces, bytes
     BRX_TRY(sc.get(&a.flags, total_bases));
@@ -592,11 +507,7 @@ int brx_set_cover_split_batch(const brx_set_t *set, const uint8_t *bases, const 
     *n_pieces = 0;
     const uint64_t total = n_reads ? offsets[n_reads] : 0;
     BRX_TRY(check_batch(me, set, bases, offsets, n_reads, total));
-    for (uint32_t r = 0; r < n_reads; r++)
-        if (offsets[r + 1] < offsets[r] || offsets[r + 1] - offsets[r] > 0xfffffff0ull || (r == 0 && offsets[0] != 0)) {
-            set_error("%s: offsets must start at 0 and not decrease; a read holds fewer than 2^32 - 16 bases (read %u)", me, r);
-            return BRX_ERR_ARG;
-        }
+    BRX_TRY(check_offsets(me, offsets, n_reads));
     BRX_TRY(use_device(set->device));
     // the bounds of include/brx.h: no retry
     const uint64_t unit = (uint64_t)std::max<uint32_t>(std::max<uint32_t>((uint32_t)set->k, min_len), 1u) + 1ull;

@@ -228,18 +228,10 @@ __global__ void index_get_kernel(IdxView v, const uint32_t *__restrict__ bits, c
     if (i >= n)
         return;
     const uint64_t fwd = kmers[i] & kmask(k);
-    int r = index_probe(v, fwd, k);
-    if (r == 2) {
+    int home = 0;
+    out[i] = set_get<true, LINE_BITS_NEVER, true>(v, bits, fwd, k, &home) ? 1 : 0;
+    if (home == 2) // the home line could not say: the bit vector or the chain did
         atomicAdd(n_fallback, 1ull);
-        if (bits) {
-            const uint64_t h = khash(fwd, k);
-            r = (bits[h >> 5] >> (h & 31u)) & 1u;
-        } else {
-            for (uint32_t hop = 1; r == 2; hop++) // sparse set: the key was chained into a following line
-                r = index_probe(v, fwd, k, hop);
-        }
-    }
-    out[i] = (uint8_t)r;
 }
 
 // moves every key of one table into another (growing an insert-built set)
@@ -288,6 +280,16 @@ int env_int(const char *name, int dflt)
 } // namespace
 
 namespace brx {
+
+// (the occupancy bits lie behind the lines, in the same allocation)
+SetView set_view(const brx_set *set, bool line_bits, bool any_index)
+{
+    SetView v{no_bits(set) ? nullptr : set->d_bits.get(), IdxView{nullptr, 0, 0, 0}};
+    if (set->idx_valid && (any_index || index_wanted(set->k) || no_bits(set)))
+        v.idx = IdxView{set->d_lines, 32u - set->idx_log_lines, set->idx_m, (uint32_t)set->k - set->idx_m + 1u,
+                        line_bits && set->idx_linebits ? (const uint32_t *)(set->d_lines + (8ull << set->idx_log_lines)) : nullptr};
+    return v;
+}
 
 bool index_wanted(int k)
 {
@@ -867,8 +869,8 @@ int brx_set_get_batch_indexed(const brx_set_t *set, const uint64_t *forward_kmer
     BRX_HIP(hipMemset(d_f, 0, 8));
     BRX_HIP(hipMemcpy(d_k, forward_kmers, (uint64_t)n * 8, hipMemcpyHostToDevice));
     unsigned long long fb = 0;
-    IdxView v{set->d_lines, 32u - set->idx_log_lines, set->idx_m, (uint32_t)set->k - set->idx_m + 1u};
-    index_get_kernel<<<(n + 255) / 256, 256>>>(v, no_bits(set) ? nullptr : set->d_bits.get(), d_k, n, set->k, d_o, d_f);
+    const SetView v = set_view(set, false, true);
+    index_get_kernel<<<(n + 255) / 256, 256>>>(v.idx, v.bits, d_k, n, set->k, d_o, d_f);
     BRX_HIP(hipMemcpy(out, d_o, n, hipMemcpyDeviceToHost));
     BRX_HIP(hipMemcpy(&fb, d_f, 8, hipMemcpyDeviceToHost));
     if (n_fallback)

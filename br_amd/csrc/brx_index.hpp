@@ -16,6 +16,8 @@
 #pragma once
 #include "brx_kmer.hpp"
 
+struct brx_set;
+
 namespace brx {
 
 constexpr int IDX_SLOTS = 7;
@@ -44,6 +46,15 @@ struct IdxView {
     // and the reverse pass of run_correction probes almost only absent k-mers).  nullptr: not kept for this index.
     const uint32_t *line_bits = nullptr;
 };
+
+// How a kernel reaches a set (brx_index.hip): the bit vector -- nullptr for a sparse set and for a lazy one, which stays
+// lazy -- and the index, lines == nullptr where the set has none or, unless any_index, where k is outside the indexed
+// range and the bit vector answers.  line_bits false: the occupancy bits are not handed out (BRX_LINE_BITS=0).
+struct SetView {
+    const uint32_t *bits;
+    IdxView idx;
+};
+SetView set_view(const brx_set *set, bool line_bits, bool any_index = false);
 
 #if defined(__HIPCC__)
 
@@ -199,16 +210,44 @@ __device__ __forceinline__ int index_probe_filtered(const IdxView &v, uint64_t f
         return 0;
     return index_probe_at(v, key, home, 0u);
 }
-// KmerSet::get through the probe index with "cannot say" settled on the spot: the lane asks the bit vector when there is
-// one, else -- sets without one chain their overflowed keys into the following lines -- the next lines of the chain.
-// One probe in a thousand at configs[1]'s occupancy; the other lanes of the wave wait for it.
-__device__ __forceinline__ bool index_get(const IdxView &v, const uint32_t *__restrict__ bits, uint64_t fwd, int k)
+// one bit of the bit vector
+__device__ __forceinline__ bool probe(const uint32_t *__restrict__ bits, uint64_t fwd, int k)
 {
+    const uint64_t h = khash(fwd, k);
+    return (bits[h >> 5] >> (h & 31u)) & 1u;
+}
+
+// KmerSet::get of one forward k-mer (src/set/pcon.rs:189-191), whatever holds the set: THE definition, every kernel
+// that asks goes through it.  IDX = false: the bit vector.  IDX = true: the probe index with "cannot say" settled on
+// the spot -- the lane asks the bit vector when there is one, else (sets without one chain their overflowed keys into
+// the following lines) the next lines of the chain, never more of them than the index has.  One probe in a thousand
+// at configs[1]'s occupancy; the other lanes of the wave wait for it.  TELL: *home_answer = what the home line said
+// (0, 1, or 2 = cannot say).
+// The occupancy bits: an empty home line answers "absent" from its bit, and most k-mers with an error point at one.  When
+// the bits are consulted -- given that the index keeps them and the host handed them out -- is the caller's LB:
+//   LINE_BITS_IN_L2  a wave asks about 64 neighbouring positions per step (lane_mask_kernel; cover_kernel's cover_get): while the
+//                    bits live in the L2, i.e. at most 2^26 lines (4 MiB at 2^25).  Past that every lookup is a request
+//                    of its own on top of the line's (BASELINE configs[4]'s share, 2^28 lines: lane_mask_kernel 40.1 ms
+//                    with the bits, 35.1 without);
+//   LINE_BITS_KEPT   the group kernels' scans and walks (brx_correct.hip): always;
+//   LINE_BITS_NEVER  single probes (lane_sync_kernel, succ_build_kernel, index_get_kernel).
+// (LB and TELL are template parameters so that each caller compiles to the code it had when it wrote this out itself.)
+enum LineBitsUse { LINE_BITS_NEVER, LINE_BITS_KEPT, LINE_BITS_IN_L2 };
+template <bool IDX, LineBitsUse LB, bool TELL = false>
+__device__ __forceinline__ bool set_get(const IdxView &v, const uint32_t *__restrict__ bits, uint64_t fwd, int k, int *home_answer = nullptr)
+{
+    if (!IDX)
+        return probe(bits, fwd, k);
+    if (TELL)
+        *home_answer = 0;
     uint64_t key;
     const uint32_t home = index_locate(v, fwd, k, key);
-    if (v.line_bits && !((v.line_bits[home >> 5] >> (home & 31u)) & 1u))
+    if (LB != LINE_BITS_NEVER && v.line_bits && (LB == LINE_BITS_KEPT || v.line_shift >= 6u) &&
+        !((v.line_bits[home >> 5] >> (home & 31u)) & 1u))
         return false;
     int a = index_probe_at(v, key, home, 0u);
+    if (TELL)
+        *home_answer = a;
     if (a == 2) {
         if (bits) {
             const uint64_t h = khash(fwd, k);

@@ -34,6 +34,12 @@ void set_error(const char *fmt, ...);
 
 // BRX_OK if `device` is a usable GPU and has been made current
 int use_device(int device);
+// What the batch entries refuse (brx_api.hip); `what` names the entry in the message.  check_batch_args: null bases or
+// offsets for a batch that has some, bases in no reads.  check_offsets, host offsets only: they start at 0 and do not
+// decrease, and a read holds fewer than 2^32 - 16 bases; strand_rule (brx_revcomp_batch): they may start anywhere -- the
+// bytes in front of offsets[0] belong to no read -- and a read holds up to 2^32 - 2 bases.
+int check_batch_args(const char *what, const void *bases, const uint64_t *offsets, uint32_t n_reads, uint64_t total_bases);
+int check_offsets(const char *what, const uint64_t *offsets, uint32_t n_reads, bool strand_rule = false);
 // pooled page-locked host memory (brx_api.hip): what brx_host_alloc and the callee-allocated outputs are made of
 void *host_buf_acquire(size_t bytes);
 void host_buf_release(void *p);
@@ -252,6 +258,31 @@ void tab_set_merged(brx_counter *c, int world, int rank);
 bool tab_merged(const brx_counter *c, int *world, int *rank);
 int tab_reset(brx_counter *c, hipStream_t s);
 int tab_spectrum(brx_counter *c, hipStream_t s, unsigned long long *d_hist);
+// the rest of what brx_set.hip's counter entries call: the counting table (brx_counttable.hip) ...
+int tab_begin(brx_counter *c);
+void tab_free(brx_counter *c);
+int tab_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
+                  hipStream_t s);
+int tab_finish_into(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set *dst);
+// ... and the partitioned counter (brx_partbuild.hip)
+bool part_supported(int k);
+int part_begin(brx_counter *c);
+void part_free(brx_counter *c);
+int part_reset(brx_counter *c);
+int part_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads,
+                   uint64_t total_bases, hipStream_t s);
+int part_finish_into(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set *dst);
+int part_spectrum(brx_counter *c, hipStream_t s, unsigned long long *d_hist);
+int part_l1_view(brx_counter *c, void **d_keys, void **d_l1off, uint32_t *n_buckets, uint64_t *n_keys);
+int part_add_partitioned(brx_counter *c, const uint32_t *d_keys, const uint64_t *d_l1off, uint64_t n_keys);
+// exclusive scan of n u32 lengths into n + 1 u64 offsets, the total also into *d_total (brx_scan.hip); d_tmp holds
+// scan_tmp_bytes(n) bytes
+uint64_t scan_tmp_bytes(uint32_t n);
+int exclusive_scan_lens(const uint32_t *d_lens, uint32_t n, uint64_t *d_tmp, uint64_t *d_out_offsets,
+                        unsigned long long *d_total, hipStream_t s);
+// a host batch into the chain's staging buffers, offsets made relative to the first read (brx_set.hip)
+int upload_batch(const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, DevBuf<uint8_t> &d_bases, DevBuf<uint64_t> &d_off,
+                 uint64_t *total, hipStream_t stream);
 // count view of a BRX_COUNT_SORTED counter (brx_partbuild.hip); the callers hold the counter's lock.  part_lookup_view:
 // false = no valid view; true with *keys == nullptr = nothing was counted.  part_lookup_shape: the buckets the offsets
 // delimit and the positions behind them (brx_keyfile.hip walks the whole view to save it)

@@ -41,13 +41,6 @@
 
 using namespace brx;
 
-namespace brx {
-uint64_t scan_tmp_bytes(uint32_t n);
-int exclusive_scan_lens(const uint32_t *d_lens, uint32_t n, uint64_t *d_tmp, uint64_t *d_out_offsets,
-                        unsigned long long *d_total, hipStream_t s);
-}
-
-
 namespace {
 
 constexpr uint32_t U_VOID = 0xffffffffu;   // u_q: the unit found no sync point (its predecessor scans through it)
@@ -224,25 +217,6 @@ __global__ __launch_bounds__(256) void lane_pack_kernel(LaneArgs a)
     }
 }
 
-// KmerSet::get of one forward k-mer, whatever holds the set (src/set/pcon.rs:189-191)
-template <bool IDX>
-__device__ __forceinline__ bool set_get(const PassParams &p, uint64_t km, int k)
-{
-    if (!IDX)
-        return probe(p.bits, km, k);
-    uint64_t key;
-    const uint32_t home = index_locate(p.idx, km, k, key);
-    for (uint32_t hop = 0;; hop++) {
-        const int pr = index_probe_at(p.idx, key, home, hop);
-        if (pr != 2)
-            return pr == 1;
-        if (p.bits) { // the line overflowed at build time and does not hold the key: the bit vector knows
-            const uint64_t h = key - 1ull;
-            return (p.bits[h >> 5] >> (h & 31u)) & 1u;
-        }
-    }
-}
-
 // Which ORIGINAL k-mers of the batch are solid, one bit per position (a.M, laid out like P): asked once, in parallel, 64
 // neighbouring positions per wave -- neighbours share their index lines, so this is the cheap way to ask.  The automata
 // then scan stretches the reads' own bases cover (no fix inside the last k - 1 positions) from these bits, many
@@ -257,7 +231,6 @@ __global__ __launch_bounds__(256) void lane_mask_kernel(LaneArgs a)
     const unsigned long long n_units = p.ctrl[CTL_LANE_UNITS];
     const unsigned long long wave = (unsigned long long)blockIdx.x * 4ull + (threadIdx.x >> 6);
     const unsigned long long n_waves = (unsigned long long)gridDim.x * 4ull;
-    const bool filter = p.idx.line_bits != nullptr && p.idx.line_shift >= 6u; // (line_shift = 32 - log2(lines))
     uint4 ui_next = wave < n_units ? a.u_in[wave] : make_uint4(0, 0, 0, 0);
     uint32_t r_next = wave < n_units ? a.u_read[wave] : 0u;
     for (unsigned long long u = wave; u < n_units; u += n_waves) {
@@ -288,32 +261,12 @@ __global__ __launch_bounds__(256) void lane_mask_kernel(LaneArgs a)
             const uint32_t code = (row[e >> 4] >> (30u - 2u * (e & 15u))) & 3u; // (the padding behind the read packs as A)
             const uint64_t km = lane_kmer64_dpp(carry, code, lane, mask);
             bool sol = false;
-            if (e < lim && e + 1u >= (uint32_t)k) {
-                if (IDX) {
-                    uint64_t key;
-                    const uint32_t home = index_locate(p.idx, km, k, key);
-                    // an empty home line answers from its occupancy bit, and most k-mers with an error point at one -- while
-                    // the bits live in the L2 (4 MiB at 2^25 lines).  Past 2^26 lines every lookup is a request of its own on
-                    // top of the line's (BASELINE configs[4]'s share, 2^28 lines: this kernel 40.1 ms with the bits, 35.1 without)
-                    if (!filter || ((p.idx.line_bits[home >> 5] >> (home & 31u)) & 1u)) {
-                        int pr = index_probe_at(p.idx, key, home, 0u);
-                        for (uint32_t hop = 1; pr == 2 && !p.bits; hop++)
-                            pr = index_probe_at(p.idx, key, home, hop);
-                        if (pr == 2) {
-                            const uint64_t h = key - 1ull;
-                            pr = (p.bits[h >> 5] >> (h & 31u)) & 1u;
-                        }
-                        sol = pr == 1;
-                    }
-                } else {
-                    sol = probe(p.bits, km, k);
-                }
-            }
+            if (e < lim && e + 1u >= (uint32_t)k)
+                sol = set_get<IDX, LINE_BITS_IN_L2>(p.idx, p.bits, km, k);
             const uint64_t ball = __ballot(sol);
             if ((lane & 15) == 0 && e < lim)
                 mrow[e >> 4] = (uint16_t)(ball >> lane);
-            carry = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(km >> 32), 63) << 32) |
-                    (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)km, 63);
+            carry = wave_carry(km);
         }
     }
 }
@@ -359,7 +312,7 @@ __global__ __launch_bounds__(256) void lane_sync_kernel(LaneArgs a)
                 const uint64_t hi = ((uint64_t)row[wd] << 32) | row[wd + 1];
                 const uint64_t lo = row[wd + 2];
                 km = (sh ? ((hi << sh) | (lo >> (32u - sh))) : hi) >> (64u - 2u * k);
-                sol = set_get<IDX>(p, km, (int)k);
+                sol = set_get<IDX, LINE_BITS_NEVER>(p.idx, p.bits, km, (int)k);
             }
             const uint64_t ball = __ballot(sol);
             const uint32_t cur32 = (uint32_t)(ball >> (32u * half));
@@ -1023,7 +976,7 @@ __global__ __launch_bounds__(256) void succ_build_kernel(PassParams p, uint64_t 
                     const uint64_t x = o ? revcomp(cano, k) : cano;
                     uint32_t m4 = 0;
                     for (uint64_t b = 0; b < 4; b++)
-                        m4 |= (set_get<true>(p, add_nuc(x, b, mask), k) ? 1u : 0u) << b;
+                        m4 |= (set_get<true, LINE_BITS_NEVER>(p.idx, p.bits, add_nuc(x, b, mask), k) ? 1u : 0u) << b;
                     if (__popc(m4) == 1)
                         byte |= (4u | ((uint32_t)__ffs(m4) - 1u)) << (4 * o);
                 }

@@ -32,12 +32,6 @@
 #include <string.h>
 #include <atomic>
 
-namespace brx {
-uint64_t scan_tmp_bytes(uint32_t n);
-int exclusive_scan_lens(const uint32_t *d_lens, uint32_t n, uint64_t *d_tmp, uint64_t *d_out_offsets,
-                        unsigned long long *d_total, hipStream_t s);
-}
-
 using namespace brx;
 
 namespace {

@@ -345,25 +345,6 @@ int grid_for(uint64_t items, int per_block, int cap = 256 * 8)
 } // namespace
 
 namespace brx {
-bool part_supported(int k);
-int part_begin(brx_counter *c);
-void part_free(brx_counter *c);
-int part_reset(brx_counter *c);
-int part_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads,
-                   uint64_t total_bases, hipStream_t s);
-int part_finish_into(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set *dst);
-int part_spectrum(brx_counter *c, hipStream_t s, unsigned long long *d_hist);
-int part_l1_view(brx_counter *c, void **d_keys, void **d_l1off, uint32_t *n_buckets, uint64_t *n_keys);
-int part_add_partitioned(brx_counter *c, const uint32_t *d_keys, const uint64_t *d_l1off, uint64_t n_keys);
-// counting-table strategy (brx_counttable.hip)
-int tab_begin(brx_counter *c);
-void tab_free(brx_counter *c);
-int tab_reset(brx_counter *c, hipStream_t s);
-int tab_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
-                  hipStream_t s);
-int tab_finish_into(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set *dst);
-int tab_spectrum(brx_counter *c, hipStream_t s, unsigned long long *d_hist);
-int tab_info(brx_counter *c, uint64_t *info4, hipStream_t s);
 // a set of this k with nothing written yet (brx_set_load_fd fills it from a key list)
 int set_alloc_unwritten(int k, int device, brx_set **out) { return alloc_set(k, device, false, out); }
 // used by the correction chain and the host-pointer entry points

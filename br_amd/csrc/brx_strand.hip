@@ -156,11 +156,7 @@ int brx_revcomp_batch(const uint8_t *bases, const uint64_t *offsets, uint32_t n_
     }
     BRX_TRY(use_device(device));
     const uint64_t total = n_reads ? offsets[n_reads] : 0;
-    for (uint32_t r = 0; r < n_reads; r++)
-        if (offsets[r] > offsets[r + 1] || offsets[r + 1] - offsets[r] >= 0xffffffffull) {
-            set_error("brx_revcomp_batch: offsets must not decrease and a read holds fewer than 2^32 - 1 bases (read %u)", r);
-            return BRX_ERR_ARG;
-        }
+    BRX_TRY(check_offsets("brx_revcomp_batch", offsets, n_reads, true));
     if (total == 0)
         return BRX_OK;
     DevBuf<uint8_t> d_in, d_o;
