@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void table_rehash_counts_kernel(const uint64_t
 {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_old_slots; i += stride) {
-        const uint64_t v = (i & 7ull) == 7ull ? 0ull : old_lines[i]; // (entry 7 is the line's header)
+        const uint64_t v = table_slot_key(old_lines, i);
         if (v) {
             const uint64_t h = v - 1ull;
             bool fresh;
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void table_select_kernel(const uint64_t *__res
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_slots; i += stride) {
-        const uint64_t v = (i & 7ull) == 7ull ? 0ull : lines[i];
+        const uint64_t v = table_slot_key(lines, i);
         const bool keep = v && table_count_read(counts[i]) > abundance;
         if (keep && bits && v - 1ull < nbits)
             atomicOr(bits + ((v - 1ull) >> 5), 1u << ((v - 1ull) & 31u));
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void table_spectrum_kernel(const uint64_t *__r
     __syncthreads();
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_slots; i += stride)
-        if ((i & 7ull) != 7ull && lines[i])
+        if (table_slot_key(lines, i))
             atomicAdd(&h[table_count_read(counts[i])], 1ull);
     __syncthreads();
     if (h[threadIdx.x])
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void table_owner_hist_kernel(const uint64_t *_
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_slots; i += stride) {
-        const uint64_t v = (i & 7ull) == 7ull ? 0ull : lines[i];
+        const uint64_t v = table_slot_key(lines, i);
         const uint32_t own = v ? table_owner_of(v - 1ull, world) : 0xffffffffu;
         unsigned long long todo = __ballot(v != 0ull);
         while (todo) { // wave-uniform
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void table_owner_split_kernel(const uint64_t *
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_slots; i += stride) {
-        const uint64_t v = (i & 7ull) == 7ull ? 0ull : lines[i];
+        const uint64_t v = table_slot_key(lines, i);
         const uint32_t own = v ? table_owner_of(v - 1ull, world) : 0xffffffffu;
         const uint32_t cnt = v ? table_count_read(counts[i]) : 0u;
         unsigned long long todo = __ballot(v != 0ull);
@@ -357,7 +357,7 @@ int tab_finish_into(brx_counter *c, uint32_t abundance, hipStream_t s, brx_set *
     BRX_HIP(hipMemsetAsync(dst->d_keylist_n, 0, 8, s));
     if (!dst->sparse) { // the bits are written here, in the same pass (nothing left lazy)
         BRX_HIP(hipMemsetAsync(dst->d_bits, 0, dst->nwords * 4, s));
-        dst->bits_stale = false;
+        bits_mark(dst, true);
     }
     const bool list = dst->sparse || index_wanted(c->k);
     if (t->keys_known && t->d_lines) {

@@ -515,19 +515,18 @@ struct ExchangeJob {
 // IS this rank's share of the set), else taken from the bit vector
 int owned_list(brx_set_t *dst, ExchangeJob &job, void **d_list, uint64_t *n_mine, hipStream_t s)
 {
-    BRX_TRY(brx_set_keylist_device(dst, d_list, n_mine, s));
-    if (!*d_list) {
+    SetKeys keys;
+    BRX_TRY(set_keys(dst, s, &keys));
+    if (keys.holder == SetHolder::KeyList) { // (an owner whose table was empty: the valid, empty list, nothing allocated)
+        *d_list = const_cast<uint64_t *>(keys.src.keys);
+        *n_mine = keys.src.n;
+    } else if (keys.holder == SetHolder::Bits) {
         // no list (it did not fit, or BRX_LAZY_BITS=0 builds that keep none): take it from the bit vector
-        if (dst->sparse || dst->bits_stale) {
-            set_error("exchange: the owner's set has neither a key list nor a bit vector");
-            return BRX_ERR_NOMEM;
-        }
-        BRX_HIP(hipStreamSynchronize(s));
-        uint64_t pc = 0;
-        BRX_TRY(brx_set_popcount(dst, &pc));
-        BRX_TRY(job.d_extracted.reserve(pc + 64, 0, "solid k-mers of the bit vector"));
-        BRX_TRY(brx_set_extract_keys_device(dst, 0, dst->nwords * 32, job.d_extracted, pc + 64, n_mine, s));
+        BRX_TRY(keys_from_bits(dst, s, job.d_extracted, n_mine, 64));
         *d_list = job.d_extracted.get();
+    } else {
+        set_error("exchange: the owner's set has neither a key list nor a bit vector");
+        return BRX_ERR_NOMEM;
     }
     BRX_HIP(hipStreamSynchronize(s));
     return BRX_OK;
@@ -860,8 +859,7 @@ int table_finish_body(brx_comm *cm, brx_counter_t *c, uint8_t abundance, brx_set
     void *d_list = nullptr;
     uint64_t n_mine = 0, n_all = 0;
     int local = brx_set_count_finish_into(c, abundance, s, dst);
-    // (an owner whose table is empty leaves the valid, empty list without ever allocating one: nothing to take)
-    if (local == BRX_OK && !(dst->keylist_valid && !dst->d_keylist))
+    if (local == BRX_OK)
         local = owned_list(dst, job, &d_list, &n_mine, s);
     BRX_TRY(replicate_solid(cm, dst, d_list, n_mine, local, "list its solid k-mers", s, &n_all));
     cm->stats[3] = n_mine; // solid k-mers this rank owns

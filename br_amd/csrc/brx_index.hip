@@ -235,40 +235,16 @@ __global__ void index_get_kernel(IdxView v, const uint32_t *__restrict__ bits, c
 }
 
 // moves every key of one table into another (growing an insert-built set)
-__global__ __launch_bounds__(256) void table_rehash_kernel(const uint64_t *__restrict__ old_lines, uint64_t n_old_lines, int k,
-                                                           uint64_t *__restrict__ lines, uint32_t line_shift, uint32_t m, uint32_t w)
+__global__ __launch_bounds__(256) void table_rehash_kernel(KeySource old, int k, uint64_t *__restrict__ lines, uint32_t line_shift, uint32_t m,
+                                                           uint32_t w)
 {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_old_lines * IDX_SLOTS; i += stride) {
-        const uint64_t v = old_lines[(i / IDX_SLOTS) * 8ull + (i % IDX_SLOTS)];
-        if (v) {
-            const uint64_t h = v - 1ull;
-            (void)table_find_or_insert(lines, line_shift, m, w, k, (h << 1) | (uint64_t)(popc64(h) & 1));
-        }
-    }
+    for_each_key(old, [&](uint64_t h) { (void)table_find_or_insert(lines, line_shift, m, w, k, (h << 1) | (uint64_t)(popc64(h) & 1)); });
 }
 
-__global__ __launch_bounds__(256) void table_to_bits_kernel(const uint64_t *__restrict__ lines, uint64_t n_lines, uint32_t *__restrict__ bits,
-                                                            uint64_t nbits)
+// ORs the keys of a list or of a table into a bit vector (materialising a lazy one; brx_set_or_keys_device)
+__global__ __launch_bounds__(256) void or_keys_kernel(KeySource src, uint32_t *__restrict__ bits, uint64_t nbits)
 {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_lines * IDX_SLOTS; i += stride) {
-        const uint64_t v = lines[(i / IDX_SLOTS) * 8ull + (i % IDX_SLOTS)];
-        if (v && v - 1ull < nbits)
-            atomicOr(bits + ((v - 1ull) >> 5), 1u << ((v - 1ull) & 31u));
-    }
-}
-
-__global__ void keys_to_bits_kernel(const uint64_t *__restrict__ keys, const unsigned long long *__restrict__ n_ptr, uint32_t *__restrict__ bits,
-                                    uint64_t nbits)
-{
-    const uint64_t n = *n_ptr;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint64_t h = keys[i];
-        if (h < nbits)
-            atomicOr(bits + (h >> 5), 1u << (h & 31u));
-    }
+    for_each_key(src, [&](uint64_t h) { if (h < nbits) atomicOr(bits + (h >> 5), 1u << (h & 31u)); });
 }
 
 int env_int(const char *name, int dflt)
@@ -289,6 +265,87 @@ SetView set_view(const brx_set *set, bool line_bits, bool any_index)
         v.idx = IdxView{set->d_lines, 32u - set->idx_log_lines, set->idx_m, (uint32_t)set->k - set->idx_m + 1u,
                         line_bits && set->idx_linebits ? (const uint32_t *)(set->d_lines + (8ull << set->idx_log_lines)) : nullptr};
     return v;
+}
+
+// who holds the keys (brx_internal.hpp: SetKeys): the list's counter read once, the rule asked once
+int set_keys_locked(const brx_set *set, hipStream_t s, SetKeys *out)
+{
+    *out = SetKeys{};
+    out->list_cap = set->d_keylist.cap();
+    if (set->keylist_valid) {
+        BRX_TRY(use_device(set->device));
+        unsigned long long nl = 0;
+        BRX_HIP(hipMemcpyAsync(&nl, set->d_keylist_n, 8, hipMemcpyDeviceToHost, s));
+        BRX_HIP(hipStreamSynchronize(s));
+        out->listed_n = nl;
+    }
+    out->holder = set_holder(set->sparse, set->bits_stale, set->keylist_valid, out->listed_n, out->list_cap, set->idx_valid, set->idx_exact,
+                             set->d_lines.get() != nullptr);
+    if (out->holder == SetHolder::KeyList)
+        out->src = list_source(set->d_keylist, out->listed_n);
+    else if (out->holder == SetHolder::Table)
+        out->src = table_source(set->d_lines, 1ull << set->idx_log_lines);
+    else if (out->holder == SetHolder::Bits)
+        out->src = bits_source(set->d_bits, set->nwords);
+    out->sorted = out->holder == SetHolder::KeyList && set->keylist_sorted;
+    out->table_keys = set->idx_keys;
+    return BRX_OK;
+}
+
+int set_keys(const brx_set *set, hipStream_t s, SetKeys *out)
+{
+    std::lock_guard<std::mutex> g(const_cast<brx_set *>(set)->idx_mu);
+    return set_keys_locked(set, s, out);
+}
+
+// the keys of a set, whatever holds it, into d_out, in the holder's order; a lazy bit vector stays lazy.  *sorted (may be
+// null): the keys are known to ascend strictly -- they are a key list that says so.  The copy is left queued on `s`.
+int set_list_keys(const brx_set *set, hipStream_t s, DevBuf<uint64_t> &d_out, uint64_t *n_out, bool *sorted)
+{
+    d_out.reset();
+    *n_out = 0;
+    {
+        std::lock_guard<std::mutex> g(const_cast<brx_set *>(set)->idx_mu);
+        SetKeys keys;
+        const int st = set_keys_locked(set, s, &keys);
+        if (sorted)
+            *sorted = keys.sorted;
+        BRX_TRY(st);
+        if (keys.holder == SetHolder::KeyList) {
+            if (keys.src.n) {
+                BRX_TRY(d_out.reserve(keys.src.n, 0, "keys of the set"));
+                KernelTimer kt("key_list", s);
+                BRX_HIP(hipMemcpyAsync(d_out, keys.src.keys, keys.src.n * 8, hipMemcpyDeviceToDevice, s));
+            }
+            *n_out = keys.src.n;
+            return BRX_OK;
+        }
+        if (keys.holder == SetHolder::None) {
+            set_error("brx_set_save_fd: the set has neither a bit vector, nor a key list, nor a table");
+            return BRX_ERR_UNSUPPORTED;
+        }
+        if (keys.holder == SetHolder::Table) {
+            const uint64_t cap = keys.table_keys;
+            if (!cap)
+                return BRX_OK;
+            DevBuf<unsigned long long> d_n;
+            BRX_TRY(d_n.reserve(1, 0, "keys of the set"));
+            BRX_HIP(hipMemsetAsync(d_n, 0, 8, s));
+            BRX_TRY(d_out.reserve(cap, 0, "keys of the set"));
+            BRX_TRY(table_list(keys.src.lines, nullptr, keys.src.n_entries, 1u, d_out, nullptr, cap, d_n, s));
+            unsigned long long got = 0;
+            BRX_HIP(hipMemcpyAsync(&got, d_n, 8, hipMemcpyDeviceToHost, s));
+            BRX_HIP(hipStreamSynchronize(s));
+            if (got != cap) {
+                set_error("brx_set_save_fd: %llu keys in the table of a set of %llu", got, (unsigned long long)cap);
+                return BRX_ERR_HIP;
+            }
+            *n_out = got;
+            return BRX_OK;
+        }
+    }
+    KernelTimer kt("key_list", s);
+    return keys_from_bits(set, s, d_out, n_out);
 }
 
 bool index_wanted(int k)
@@ -519,11 +576,7 @@ static int index_build_locked(brx_set *set, const uint64_t *d_keys, uint64_t n, 
     set->idx_m = (uint32_t)m;
     set->idx_keys = n;
     set->idx_overflow_keys = ovf[0];
-    set->idx_exact = no_bits(set);
-    set->idx_open = false;
-    set->idx_linebits = true; // this build filled the occupancy bits behind the lines
-    set->idx_valid = true;
-    set->idx_gen++;
+    index_mark(set, no_bits(set), false, true); // closed; this build filled the occupancy bits behind the lines
     return BRX_OK;
 }
 
@@ -574,7 +627,7 @@ int index_insert_reads(brx_set *set, const uint8_t *d_bases, const uint64_t *d_o
         BRX_HIP(hipMemsetAsync(nl, 0, 64ull << log_lines, s));
         if (have && set->idx_keys) {
             KernelTimer t("index_rehash", s);
-            table_rehash_kernel<<<256 * 8, 256, 0, s>>>(set->d_lines, 1ull << set->idx_log_lines, k, nl, 32u - (uint32_t)log_lines,
+            table_rehash_kernel<<<256 * 8, 256, 0, s>>>(table_source(set->d_lines, 1ull << set->idx_log_lines), k, nl, 32u - (uint32_t)log_lines,
                                                         (uint32_t)m, (uint32_t)(k - m + 1));
         }
         BRX_HIP(hipStreamSynchronize(s));
@@ -595,11 +648,7 @@ int index_insert_reads(brx_set *set, const uint8_t *d_bases, const uint64_t *d_o
     BRX_HIP(hipMemcpyAsync(&added, d_new, 8, hipMemcpyDeviceToHost, s));
     BRX_HIP(hipStreamSynchronize(s));
     set->idx_keys += added;
-    set->idx_exact = true;
-    set->idx_linebits = false; // filled k-mer by k-mer: no occupancy bits
-    set->idx_open = true;
-    set->idx_valid = true;
-    set->idx_gen++;
+    index_mark(set, true, true, false); // open; filled k-mer by k-mer: no occupancy bits
     keylist_mark(set, false); // the table is the set now
     return BRX_OK;
 }
@@ -617,19 +666,18 @@ int ensure_bits(const brx_set *cset, hipStream_t s, const char *what)
     std::lock_guard<std::mutex> g(set->idx_mu);
     if (!set->bits_stale)
         return BRX_OK;
-    KernelTimer t("bits_materialise", s);
-    BRX_HIP(hipMemsetAsync(set->d_bits, 0, set->nwords * 4, s));
-    if (set->keylist_valid) {
-        keys_to_bits_kernel<<<256 * 8, 256, 0, s>>>(set->d_keylist, set->d_keylist_n, set->d_bits, set->nwords * 32);
-    } else if (set->idx_valid && set->idx_exact) {
-        table_to_bits_kernel<<<256 * 16, 256, 0, s>>>(set->d_lines, 1ull << set->idx_log_lines, set->d_bits, set->nwords * 32);
-    } else {
+    SetKeys keys;
+    BRX_TRY(set_keys_locked(set, s, &keys));
+    if (keys.holder == SetHolder::None) {
         set_error("%s: the set has neither bits, key list nor an exact index", what);
         return BRX_ERR_ARG;
     }
+    KernelTimer t("bits_materialise", s);
+    BRX_HIP(hipMemsetAsync(set->d_bits, 0, set->nwords * 4, s));
+    or_keys_kernel<<<keys.holder == SetHolder::KeyList ? 256 * 8 : 256 * 16, 256, 0, s>>>(keys.src, set->d_bits, set->nwords * 32);
     BRX_HIP(hipGetLastError());
     BRX_HIP(hipStreamSynchronize(s));
-    set->bits_stale = false;
+    bits_mark(set, true);
     return BRX_OK;
 }
 
@@ -644,22 +692,13 @@ int index_ensure(const brx_set *cset, hipStream_t s)
     if (set->idx_valid || set->idx_declined)
         return BRX_OK;
     BRX_TRY(use_device(set->device));
+    SetKeys keys;
+    BRX_TRY(set_keys_locked(set, s, &keys));
     uint64_t n = 0;
-    bool listed = false;
-    if (set->keylist_valid) {
-        unsigned long long nl = 0;
-        BRX_HIP(hipMemcpyAsync(&nl, set->d_keylist_n, 8, hipMemcpyDeviceToHost, s));
-        BRX_HIP(hipStreamSynchronize(s));
-        listed = nl <= set->d_keylist.cap(); // a truncated list is useless
-        n = nl;
-    }
-    if (!listed) {
-        BRX_HIP(hipStreamSynchronize(s)); // the bits may still be in flight on `s`; popcount runs on the null stream
-        BRX_TRY(brx_set_popcount(set, &n));
-    }
-    if (no_bits(set) && !listed) {
+    BRX_TRY(keys_count(set, keys, s, &n));
+    if (no_bits(set) && keys.holder != SetHolder::KeyList) { // (no table either: the set has no index)
         set_error("set without bit vector and without a complete key list (%llu solid k-mers counted, room for %llu)", (unsigned long long)n,
-                  (unsigned long long)set->d_keylist.cap());
+                  (unsigned long long)keys.list_cap);
         return BRX_ERR_NOMEM;
     }
     if (!no_bits(set) && set->k - index_auto_m(set->k, n) + 1 < 3 && env_int("BRX_INDEX_M", 0) <= 0) {
@@ -667,12 +706,11 @@ int index_ensure(const brx_set *cset, hipStream_t s)
         set->idx_declined = true;
         return BRX_OK;
     }
-    if (listed)
-        return index_build_locked(set, set->d_keylist, n, 0, 0, s);
+    if (keys.holder == SetHolder::KeyList)
+        return index_build_locked(set, keys.src.keys, n, 0, 0, s);
     DevBuf<uint64_t> d_keys;
-    BRX_TRY(d_keys.reserve(n ? n : 1, 0, "keys of the set"));
     uint64_t got = 0;
-    BRX_TRY(brx_set_extract_keys_device(set, 0, set->nwords * 32, d_keys, n, &got, s));
+    BRX_TRY(keys_from_bits(set, s, d_keys, &got, 0, &n));
     return index_build_locked(set, d_keys, got, 0, 0, s);
 }
 
@@ -685,13 +723,9 @@ int brx_set_index_build(brx_set_t *set, int m, int log2_lines, void *stream)
     if (!set)
         return BRX_ERR_ARG;
     BRX_TRY(use_device(set->device));
-    BRX_HIP(hipStreamSynchronize((hipStream_t)stream));
-    uint64_t n = 0;
-    BRX_TRY(brx_set_popcount(set, &n));
     DevBuf<uint64_t> d_keys;
-    BRX_TRY(d_keys.reserve(n ? n : 1, 0, "keys of the set"));
     uint64_t got = 0;
-    BRX_TRY(brx_set_extract_keys_device(set, 0, set->nwords * 32, d_keys, n, &got, stream));
+    BRX_TRY(keys_from_bits(set, (hipStream_t)stream, d_keys, &got)); // (a lazy vector is written first)
     return index_build_from_keys(set, d_keys, got, m, log2_lines, (hipStream_t)stream);
 }
 
@@ -705,22 +739,37 @@ int brx_set_index_build_from_keys_device(brx_set_t *set, const uint64_t *d_keys,
     return st;
 }
 
+int brx_set_or_keys_device(brx_set_t *set, const uint64_t *d_keys, uint64_t n, void *stream)
+{
+    if (!set || (!d_keys && n))
+        return BRX_ERR_ARG;
+    BRX_TRY(ensure_bits(set, nullptr, "or_keys (use brx_set_index_build_from_keys_device)"));
+    BRX_TRY(use_device(set->device));
+    if (!n)
+        return BRX_OK;
+    index_invalidate(set);
+    hipStream_t s = (hipStream_t)stream;
+    {
+        KernelTimer t("or_keys", s);
+        const uint64_t blocks = (n + 255) / 256;
+        or_keys_kernel<<<(int)(blocks < 256 * 8 ? blocks : 256 * 8), 256, 0, s>>>(list_source(d_keys, n), set->d_bits, set->nwords * 32);
+    }
+    BRX_HIP(hipGetLastError());
+    return BRX_OK;
+}
+
 int brx_set_keylist_device(const brx_set_t *set, void **d_keys, uint64_t *n, void *stream)
 {
     if (!set || !d_keys || !n)
         return BRX_ERR_ARG;
     *d_keys = nullptr;
     *n = 0;
-    if (!set->keylist_valid)
-        return BRX_OK;
-    BRX_TRY(use_device(set->device));
-    unsigned long long nl = 0;
-    BRX_HIP(hipMemcpyAsync(&nl, set->d_keylist_n, 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    BRX_HIP(hipStreamSynchronize((hipStream_t)stream));
-    if (nl > set->d_keylist.cap())
-        return BRX_OK; // truncated list: treat as absent
-    *d_keys = set->d_keylist;
-    *n = nl;
+    SetKeys keys;
+    BRX_TRY(set_keys(set, (hipStream_t)stream, &keys));
+    if (keys.holder == SetHolder::KeyList) {
+        *d_keys = const_cast<uint64_t *>(keys.src.keys);
+        *n = keys.src.n;
+    }
     return BRX_OK;
 }
 
@@ -740,46 +789,10 @@ __device__ __forceinline__ void fp_add(unsigned long long *out, unsigned long lo
         atomicAdd(out + 2, s2);
     }
 }
-__global__ __launch_bounds__(256) void fp_list_kernel(const uint64_t *__restrict__ keys, const unsigned long long *__restrict__ n_dev, uint64_t cap,
-                                                      unsigned long long *out)
-{
-    const uint64_t n = *n_dev < cap ? *n_dev : cap;
-    unsigned long long c = 0, s1 = 0, s2 = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
-        const unsigned long long h = keys[i];
-        c++;
-        s1 += h;
-        s2 += h * h;
-    }
-    fp_add(out, c, s1, s2);
-}
-__global__ __launch_bounds__(256) void fp_table_kernel(const uint64_t *__restrict__ lines, uint64_t n_lines, unsigned long long *out)
+__global__ __launch_bounds__(256) void fp_kernel(KeySource src, unsigned long long *out)
 {
     unsigned long long c = 0, s1 = 0, s2 = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n_lines * 8ull; i += (uint64_t)gridDim.x * 256u) {
-        const unsigned long long v = (i & 7ull) == 7ull ? 0ull : lines[i]; // (slot 7 is the line's header)
-        if (v) {
-            const unsigned long long h = v - 1ull;
-            c++;
-            s1 += h;
-            s2 += h * h;
-        }
-    }
-    fp_add(out, c, s1, s2);
-}
-__global__ __launch_bounds__(256) void fp_bits_kernel(const uint32_t *__restrict__ bits, uint64_t nwords, unsigned long long *out)
-{
-    unsigned long long c = 0, s1 = 0, s2 = 0;
-    for (uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x; w < nwords; w += (uint64_t)gridDim.x * 256u) {
-        uint32_t x = bits[w];
-        while (x) {
-            const unsigned long long h = w * 32ull + (unsigned long long)(__ffs(x) - 1);
-            x &= x - 1u;
-            c++;
-            s1 += h;
-            s2 += h * h;
-        }
-    }
+    for_each_key(src, [&](uint64_t h) { c++, s1 += h, s2 += h * h; });
     fp_add(out, c, s1, s2);
 }
 } // namespace
@@ -793,18 +806,13 @@ int brx_set_fingerprint(const brx_set_t *set, uint64_t *out3, void *stream)
     DevBuf<unsigned long long> d;
     BRX_TRY(d.reserve(3, 0, "fingerprint"));
     BRX_HIP(hipMemsetAsync(d, 0, 24, s));
-    if (set->keylist_valid) { // (a truncated list is never left valid with a set that has nothing else)
-        fp_list_kernel<<<2048, 256, 0, s>>>(set->d_keylist, set->d_keylist_n, set->d_keylist.cap(), d);
-    } else if (no_bits(set)) {
-        // no bit vector (sparse, or lazy and not written): the chained table is exact and holds every key once
-        if (!set->idx_valid || !set->d_lines) {
-            set_error("fingerprint: the set has neither a bit vector, nor a key list, nor a table");
-            return BRX_ERR_UNSUPPORTED;
-        }
-        fp_table_kernel<<<4096, 256, 0, s>>>(set->d_lines, 1ull << set->idx_log_lines, d);
-    } else {
-        fp_bits_kernel<<<4096, 256, 0, s>>>(set->d_bits, set->nwords, d);
+    SetKeys keys;
+    BRX_TRY(set_keys(set, s, &keys));
+    if (keys.holder == SetHolder::None) {
+        set_error("fingerprint: the set has neither a bit vector, nor a key list, nor a table");
+        return BRX_ERR_UNSUPPORTED;
     }
+    fp_kernel<<<keys.holder == SetHolder::KeyList ? 2048 : 4096, 256, 0, s>>>(keys.src, d);
     BRX_HIP(hipGetLastError());
     unsigned long long h[3] = {0, 0, 0};
     BRX_HIP(hipMemcpyAsync(h, d, 24, hipMemcpyDeviceToHost, s));

@@ -56,7 +56,46 @@ struct SetView {
 };
 SetView set_view(const brx_set *set, bool line_bits, bool any_index = false);
 
+// What one launch enumerates (for_each_key): a key list (`n` clamped on the host to what the list holds), the entries of a
+// table's lines (8 per line, the header among them) or the words of a bit vector -- the first pointer that is set.
+struct KeySource {
+    const uint64_t *keys = nullptr;
+    uint64_t n = 0;
+    const uint64_t *lines = nullptr;
+    uint64_t n_entries = 0;
+    const uint32_t *bits = nullptr;
+    uint64_t nwords = 0;
+};
+inline KeySource list_source(const uint64_t *keys, uint64_t n) { KeySource s; s.keys = keys; s.n = n; return s; }
+inline KeySource table_source(const uint64_t *lines, uint64_t n_lines) { KeySource s; s.lines = lines; s.n_entries = n_lines * 8ull; return s; }
+inline KeySource bits_source(const uint32_t *bits, uint64_t nwords) { KeySource s; s.bits = bits; s.nwords = nwords; return s; }
+
 #if defined(__HIPCC__)
+
+// entry i of a table's lines as a slot: the key + 1, 0 for an empty slot and for the line's header (entry 7)
+__device__ __forceinline__ uint64_t table_slot_key(const uint64_t *__restrict__ lines, uint64_t i)
+{
+    return (i & 7ull) == 7ull ? 0ull : lines[i];
+}
+
+// f(key) for every key of the source (key = canonical >> 1), each once, in a grid-stride loop; the kind is uniform per launch
+template <class F>
+__device__ __forceinline__ void for_each_key(const KeySource &src, F f)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, first = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (src.keys)
+        for (uint64_t i = first; i < src.n; i += stride)
+            f(src.keys[i]);
+    else if (src.lines)
+        for (uint64_t i = first; i < src.n_entries; i += stride) {
+            if (const uint64_t v = table_slot_key(src.lines, i))
+                f(v - 1ull);
+        }
+    else
+        for (uint64_t w = first; w < src.nwords; w += stride)
+            for (uint32_t x = src.bits[w]; x; x &= x - 1u)
+                f(w * 32ull + (uint64_t)(__ffs(x) - 1));
+}
 
 // hash of the minimizer of a k-mer: min over its W m-mers of (min(m-mer, revcomp(m-mer)) * odd) mod 2^32,
 // an injective order of the canonical m-mers, so equal hashes mean equal minimizers.

@@ -11,6 +11,8 @@
 #include "../../include/brx.h"
 #include "brx_kmer.hpp"
 #include "brx_devbuf.hpp"
+#include "brx_setstate.hpp"
+#include "brx_index.hpp"
 
 namespace brx {
 
@@ -97,19 +99,35 @@ inline uint64_t set_nbytes_file(int k) { return (set_nbits(k) + 7) / 8; }
 
 } // namespace brx
 
+// A solid set.  Its keys can be held four ways at once; who holds them RIGHT NOW is set_holder's rule (brx_setstate.hpp),
+// asked through set_keys below, and the flags are written through bits_mark / keylist_mark / index_mark alone.
+// The reachable states, and the entry that leaves each:
+//   bits     current   brx_set_new, a .solid stream, a dense or table finish (k <= 19), a partitioned finish at k outside the
+//                      indexed range or under BRX_LAZY_BITS=0, key files and set algebra (set_build_from_keys), and any
+//                      lazy set after ensure_bits
+//            lazy      (bits_stale) the partitioned finish at indexed k <= 19: allocated, not written
+//            sparse    k >= 21, BRX_FORCE_SPARSE: no vector at all
+//   list     none      sets that never had one; every mutation of the bits (index_invalidate); a table built from a
+//                      foreign list while there are no bits (brx_set_index_build_from_keys_device); insert into a sparse set
+//            complete  a finish at indexed k, key files and set algebra at indexed k (those two: sorted); the empty list of
+//                      a fresh sparse set
+//            truncated the device counter passed the capacity: only the partitioned finish that also writes current bits
+//                      (BRX_LAZY_BITS=0) sizes its list below the exact bound, so only current bits meet it
+//   index    none      until something asks; after index_invalidate / brx_set_index_drop
+//            accelerator  built while the bits were current (index_ensure, brx_set_index_build): overflowed lines defer to the bits
+//            exact, closed  built while there were no bits: chained, answers alone; stays exact if the bits appear later
+//            exact, open    brx_set_insert_batch on a sparse set: the table is the set, more can be added, no list
+//   lazy or sparse x no complete list x no exact table holds no keys (SetHolder::None): brx_set_index_drop on a set whose
+//   table was all it had gets there, and every enumerating entry refuses it in its own words.
 struct brx_set {
     int k;
     int device;
     uint64_t nwords;   // u32 words
     brx::DevBuf<uint32_t> d_bits; // nwords, zero padded; empty for a sparse set
-    // sparse set (k >= 21: 2^(2k-1) bits do not fit): the solid hashes live in the key list and in the probe
-    // index only, whose overflowing lines then chain into the next line instead of falling back to the bits
     bool sparse;
-    // lazy bit vector (k <= 19): a partitioned finish leaves only the key list; the bits are materialised from it
-    // (or from the chained index) by the first entry point that really needs them -- correction with One does not
     bool bits_stale;
     bool idx_exact;          // the index was built with chaining (answers without the bit vector)
-    bool idx_open;           // ... and k-mer by k-mer (brx_set_insert_batch on a sparse set): more can be added
+    bool idx_open;           // ... and k-mer by k-mer: more can be added
     // probe index over the same set (brx_index.hpp): built on demand, invalidated by every mutation
     // of the bits that goes through the ABI
     brx::DevBuf<uint64_t> d_lines; // 8 u64 per line
@@ -127,13 +145,10 @@ struct brx_set {
     uint64_t succ_gen = ~0ull;   // idx_gen it was built at
     uint64_t idx_gen = 0;
     uint64_t idx_keys, idx_overflow_keys;
-    // solid hashes of the current bits, when the builder produced them on the side (partitioned finish)
     brx::DevBuf<uint64_t> d_keylist;             // (its cap(): entries)
     brx::DevBuf<unsigned long long> d_keylist_n; // device counter (may exceed the list's capacity: list truncated)
     bool keylist_valid;
-    // the valid key list is known to ascend strictly (it came from a key file or from set algebra): listing it needs no
-    // sort.  Written through keylist_mark alone, which every site that validates or drops the list calls.
-    bool keylist_sorted = false;
+    bool keylist_sorted = false; // the valid list is known to ascend strictly: listing it needs no sort
     std::mutex idx_mu;
 };
 
@@ -157,9 +172,39 @@ inline bool no_bits(const brx_set *set) { return set->sparse || set->bits_stale;
 int ensure_bits(const brx_set *set, hipStream_t s, const char *what);
 // builds the index from the bitset when the set has none (no-op for k outside the indexed range)
 int index_ensure(const brx_set *set, hipStream_t s);
-// the one place keylist_valid is written: a list is in order only where its writer says so
+// the one place each group of flags is written.  keylist_mark: a list is in order only where its writer says so.
+// bits_mark: the vector is written (or being written on the caller's stream) / allocated but unwritten.  index_mark: what
+// a finished build leaves -- chained, open to more k-mers, occupancy bits filled.
 inline void keylist_mark(brx_set *set, bool valid, bool sorted = false) { set->keylist_valid = valid; set->keylist_sorted = valid && sorted; }
+inline void bits_mark(brx_set *set, bool current) { set->bits_stale = !current; }
+inline void index_mark(brx_set *set, bool exact, bool open, bool linebits) { set->idx_exact = exact; set->idx_open = open; set->idx_linebits = linebits; set->idx_valid = true; set->idx_gen++; }
 inline void index_invalidate(brx_set *set) { set->idx_valid = false; set->idx_declined = false; keylist_mark(set, false); }
+// Who holds the keys, resolved (brx_index.hip): the holder and what to read it through.  set_keys takes idx_mu, reads the
+// list's counter once -- one 8-byte readback on `s` and its synchronisation, only when a list is attached -- and asks
+// set_holder; set_keys_locked is the same for a caller that holds idx_mu.  None is not an error here: each caller has
+// its own words for it.  listed_n / list_cap are what the rule was asked with (0 / the buffer's entries without a list).
+struct SetKeys {
+    SetHolder holder = SetHolder::None;
+    KeySource src;           // the holder, as a kernel enumerates it (brx_index.hpp); a list's n is src.n
+    bool sorted = false;     // KeyList: known to ascend strictly
+    uint64_t table_keys = 0; // Table: the keys it holds
+    uint64_t listed_n = 0, list_cap = 0;
+};
+int set_keys(const brx_set *set, hipStream_t s, SetKeys *out);
+int set_keys_locked(const brx_set *set, hipStream_t s, SetKeys *out);
+// the number of keys, on `s` (brx_set.hip): the list's, the table's, or the popcount kernel's.  A set that holds no keys
+// answers what its truncated list counted (0 without one), as brx_set_popcount always has.
+int keys_count(const brx_set *set, const SetKeys &keys, hipStream_t s, uint64_t *n);
+int set_count(const brx_set *set, hipStream_t s, uint64_t *n);
+// the keys of a current bit vector into d_out (brx_set.hip): popcount, room for them and `spare` more (at least one entry),
+// extract; returns after `s` has run them.  counted: the popcount where the caller has taken it already.  A lazy vector is
+// materialised first, a sparse set refused (ensure_bits).
+int keys_from_bits(const brx_set *set, hipStream_t s, DevBuf<uint64_t> &d_out, uint64_t *n_out, uint64_t spare = 0,
+                   const uint64_t *counted = nullptr);
+// every slot of a chained table that holds a key seen at least min_count times (counts == nullptr: every key), compacted
+// into d_keys / d_cnts in no order, *d_n (zeroed by the caller) counting them past `cap` too (brx_keyfile.hip; timer "key_list")
+int table_list(const uint64_t *lines, const uint32_t *counts, uint64_t n_entries, uint32_t min_count, uint64_t *d_keys, uint8_t *d_cnts,
+               uint64_t cap, unsigned long long *d_n, hipStream_t s);
 int index_auto_m(int k, uint64_t n_keys);
 bool index_wanted(int k);
 }
@@ -244,7 +289,7 @@ int tab_info(brx_counter *c, uint64_t *info4, hipStream_t s);
 int set_alloc_unwritten(int k, int device, brx_set **out);
 // What set algebra (brx_setops.hip) shares with the key files (brx_keyfile.hip).  keys_scan_exclusive: d_data[0 .. n) in
 // place, d_sums holds keys_scan_sums(n) + 1 entries and the last one receives the total.  keys_sort: brx_sort_keys_device.
-// set_list_keys: the keys of a set, whatever holds it, into d_out, *sorted telling whether they are known to ascend (a key
+// set_list_keys (brx_index.hip, on set_keys): the keys of a set, whatever holds it, into d_out, *sorted telling whether they are known to ascend (a key
 // list marked so); the set is only read, a lazy bit vector stays lazy.  set_build_from_keys: makes a set_alloc_unwritten set the closed set of n sorted keys -- d_keys (exactly n entries,
 // empty for n = 0) becomes its key list, a sparse set builds its chained index, the others write their bits and keep the
 // list where index_wanted(k); `me` names the entry in messages.  keys_sort and set_build_from_keys return after `s` has been

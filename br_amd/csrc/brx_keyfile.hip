@@ -5,8 +5,8 @@
 //            4096 slots placed by a block scan and one atomic per block trip; keys with min(255, count) >= min_count and
 //            their count bytes; the counter is only read.  A partitioned counter: its count view compacted in place
 //            order (view_count_kernel, a scan, view_write_kernel) -- sorted already, the sort below finds nothing to do
-//            and is not called.  A set: its key
-//            list as it is, the lines of its chained table (the same kernel, no counts), or the bits (brx_set_extract_keys_device).
+//            and is not called.  A set: set_list_keys
+//            (brx_index.hip) -- its key list as it is, the lines of its chained table (the same kernel, no counts), or the bits.
 //   sort     stable LSD radix sort of (u64 key, optional u8 payload), 8-bit digits, ceil(key_bits / 8) passes between two
 //            buffers.  A pass is three steps, each its own launches: digit histograms per tile of 4096 keys, an exclusive
 //            scan of the (digit, tile) counts, a scatter that ranks the keys inside their tile.  No workgroup ever waits
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void table_list_kernel(const uint64_t *__restr
         uint32_t mine = 0;
         for (uint32_t j = 0; j < LIST_PER_THREAD; j++) {
             const uint64_t i = c * LIST_CHUNK + (uint64_t)j * 256u + threadIdx.x;
-            const uint64_t x = (i & 7ull) == 7ull || i >= n_slots ? 0ull : lines[i]; // (entry 7 is the line's header)
+            const uint64_t x = i >= n_slots ? 0ull : table_slot_key(lines, i);
             const uint32_t cnt = (x && counts) ? table_count_read(counts[i]) : 1u;
             const bool keep = x && cnt >= min_count;
             v[j] = keep ? x : 0ull;
@@ -1158,77 +1158,6 @@ int list_view(const brx_counter *c, uint8_t floor, hipStream_t s, DevScratch &ws
     return BRX_OK;
 }
 
-// the keys of a set, whatever holds it, into d_out; a lazy bit vector stays lazy.  *sorted (may be null): the keys are known
-// to ascend strictly -- they are a key list that says so (brx_set::keylist_sorted)
-int list_set(const brx_set *cset, hipStream_t s, DevBuf<uint64_t> &d_out, uint64_t *n_out, bool *sorted = nullptr)
-{
-    brx_set *set = const_cast<brx_set *>(cset);
-    d_out.reset();
-    *n_out = 0;
-    if (sorted)
-        *sorted = false;
-    {
-        std::lock_guard<std::mutex> g(set->idx_mu);
-        if (set->keylist_valid) {
-            u64 nl = 0;
-            BRX_HIP(hipMemcpyAsync(&nl, set->d_keylist_n, 8, hipMemcpyDeviceToHost, s));
-            BRX_HIP(hipStreamSynchronize(s));
-            if (nl <= set->d_keylist.cap()) { // (a truncated list is no list)
-                if (sorted)
-                    *sorted = set->keylist_sorted;
-                if (nl) {
-                    BRX_TRY(d_out.reserve(nl, 0, "keys of the set"));
-                    KernelTimer kt("key_list", s);
-                    BRX_HIP(hipMemcpyAsync(d_out, set->d_keylist, nl * 8, hipMemcpyDeviceToDevice, s));
-                }
-                *n_out = nl;
-                return BRX_OK;
-            }
-        }
-        if (no_bits(set)) {
-            if (!set->idx_valid || !set->idx_exact || !set->d_lines) {
-                set_error("brx_set_save_fd: the set has neither a bit vector, nor a key list, nor a table");
-                return BRX_ERR_UNSUPPORTED;
-            }
-            const uint64_t cap = set->idx_keys, n_slots = 8ull << set->idx_log_lines;
-            if (!cap)
-                return BRX_OK;
-            DevScratch ws;
-            u64 *d_n = nullptr;
-            BRX_TRY(ws.get(&d_n, 1));
-            BRX_HIP(hipMemsetAsync(d_n, 0, 8, s));
-            BRX_TRY(d_out.reserve(cap, 0, "keys of the set"));
-            {
-                KernelTimer kt("key_list", s);
-                table_list_kernel<<<grid_of(n_slots, LIST_CHUNK), 256, 0, s>>>(set->d_lines, nullptr, n_slots, 1u, d_out, nullptr, cap, d_n);
-                BRX_HIP(hipGetLastError());
-            }
-            u64 got = 0;
-            BRX_HIP(hipMemcpyAsync(&got, d_n, 8, hipMemcpyDeviceToHost, s));
-            BRX_HIP(hipStreamSynchronize(s));
-            if (got != cap) {
-                set_error("brx_set_save_fd: %llu keys in the table of a set of %llu", got, (u64)cap);
-                return BRX_ERR_HIP;
-            }
-            *n_out = got;
-            return BRX_OK;
-        }
-    }
-    // the bit vector (current: a lazy one has a key list or an exact table and was served above)
-    uint64_t n = 0, got = 0;
-    BRX_HIP(hipStreamSynchronize(s));
-    BRX_TRY(brx_set_popcount(set, &n));
-    if (!n)
-        return BRX_OK;
-    BRX_TRY(d_out.reserve(n, 0, "keys of the set"));
-    {
-        KernelTimer kt("key_list", s);
-        BRX_TRY(brx_set_extract_keys_device(set, 0, set->nwords * 32, d_out, n, &got, s));
-    }
-    *n_out = got;
-    return BRX_OK;
-}
-
 } // namespace
 
 // ---- what set algebra (brx_setops.hip) shares with the key files ------------------------------------------------------------
@@ -1237,7 +1166,14 @@ namespace brx {
 uint64_t keys_scan_sums(uint64_t n) { return (n + SCAN_CHUNK - 1) / SCAN_CHUNK; }
 int keys_scan_exclusive(unsigned long long *d_data, uint64_t n, unsigned long long *d_sums, hipStream_t s) { return scan_exclusive(d_data, n, d_sums, s); }
 int keys_sort(uint64_t *d_keys, uint8_t *d_pay, uint64_t n, uint32_t key_bits, hipStream_t s) { return sort_pairs(d_keys, d_pay, n, key_bits, s); }
-int set_list_keys(const brx_set *set, hipStream_t s, DevBuf<uint64_t> &d_out, uint64_t *n_out, bool *sorted) { return list_set(set, s, d_out, n_out, sorted); }
+int table_list(const uint64_t *lines, const uint32_t *counts, uint64_t n_entries, uint32_t min_count, uint64_t *d_keys, uint8_t *d_cnts,
+               uint64_t cap, unsigned long long *d_n, hipStream_t s)
+{
+    KernelTimer kt("key_list", s);
+    table_list_kernel<<<grid_of(n_entries, LIST_CHUNK), 256, 0, s>>>(lines, counts, n_entries, min_count, d_keys, d_cnts, cap, d_n);
+    BRX_HIP(hipGetLastError());
+    return BRX_OK;
+}
 
 int set_build_from_keys(brx_set *set, DevBuf<uint64_t> &d_keys, uint64_t n_keys, hipStream_t s, const char *me)
 {
@@ -1251,7 +1187,7 @@ int set_build_from_keys(brx_set *set, DevBuf<uint64_t> &d_keys, uint64_t n_keys,
     if (set->sparse) {
         BRX_TRY(index_build_from_keys(set, set->d_keylist, n_keys, 0, 0, s));
     } else {
-        set->bits_stale = true; // (nothing written yet)
+        bits_mark(set, false); // (nothing written yet)
         BRX_TRY(ensure_bits(set, s, me));
         if (!index_wanted(set->k)) { // as after a finish at this k: the bits are the set
             keylist_mark(set, false);
@@ -1347,11 +1283,7 @@ int brx_counter_save_fd(brx_counter_t *c, uint8_t min_count, int out_fd, uint64_
         BRX_TRY(ws.get(&d_n, 1));
         BRX_HIP(hipMemsetAsync(d_n, 0, 8, s));
         const uint64_t n_slots = 8ull << log_lines;
-        {
-            KernelTimer kt("key_list", s);
-            table_list_kernel<<<grid_of(n_slots, LIST_CHUNK), 256, 0, s>>>(lines, counts, n_slots, floor, d_keys, d_cnts, cap, d_n);
-            BRX_HIP(hipGetLastError());
-        }
+        BRX_TRY(table_list(lines, counts, n_slots, floor, d_keys, d_cnts, cap, d_n, s));
         u64 got = 0;
         BRX_HIP(hipMemcpyAsync(&got, d_n, 8, hipMemcpyDeviceToHost, s));
         BRX_HIP(hipStreamSynchronize(s));
@@ -1455,7 +1387,7 @@ int brx_set_save_fd(const brx_set_t *set, int out_fd, uint64_t *stats8)
     BRX_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     DevBuf<uint64_t> d_keys;
     uint64_t n = 0;
-    int st = list_set(set, s, d_keys, &n);
+    int st = set_list_keys(set, s, d_keys, &n, nullptr);
     if (st == BRX_OK)
         st = sort_pairs(d_keys, nullptr, n, (uint32_t)(2 * set->k - 1), s);
     st8[4] = ns_since(t0);

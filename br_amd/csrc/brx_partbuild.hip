@@ -2230,7 +2230,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
             keylist_mark(dst, true); // the empty list
         } else {
             BRX_HIP(hipMemsetAsync(dst->d_bits, 0, dst->nwords * 4, s));
-            dst->bits_stale = false;
+            bits_mark(dst, true);
         }
         return BRX_OK;
     } else if (st->batches.size() == 1) {
@@ -2343,7 +2343,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
         BRX_HIP(hipGetLastError());
         trace_stage(s, "hash final");
         keylist_mark(dst, true);
-        dst->bits_stale = lazy;
+        bits_mark(dst, !lazy);
         return BRX_OK;
     }
     const uint64_t *fin_off = st->d_coff[pl.nlev - 1];
@@ -2389,7 +2389,7 @@ static int part_finish_impl(brx_counter *c, uint32_t abundance, hipStream_t s, b
     BRX_HIP(hipGetLastError());
     trace_stage(s, "final count");
     keylist_mark(dst, emit);
-    dst->bits_stale = lazy;
+    bits_mark(dst, !lazy);
     return BRX_OK;
 }
 

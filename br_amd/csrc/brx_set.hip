@@ -268,16 +268,6 @@ __global__ __launch_bounds__(256) void extract_kernel(const uint32_t *__restrict
     }
 }
 
-__global__ void or_keys_kernel(uint32_t *__restrict__ bits, const uint64_t *__restrict__ keys, uint64_t n, uint64_t nbits)
-{
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint64_t h = keys[i];
-        if (h < nbits)
-            atomicOr(bits + (h >> 5), 1u << (h & 31u));
-    }
-}
-
 int check_k(int k, bool need_odd)
 {
     if (k < 1 || k > 31) {
@@ -347,6 +337,45 @@ int grid_for(uint64_t items, int per_block, int cap = 256 * 8)
 namespace brx {
 // a set of this k with nothing written yet (brx_set_load_fd fills it from a key list)
 int set_alloc_unwritten(int k, int device, brx_set **out) { return alloc_set(k, device, false, out); }
+int keys_count(const brx_set *set, const SetKeys &keys, hipStream_t s, uint64_t *n)
+{
+    if (keys.holder != SetHolder::Bits) {
+        *n = keys.holder == SetHolder::KeyList ? keys.src.n : keys.holder == SetHolder::Table ? keys.table_keys : keys.listed_n;
+        return BRX_OK;
+    }
+    BRX_TRY(use_device(set->device));
+    DevBuf<unsigned long long> d_t;
+    BRX_TRY(d_t.reserve(1, 0, "popcount"));
+    BRX_HIP(hipMemsetAsync(d_t, 0, 8, s));
+    popcount_kernel<<<grid_for(keys.src.nwords, 256 * 8), 256, 0, s>>>(keys.src.bits, keys.src.nwords, d_t);
+    unsigned long long t = 0;
+    BRX_HIP(hipMemcpyAsync(&t, d_t, 8, hipMemcpyDeviceToHost, s));
+    BRX_HIP(hipStreamSynchronize(s));
+    *n = t;
+    return BRX_OK;
+}
+
+int set_count(const brx_set *set, hipStream_t s, uint64_t *n)
+{
+    SetKeys keys;
+    BRX_TRY(set_keys(set, s, &keys));
+    return keys_count(set, keys, s, n);
+}
+
+int keys_from_bits(const brx_set *set, hipStream_t s, DevBuf<uint64_t> &d_out, uint64_t *n_out, uint64_t spare, const uint64_t *counted)
+{
+    BRX_TRY(ensure_bits(set, s, "extract_keys (use brx_set_keylist_device)"));
+    SetKeys bits;
+    bits.holder = SetHolder::Bits;
+    bits.src = bits_source(set->d_bits, set->nwords);
+    uint64_t n = counted ? *counted : 0;
+    if (!counted)
+        BRX_TRY(keys_count(set, bits, s, &n));
+    const uint64_t cap = n + spare ? n + spare : 1;
+    BRX_TRY(d_out.reserve(cap, 0, "keys of the set"));
+    return brx_set_extract_keys_device(set, 0, set->nwords * 32, d_out, cap, n_out, s);
+}
+
 // used by the correction chain and the host-pointer entry points
 int upload_batch(const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, DevBuf<uint8_t> &d_bases, DevBuf<uint64_t> &d_off,
                  uint64_t *total, hipStream_t stream)
@@ -549,26 +578,7 @@ int brx_set_popcount(const brx_set_t *set, uint64_t *n_set_bits)
 {
     if (!set || !n_set_bits)
         return BRX_ERR_ARG;
-    BRX_TRY(use_device(set->device));
-    if (no_bits(set)) {
-        if (set->idx_valid) {
-            *n_set_bits = set->idx_keys;
-            return BRX_OK;
-        }
-        unsigned long long nl = 0;
-        if (set->keylist_valid)
-            BRX_HIP(hipMemcpy(&nl, set->d_keylist_n, 8, hipMemcpyDeviceToHost));
-        *n_set_bits = nl;
-        return BRX_OK;
-    }
-    DevBuf<unsigned long long> d_t;
-    BRX_TRY(d_t.reserve(1, 0, "popcount"));
-    BRX_HIP(hipMemset(d_t, 0, 8));
-    popcount_kernel<<<grid_for(set->nwords, 256 * 8), 256>>>(set->d_bits, set->nwords, d_t);
-    unsigned long long t = 0;
-    BRX_HIP(hipMemcpy(&t, d_t, 8, hipMemcpyDeviceToHost));
-    *n_set_bits = t;
-    return BRX_OK;
+    return set_count(set, nullptr, n_set_bits);
 }
 
 int brx_set_device_bits(const brx_set_t *set, void **d_bits, uint64_t *n_bytes)
@@ -753,7 +763,7 @@ int brx_set_count_finish_into(brx_counter_t *c, uint8_t abundance, void *stream,
         set_error("the dense count strategy needs a bit vector; a sparse set (k=%d) has none", dst->k);
         return BRX_ERR_UNSUPPORTED;
     }
-    dst->bits_stale = false; // every word is written below
+    bits_mark(dst, true); // every word is written below
     {
         KernelTimer t("threshold", s);
         threshold_kernel<<<grid_for(dst->nwords, 256, 256 * 16), 256, 0, s>>>((const uint4 *)c->d_counts.get(), dst->nwords,
@@ -969,24 +979,6 @@ int brx_set_extract_keys_device(const brx_set_t *set, uint64_t first_hash, uint6
         set_error("extract found %llu keys, buffer holds %llu", n, (unsigned long long)cap);
         return BRX_ERR_OVERFLOW;
     }
-    return BRX_OK;
-}
-
-int brx_set_or_keys_device(brx_set_t *set, const uint64_t *d_keys, uint64_t n, void *stream)
-{
-    if (!set || (!d_keys && n))
-        return BRX_ERR_ARG;
-    BRX_TRY(need_bits(set, "or_keys (use brx_set_index_build_from_keys_device)"));
-    BRX_TRY(use_device(set->device));
-    if (!n)
-        return BRX_OK;
-    index_invalidate(set);
-    hipStream_t s = (hipStream_t)stream;
-    {
-        KernelTimer t("or_keys", s);
-        or_keys_kernel<<<grid_for(n, 256, 256 * 8), 256, 0, s>>>(set->d_bits, d_keys, n, set->nwords * 32);
-    }
-    BRX_HIP(hipGetLastError());
     return BRX_OK;
 }
 
