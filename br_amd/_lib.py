@@ -43,6 +43,13 @@ class OutputOpts(C.Structure):
 
 OUT_MODES = {"plain": 0, "mask": 1, "split": 2}
 
+
+class TrustOpts(C.Structure):
+    _fields_ = [("min_quality", C.c_uint8), ("acgt_only", C.c_uint8), ("reserved", C.c_uint16), ("min_len", C.c_uint32)]
+
+
+READ_FORMATS = {"fasta": 0, "fastq": 1}
+
 _vp, _u8p, _u64p = C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)
 _pp = C.POINTER(C.c_void_p)
 
@@ -84,6 +91,10 @@ SIGNATURES = {
                                                    _vp, _vp, C.c_uint32, C.POINTER(C.c_uint32), _u64p, _vp]),
     "brx_set_cover_split_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.POINTER(_u8p), C.POINTER(_u64p),
                                             C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(_u64p), C.POINTER(C.c_uint32)]),
+    "brx_trust_split_batch_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(TrustOpts), _vp, C.c_uint64, _vp,
+                                               _vp, _vp, C.c_uint32, _vp, C.POINTER(C.c_uint32), _u64p, C.c_int, _vp]),
+    "brx_trust_split_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(TrustOpts), C.POINTER(_u8p), C.POINTER(_u64p),
+                                        C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(_u64p), _vp, C.POINTER(C.c_uint32), C.c_int]),
     "brx_set_free": (None, [_vp]),
     "brx_set_count_begin": (C.c_int, [C.c_uint8, C.c_int, C.c_int, _pp]),
     "brx_set_count_add_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
@@ -152,6 +163,8 @@ SIGNATURES = {
                                              C.POINTER(OutputOpts), _u64p, _u64p]),
     "brx_count_fasta_fd": (C.c_int, [_vp, C.c_int, C.c_uint32, _u64p]),
     "brx_set_insert_fasta_fd": (C.c_int, [_vp, C.c_int, C.c_uint32, _u64p]),
+    "brx_count_reads_fd": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.POINTER(TrustOpts), _u64p, _u64p]),
+    "brx_set_insert_reads_fd": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.POINTER(TrustOpts), _u64p, _u64p]),
     "brx_set_insert_batch_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp]),
     "brx_synth_genome_device": (C.c_int, [C.POINTER(Synth), C.c_int, _vp, _vp]),
     "brx_synth_reads_device": (C.c_int, [C.POINTER(Synth), C.c_int, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64,

@@ -43,6 +43,18 @@ Not in the reference, like `--device` (include/brx.h "coverage"; a base is cover
                                sniffed, of the same k as the set in use:
                                  python -m br_amd -i reads.fa -o corr.fa --set-or illumina.keys --set-minus mito.keys \
                                      --save-set final.keys -c one fasta -i reads.fa -k 21 -a 3
+    fastq -i R.fq [-i ...] -k K (-a N | first-minimum | ...) [-q MINQ] [--all-bytes]
+                               a sub-command like `fasta` that counts FASTQ reads (gz / bz2 / xz sniffed), and only the k-mers
+                               none of whose bases is untrusted: a base is untrusted when it is not ACGTacgt or its quality
+                               (Phred+33) lies below MINQ (default 0: no floor).  --all-bytes counts every byte as a base, as
+                               `fasta` does.  The reads are cut into their trusted stretches on the GPU (br_amd/trust.py), the
+                               counters take the pieces; -a, the threshold selectors, --save-counts, --abundance-report,
+                               --save-set and --set-* work as with `fasta`.  One line of totals goes to stderr:
+                                 python -m br_amd -i reads.fa -o corr.fa --save-set illumina.keys -c one \
+                                     fastq -i illumina.fq.gz -k 21 -q 20 first-minimum
+    fasta ... --skip-non-acgt  count only the k-mers of ACGTacgt bases (off by default: the reference counts every byte)
+    solid | large-kmer -f fastq|fasta ... [-q MINQ] [--skip-non-acgt]
+                               the same two switches for the presence-only sets
     --second-pass MODE         reverse (default: the reference's second scan, reads reversed and not complemented),
                                revcomp (the second scan on the reverse complement: br_amd/strand.py) or none (= -s)
 """
@@ -56,7 +68,7 @@ import lzma
 import sys
 from typing import BinaryIO, List, Optional
 
-from . import _lib, abundance, fasta, keyfile, spectrum, strand
+from . import _lib, abundance, fasta, keyfile, spectrum, strand, trust
 from .correct import build_methods
 from .driver import run_correction
 from .set import Counter, Pcon
@@ -76,6 +88,17 @@ def u8(text: str) -> int:
     return v
 
 
+def min_quality(text: str) -> int:
+    """-q MINQ: a Phred score, 0..93 (Phred+33 ends at '~')"""
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("invalid digit found in string: %r" % text)
+    if not 0 <= v <= trust.MAX_QUALITY:
+        raise argparse.ArgumentTypeError("%r is not in 0..=%d" % (text, trust.MAX_QUALITY))
+    return v
+
+
 def min_len(text: str) -> int:
     try:
         v = int(text)
@@ -84,6 +107,9 @@ def min_len(text: str) -> int:
     if not 0 <= v < 1 << 32:
         raise argparse.ArgumentTypeError("%r is not in 0..2^32" % text)
     return v
+
+
+COUNTING = ("fasta", "fastq", "count")  # the sub-commands that build a counter
 
 
 def output_form(args):
@@ -100,9 +126,9 @@ def abundance_reports(args):
     paths = args.abundance_report
     if paths is None:
         return None
-    if args.subcommand not in ("fasta", "count"):
+    if args.subcommand not in COUNTING:
         raise SystemExit("Error: --abundance-report asks the k-mer counter, and `%s` builds its set without a counter: "
-                         "use it with `fasta` or `count`" % args.subcommand)
+                         "use it with `fasta`, `fastq` or `count`" % args.subcommand)
     n_out = len(args.outputs) if args.outputs else 1
     if len(paths) != n_out:
         raise SystemExit("Error: %d --abundance-report for %d output(s): give one per -o" % (len(paths), n_out))
@@ -117,9 +143,9 @@ def save_counts_of(args):
         if args.save_min_count is not None:
             raise SystemExit("Error: --save-min-count goes with --save-counts")
         return None
-    if args.subcommand not in ("fasta", "count"):
+    if args.subcommand not in COUNTING:
         raise SystemExit("Error: --save-counts writes the k-mer counter, and `%s` builds its set without a counter: "
-                         "use it with `fasta` or `count` (--save-set writes the set)" % args.subcommand)
+                         "use it with `fasta`, `fastq` or `count` (--save-set writes the set)" % args.subcommand)
     return args.save_counts
 
 
@@ -240,7 +266,17 @@ def parser() -> argparse.ArgumentParser:
     f.add_argument("-i", "--inputs", dest="sub_inputs", action="append", required=True)
     f.add_argument("-k", "--kmer-size", type=int, required=True)
     f.add_argument("-a", "--abundance", type=u8, default=None)
+    f.add_argument("--skip-non-acgt", action="store_true",
+                   help="count only the k-mers of ACGTacgt bases (not in the reference, which counts every byte)")
     abundance_methods(f)
+    fq = sub.add_parser("fastq", help="With Fastq: count the trusted stretches of FASTQ reads (not in the reference)")
+    fq.add_argument("-i", "--inputs", dest="sub_inputs", action="append", required=True)
+    fq.add_argument("-k", "--kmer-size", type=int, required=True)
+    fq.add_argument("-a", "--abundance", type=u8, default=None)
+    fq.add_argument("-q", "--min-quality", type=min_quality, default=0, metavar="MINQ",
+                    help="skip the k-mers over a base of Phred quality below MINQ (Phred+33; default 0: no floor)")
+    fq.add_argument("--all-bytes", action="store_true", help="count every byte as a base, as `fasta` does (default: ACGTacgt only)")
+    abundance_methods(fq)
     s = sub.add_parser("solid", help="With Solid")
     s.add_argument("-i", "--input", dest="sub_input", required=True)
     s.add_argument("-f", "--format", choices=["solid", "fasta", "fastq", "csv", "keys"], required=True)
@@ -249,6 +285,11 @@ def parser() -> argparse.ArgumentParser:
     lk.add_argument("-i", "--input", dest="sub_input", required=True)
     lk.add_argument("-f", "--format", choices=["fasta", "fastq", "csv"], required=True)
     lk.add_argument("-k", "--kmer-size", type=int, required=True)
+    for sp in (s, lk):
+        sp.add_argument("-q", "--min-quality", type=min_quality, default=0, metavar="MINQ",
+                        help="-f fastq: skip the k-mers over a base of Phred quality below MINQ (not in the reference)")
+        sp.add_argument("--skip-non-acgt", action="store_true",
+                        help="-f fasta / fastq: skip the k-mers over a byte that is not ACGTacgt (not in the reference)")
     return p
 
 
@@ -295,16 +336,28 @@ def build_set(args, keep: Optional[dict] = None) -> Pcon:
     its count + view + compaction measured faster than the table's count + list + sort at k = 19 and k = 21 (DESIGN.md
     section 4, tools/partition_keyfile_bench.py), and main() builds the view before it saves"""
     dev = args.device
-    if args.subcommand == "fasta":
+    if args.subcommand in ("fasta", "fastq"):
         k = fasta_kmer_size(args.kmer_size)
         if args.abundance is None and args.abundance_selection is None:
             raise SystemExit("Error: You must provide an abundance method or an abundance threshold")  # main.rs:109
         # (the table takes odd k from 5; below that the dense u8 table is the default anyway and can be looked up too)
         view_save = keep is not None and args.abundance_report is None and 15 <= k <= 21
         cnt = Counter(k, dev) if keep is None or view_save else Counter(k, dev, _lib.COUNT_TABLE if k >= 5 else _lib.COUNT_DENSE)
+        tot = dict.fromkeys(trust.TOTALS, 0)
         for path in args.sub_inputs:
             with open_input(path) as f:
-                cnt.count_fasta(f)
+                if args.subcommand == "fastq":
+                    st = cnt.count_reads(f, "fastq", args.min_quality, not args.all_bytes)
+                elif args.skip_non_acgt:
+                    st = cnt.count_reads(f, "fasta", 0, True)
+                else:
+                    cnt.count_fasta(f)  # the reference's rule, and its launches: every k-mer, every byte a base
+                    continue
+                for name in tot:
+                    tot[name] += st["trust"][name]
+        if args.subcommand == "fastq":
+            sys.stderr.write("fastq: %(bases)d bases, %(non_acgt)d not ACGT, %(low_quality)d below the quality floor, "
+                             "%(pieces)d trusted stretches of %(kept_bases)d bases, %(kmers)d k-mers counted\n" % tot)
         return threshold_and_finish(cnt, args, keep)
     if args.subcommand == "solid":
         if args.format == "solid":
@@ -318,7 +371,7 @@ def build_set(args, keep: Optional[dict] = None) -> Pcon:
                     raise SystemExit(f"Error: {args.sub_input}: {e}")
         if args.kmer_size is None:
             raise SystemExit("Error: Solid input fasta require kmer size")            # error.rs SolidRequireKmerSize
-        return presence_set(args.sub_input, args.format, args.kmer_size, dev)
+        return presence_set(args.sub_input, args.format, args.kmer_size, dev, args.min_quality, args.skip_non_acgt)
     if args.subcommand == "count":
         # src/main.rs:59-70: Counter::from_stream, then the same threshold -> Solid::from_count as `fasta`
         # a key file (--save-counts) is told from a pcon table by its magic, after decompression
@@ -337,17 +390,22 @@ def build_set(args, keep: Optional[dict] = None) -> Pcon:
     # of the {k-mer, revcomp} pair for even k.
     if args.kmer_size % 2 == 0 or not 1 <= args.kmer_size <= 31:
         raise SystemExit("Error: large-kmer mode needs an odd k <= 31 on the HIP path (k=%d)" % args.kmer_size)
-    return presence_set(args.sub_input, args.format, args.kmer_size, dev)
+    return presence_set(args.sub_input, args.format, args.kmer_size, dev, args.min_quality, args.skip_non_acgt)
 
 
-def presence_set(path: str, fmt: str, k: int, dev: int) -> Pcon:
+def presence_set(path: str, fmt: str, k: int, dev: int, min_q: int = 0, skip_non_acgt: bool = False) -> Pcon:
     """Pcon::from_fasta / from_fastq / from_csv and their set::Hash twins: every canonical k-mer of every record
-    (FASTA through the native pipeline; FASTQ and CSV -- optional features of the reference -- parsed on the host)"""
+    (FASTA and FASTQ through the native pipeline; CSV -- an optional feature of the reference -- parsed on the host).
+    min_q / skip_non_acgt (not in the reference): only the k-mers of the trusted stretches (br_amd/trust.py)"""
+    if fmt == "csv" and (min_q or skip_non_acgt):
+        raise SystemExit("Error: -q / --skip-non-acgt go with -f fasta or -f fastq")
+    if fmt == "fasta" and min_q:
+        raise SystemExit("Error: -q needs qualities: use it with -f fastq")
     with open_input(path) as f:
-        if fmt == "fasta":
+        if fmt == "fasta" and not skip_non_acgt:
             return Pcon.from_fasta_file(f, k, dev)
-        if fmt == "fastq":
-            return Pcon.from_fasta(fasta.read_fastq_sequences(f), k, dev)
+        if fmt in ("fasta", "fastq"):
+            return Pcon.from_reads_file(f, fmt, k, dev, min_q, skip_non_acgt)
         try:
             return Pcon.from_fasta(fasta.read_csv_kmers(f, k), k, dev)
         except ValueError as e:

@@ -24,9 +24,11 @@
 // Split form: the cover kernel also leaves the number of run starts per tile; an exclusive scan numbers the runs of the
 // batch in (read, position) order, a second pass over the flags writes every run's start and -- the i-th end of a
 // batch belongs to the i-th start -- its end; runs of at least min_len bases are numbered and laid out by two more
-// scans, and a copy kernel moves them.  The order of the output is fixed by those scans, never by timing.
+// scans, and a copy kernel moves them (brx_pieces.hpp, shared with the trusted stretches of brx_trust.hip).  The order of
+// the output is fixed by those scans, never by timing.
 #include "brx_correct.hpp"
 #include "brx_tiles.hpp"
+#include "brx_pieces.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -50,16 +52,8 @@ struct CoverArgs {
     uint32_t *tile_runs;              // run starts per tile              [tile bound]
     // split form
     const uint64_t *run_base;         // exclusive scan of tile_runs      [tile bound + 1]
-    uint32_t *run_read, *run_start, *run_end; // [runs]
-    const unsigned long long *n_runs;
-    uint32_t min_len;
-    uint32_t *keep_flag, *keep_len;   // [runs]
-    const uint64_t *piece_of;         // exclusive scan of keep_flag      [runs + 1]
-    const uint64_t *byte_of;          // exclusive scan of keep_len       [runs + 1]
-    uint8_t *out;
-    uint64_t *out_offsets;
-    uint32_t *piece_read;
-    uint64_t *piece_start;
+    PieceArgs pc;                     // the runs, what is kept of them and where it goes (brx_pieces.hpp); its bases /
+                                      // offsets are the batch's
 };
 
 // set_get<IDX, LINE_BITS_IN_L2> (brx_index.hpp), kept written out for this one kernel: through the shared function
@@ -196,11 +190,11 @@ __global__ __launch_bounds__(256) void cover_runs_kernel(CoverArgs a)
         const uint64_t below = (1ull << lane) - 1ull;
         if ((starts >> lane) & 1ull) {
             const uint64_t i = s_at + (uint32_t)__popcll(starts & below);
-            a.run_read[i] = t.r;
-            a.run_start[i] = j;
+            a.pc.run_read[i] = t.r;
+            a.pc.run_start[i] = j;
         }
         if ((falls >> lane) & 1ull)
-            a.run_end[e_at + (uint32_t)__popcll(falls & below)] = j - 1u;
+            a.pc.run_end[e_at + (uint32_t)__popcll(falls & below)] = j - 1u;
         s_at += (uint32_t)__popcll(starts);
         e_at += (uint32_t)__popcll(falls);
         carry = (uint32_t)(Cw >> 63);
@@ -208,45 +202,7 @@ __global__ __launch_bounds__(256) void cover_runs_kernel(CoverArgs a)
             carry = (uint32_t)(Cw >> (t.p1 - pb - 1u)) & 1u;
     }
     if (t.p1 == t.n && carry && lane == 0u)
-        a.run_end[e_at] = t.n - 1u;
-}
-
-__global__ __launch_bounds__(256) void cover_keep_kernel(CoverArgs a)
-{
-    const unsigned long long n = *a.n_runs;
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256ull) {
-        const uint32_t len = a.run_end[i] - a.run_start[i] + 1u;
-        const bool keep = len >= a.min_len;
-        a.keep_flag[i] = keep ? 1u : 0u;
-        a.keep_len[i] = keep ? len : 0u;
-    }
-}
-
-// A wave per run that is kept: its row of the piece table and its bytes.
-__global__ __launch_bounds__(256) void cover_copy_kernel(CoverArgs a)
-{
-    const unsigned long long n = *a.n_runs;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        a.out_offsets[a.piece_of[n]] = a.byte_of[n];
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 4ull + wv; i < n; i += (unsigned long long)gridDim.x * 4ull) {
-        if (!a.keep_flag[i])
-            continue;
-        const uint64_t p = a.piece_of[i], at = a.byte_of[i];
-        const uint32_t r = a.run_read[i], s = a.run_start[i], len = a.keep_len[i];
-        if (lane == 0u) {
-            a.out_offsets[p] = at;
-            if (a.piece_read)
-                a.piece_read[p] = r;
-            if (a.piece_start)
-                a.piece_start[p] = s;
-        }
-        const uint8_t *src = a.bases + a.offsets[r] + s;
-        uint8_t *dst = a.out + at;
-        for (uint32_t b = lane; b < len; b += 64u)
-            dst[b] = src[b];
-    }
+        a.pc.run_end[e_at] = t.n - 1u;
 }
 
 // how the kernels reach the set.  Never writes the bit vector: a lazy one stays lazy, the index answers for it
@@ -396,7 +352,9 @@ int brx_set_cover_split_batch_device(const brx_set_t *set, const uint8_t *d_base
     a.n_reads = n_reads;
     a.bases = d_bases;
     a.offsets = d_offsets;
-    a.min_len = min_len;
+    a.pc.min_len = min_len;
+    a.pc.bases = d_bases;
+    a.pc.offsets = d_offsets;
     uint64_t tile_bound = total_bases / READ_TILE + n_reads;
     uint64_t *run_base = nullptr, *tmp = nullptr;
     unsigned long long *d_totals = nullptr; // runs, pieces, bytes
@@ -414,7 +372,7 @@ int brx_set_cover_split_batch_device(const brx_set_t *set, const uint8_t *d_base
     if (st == BRX_OK) {
         st = exclusive_scan_lens(a.tile_runs, (uint32_t)tile_bound, tmp, run_base, d_totals, s);
         a.run_base = run_base;
-        a.n_runs = d_totals;
+        a.pc.n_runs = d_totals;
     }
     auto sync = [&](int st_in) -> int {
         const hipError_t e = hipStreamSynchronize(s);
@@ -437,21 +395,21 @@ int brx_set_cover_split_batch_device(const brx_set_t *set, const uint8_t *d_base
     if (n_runs) {
         uint64_t *piece_of = nullptr, *byte_of = nullptr, *tmp2 = nullptr;
         auto enqueue = [&]() -> int {
-            BRX_TRY(sc.get(&a.run_read, n_runs));
-            BRX_TRY(sc.get(&a.run_start, n_runs));
-            BRX_TRY(sc.get(&a.run_end, n_runs));
-            BRX_TRY(sc.get(&a.keep_flag, n_runs));
-            BRX_TRY(sc.get(&a.keep_len, n_runs));
+            BRX_TRY(sc.get(&a.pc.run_read, n_runs));
+            BRX_TRY(sc.get(&a.pc.run_start, n_runs));
+            BRX_TRY(sc.get(&a.pc.run_end, n_runs));
+            BRX_TRY(sc.get(&a.pc.keep_flag, n_runs));
+            BRX_TRY(sc.get(&a.pc.keep_len, n_runs));
             BRX_TRY(sc.get(&piece_of, n_runs + 1));
             BRX_TRY(sc.get(&byte_of, n_runs + 1));
             BRX_TRY(sc.get(&tmp2, scan_tmp_bytes((uint32_t)n_runs) / 8 + 1));
             {
                 KernelTimer t("cover_runs", s);
                 cover_runs_kernel<<<(uint32_t)((tile_bound + 3ull) / 4ull), 256, 0, s>>>(a);
-                cover_keep_kernel<<<read_grid((n_runs + 255ull) / 256ull, 4096u), 256, 0, s>>>(a);
+                piece_keep_launch(a.pc, n_runs, s);
             }
-            BRX_TRY(exclusive_scan_lens(a.keep_flag, (uint32_t)n_runs, tmp2, piece_of, d_totals + 1, s));
-            BRX_TRY(exclusive_scan_lens(a.keep_len, (uint32_t)n_runs, tmp2, byte_of, d_totals + 2, s));
+            BRX_TRY(exclusive_scan_lens(a.pc.keep_flag, (uint32_t)n_runs, tmp2, piece_of, d_totals + 1, s));
+            BRX_TRY(exclusive_scan_lens(a.pc.keep_len, (uint32_t)n_runs, tmp2, byte_of, d_totals + 2, s));
             BRX_HIP(hipGetLastError());
             BRX_HIP(hipMemcpyAsync(h_tot + 1, d_totals + 1, 16, hipMemcpyDeviceToHost, s));
             return BRX_OK;
@@ -459,8 +417,8 @@ int brx_set_cover_split_batch_device(const brx_set_t *set, const uint8_t *d_base
         st = sync(enqueue());
         if (st != BRX_OK)
             return st;
-        a.piece_of = piece_of;
-        a.byte_of = byte_of;
+        a.pc.piece_of = piece_of;
+        a.pc.byte_of = byte_of;
     }
     const uint64_t pieces = h_tot[1], bytes = h_tot[2];
     *n_pieces = (uint32_t)pieces;
@@ -478,14 +436,13 @@ int brx_set_cover_split_batch_device(const brx_set_t *set, const uint8_t *d_base
         BRX_HIP(hipMemsetAsync(d_out_offsets, 0, 8, s));
         return sync(BRX_OK);
     }
-    a.out = d_out;
-    a.out_offsets = d_out_offsets;
-    a.piece_read = d_piece_read;
-    a.piece_start = d_piece_start;
+    a.pc.out = d_out;
+    a.pc.out_offsets = d_out_offsets;
+    a.pc.piece_read = d_piece_read;
+    a.pc.piece_start = d_piece_start;
     {
         KernelTimer t("cover_copy", s);
-        const uint64_t want = (n_runs + 3ull) / 4ull;
-        cover_copy_kernel<<<read_grid(want, 8192u), 256, 0, s>>>(a);
+        piece_copy_launch(a.pc, n_runs, s);
     }
     st = hipGetLastError() == hipSuccess ? BRX_OK : BRX_ERR_HIP;
     return sync(st);

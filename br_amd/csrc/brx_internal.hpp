@@ -343,6 +343,8 @@ int abund_batch(const brx_counter *c, const uint8_t *d_bases, const uint64_t *d_
 int abund_get_counts(const brx_counter *c, const uint64_t *d_kmers, uint32_t n, uint8_t *d_out, hipStream_t s);
 // sets the error of a partitioned counter that has no count view, returns BRX_ERR_UNSUPPORTED
 int abund_refuse_partitioned(const char *what, int k);
+// trusted stretches (brx_trust.hip): adds the five columns of n_reads statistics rows to d_tot5[0 .. 5), enqueued on `s`
+int trust_totals_add(const brx_trust_stats_t *d_stats, uint32_t n_reads, unsigned long long *d_tot5, hipStream_t s);
 }
 
 struct brx_chain {

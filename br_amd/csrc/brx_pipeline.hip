@@ -102,6 +102,8 @@ struct Pinned {
 struct Batch {
     uint64_t seq = 0;             // position in the stream (the writer emits in this order)
     Pinned bases;                 // concatenated sequences
+    Pinned quals;                 // their qualities, laid out like `bases`: filled for FASTQ only
+    bool has_quals = false;
     std::vector<uint64_t> offsets; // n + 1
     std::string defs;             // re-emitted definition lines, concatenated
     std::vector<uint32_t> def_end; // end offset of record r's definition in `defs`
@@ -125,6 +127,7 @@ struct Batch {
         def_end.clear();
         total = 0;
         last = false;
+        has_quals = false;
         cover_st.clear();
         report.clear();
     }
@@ -414,6 +417,69 @@ class FastaBatcher {
     bool have_def_ = false, in_record_ = false, cur_open_ = false, done_ = false;
 };
 
+// the same over FASTQ: records of four lines -- '@' + a non-empty name that does not start with whitespace, the sequence, a
+// line that starts with '+', qualities of the sequence's length -- the rules of br_amd/fasta.py read_fastq_sequences (the
+// tests compare the two): line ends stripped, a line the stream no longer has reads as an empty one, an empty sequence is a
+// record, and the first malformed or truncated record ends the stream silently after the records before it
+class FastqBatcher {
+  public:
+    FastqBatcher(int fd, uint32_t max_records) : lr_(fd), max_records_(max_records ? max_records : 16384u) {}
+    int fill(Batch &b)
+    {
+        b.clear();
+        b.has_quals = true;
+        const uint64_t target = batch_bases();
+        while (!done_ && b.n() < max_records_ && b.total < target) {
+            const char *line;
+            size_t len;
+            if (!lr_.next(line, len) || len < 2 || line[0] != '@' || is_ws((unsigned char)line[1])) {
+                done_ = true;
+                break;
+            }
+            size_t seq_len = 0; // the sequence goes behind the batch at once (the line is gone with the next one) and counts
+                                // only when the record is whole
+            if (lr_.next(line, len)) {
+                BRX_TRY(room(b, b.bases, len, target));
+                memcpy(b.bases.p + b.total, line, len);
+                seq_len = len;
+            }
+            if (!lr_.next(line, len) || len < 1 || line[0] != '+') {
+                done_ = true;
+                break;
+            }
+            if (!lr_.next(line, len))
+                len = 0;
+            if (len != seq_len) {
+                done_ = true;
+                break;
+            }
+            BRX_TRY(room(b, b.quals, len, target));
+            memcpy(b.quals.p + b.total, line, len);
+            b.total += len;
+            b.offsets.push_back(b.total);
+            b.def_end.push_back(0u); // (no definition lines are kept: nothing writes these records)
+        }
+        if (lr_.error()) {
+            set_error("read: %s", strerror(lr_.error()));
+            return BRX_ERR_ARG;
+        }
+        b.last = done_;
+        return BRX_OK;
+    }
+
+  private:
+    static int room(Batch &b, Pinned &p, size_t len, uint64_t target)
+    {
+        if (b.total + len + 64 <= p.cap)
+            return BRX_OK;
+        const uint64_t want = target + target / 4 + (1ull << 20);
+        return p.reserve(b.total + len + 64 > want ? b.total + len + 64 : want, b.total);
+    }
+    LineReader lr_;
+    uint32_t max_records_;
+    bool done_ = false;
+};
+
 int write_all(int fd, const char *p, size_t n)
 {
     while (n) {
@@ -547,6 +613,10 @@ struct DevBufs {
     brx::DevBuf<uint32_t> d_piece_read;
     brx::DevBuf<uint8_t> d_in, d_out;
     brx::DevBuf<uint64_t> d_off, d_out_off;
+    // counting through the trusted stretches: the batch's qualities, per-read statistics, their sums over the stream
+    brx::DevBuf<uint8_t> d_quals;
+    brx::DevBuf<brx_trust_stats_t> d_trust_st;
+    brx::DevBuf<unsigned long long> d_trust_tot;
     // the FASTA text of the batch (format_kernel): definitions, their ends, record starts, the text
     brx::DevBuf<uint8_t> d_defs, d_text;
     brx::DevBuf<uint32_t> d_def_end;
@@ -722,10 +792,13 @@ int correct_one_batch(brx_chain_t *chain, const CorrectTuning &tuning, DevBufs &
     return BRX_OK;
 }
 
-// shared by brx_count_fasta_fd / brx_set_insert_fasta_fd: parse on a thread, hand every batch (already on the
-// device) to `consume(d_bases, d_offsets, n_reads, total_bases, stream)`
-template <class F>
-int stream_fasta_batches(int device, int in_fd, uint32_t max_batch_records, hipStream_t s, uint64_t *stats8, F consume)
+// shared by the counting and inserting entries: parse on a thread (FastaBatcher or FastqBatcher), hand every batch
+// (already on the device) to `consume(d_bases, d_offsets, n_reads, total_bases, stream)`.  opts != nullptr: the batch is cut
+// into its trusted stretches of at least k bases first (brx_trust.hip) and `consume` gets the pieces; without opts it gets
+// the batch as it is and nothing else is launched.  trust_totals8: see include/brx.h
+template <class Batcher, class F>
+int stream_read_batches(int device, int in_fd, uint32_t max_batch_records, hipStream_t s, const brx_trust_opts_t *opts, int k,
+                        uint64_t *stats8, uint64_t *trust_totals8, F consume)
 {
     const double t_start = now_s();
     std::vector<Batch> slots(3);
@@ -733,6 +806,7 @@ int stream_fasta_batches(int device, int in_fd, uint32_t max_batch_records, hipS
     Shared sh;
     double t_read = 0, t_gpu = 0;
     uint64_t n_records = 0, bases_in = 0, n_batches = 0;
+    uint64_t plain_tot[3] = {0, 0, 0}; // without opts: records of at least k bases, their bases, their k-mers
     for (auto &sl : slots)
         q_free.push(&sl);
     std::thread reader([&] {
@@ -742,7 +816,7 @@ int stream_fasta_batches(int device, int in_fd, uint32_t max_batch_records, hipS
             q_ready.close();
             return;
         }
-        FastaBatcher fb(in_fd, max_batch_records);
+        Batcher fb(in_fd, max_batch_records);
         for (;;) {
             Batch *b = nullptr;
             if (!q_free.pop(b) || sh.failed())
@@ -762,6 +836,39 @@ int stream_fasta_batches(int device, int in_fd, uint32_t max_batch_records, hipS
         q_ready.close();
     });
     DevBufs dv;
+    brx_trust_opts_t o{};
+    if (opts) {
+        o = *opts;
+        o.min_len = (uint32_t)k;
+    }
+    // the stretches of one batch, then `consume` on them
+    auto trusted = [&](Batch *b) -> int {
+        const uint32_t n = b->n();
+        const bool floor = b->has_quals && o.min_quality; // (qualities that no floor asks about stay on the host)
+        const uint64_t piece_cap = (uint64_t)n + b->total / ((uint64_t)k + 1ull); // the bounds of include/brx.h: no retry
+        if (piece_cap >= 0xffffffffull) {
+            set_error("trusted stretches: batch too large");
+            return BRX_ERR_ARG;
+        }
+        if (floor) {
+            BRX_TRY(dv.d_quals.reserve(b->total + 64, b->total / 8 + 4032, "qualities"));
+            if (b->total)
+                BRX_HIP(hipMemcpyAsync(dv.d_quals, b->quals.p, b->total, hipMemcpyHostToDevice, s));
+        }
+        BRX_TRY(dv.d_split.reserve(b->total + 64, (b->total + 64) / 8 + 64, "trusted batch"));
+        BRX_TRY(dv.d_split_off.reserve(piece_cap + 1, (piece_cap + 1) / 8 + 64, "piece offsets"));
+        BRX_TRY(dv.d_trust_st.reserve(n, n / 8 + 64, "trust statistics"));
+        if (!dv.d_trust_tot) {
+            BRX_TRY(dv.d_trust_tot.reserve(8, 0, "trust totals"));
+            BRX_HIP(hipMemsetAsync(dv.d_trust_tot, 0, 64, s));
+        }
+        uint32_t np = 0;
+        uint64_t bytes = 0;
+        BRX_TRY(brx_trust_split_batch_device(dv.d_in, floor ? dv.d_quals.get() : nullptr, dv.d_off, n, b->total, &o, dv.d_split, b->total,
+                                             dv.d_split_off, nullptr, nullptr, (uint32_t)piece_cap, dv.d_trust_st, &np, &bytes, device, s));
+        BRX_TRY(trust_totals_add(dv.d_trust_st, n, dv.d_trust_tot, s));
+        return np ? consume(dv.d_split, dv.d_split_off, np, bytes, s) : BRX_OK;
+    };
     Batch *b = nullptr;
     while (q_ready.pop(b)) {
         if (!sh.failed() && b->n()) {
@@ -773,11 +880,11 @@ int stream_fasta_batches(int device, int in_fd, uint32_t max_batch_records, hipS
             if (st == BRX_OK && e == hipSuccess)
                 e = hipMemcpyAsync(dv.d_off, b->offsets.data(), ((size_t)b->n() + 1) * 8, hipMemcpyHostToDevice, s);
             if (st == BRX_OK && e == hipSuccess)
-                st = consume(dv.d_in, dv.d_off, b->n(), b->total, s);
+                st = opts ? trusted(b) : consume(dv.d_in, dv.d_off, b->n(), b->total, s);
             if (st == BRX_OK && e == hipSuccess)
                 e = hipStreamSynchronize(s); // the batch's device buffers are reused by the next one
             if (e != hipSuccess) {
-                set_error("fasta stream: %s", hipGetErrorString(e));
+                set_error("read stream: %s", hipGetErrorString(e));
                 st = BRX_ERR_HIP;
             }
             t_gpu += now_s() - t0;
@@ -786,6 +893,15 @@ int stream_fasta_batches(int device, int in_fd, uint32_t max_batch_records, hipS
             n_records += b->n();
             bases_in += b->total;
             n_batches++;
+            if (!opts && trust_totals8)
+                for (uint32_t r = 0; r < b->n(); r++) {
+                    const uint64_t len = b->offsets[r + 1] - b->offsets[r];
+                    if (len >= (uint64_t)k) {
+                        plain_tot[0]++;
+                        plain_tot[1] += len;
+                        plain_tot[2] += len - (uint64_t)k + 1u;
+                    }
+                }
         }
         q_free.push(b);
     }
@@ -801,9 +917,42 @@ int stream_fasta_batches(int device, int in_fd, uint32_t max_batch_records, hipS
         stats8[5] = (uint64_t)(t_gpu * 1e9);
         stats8[7] = (uint64_t)((now_s() - t_start) * 1e9);
     }
+    if (trust_totals8) {
+        for (int i = 0; i < 8; i++)
+            trust_totals8[i] = 0;
+        if (!opts) {
+            trust_totals8[0] = bases_in;
+            trust_totals8[3] = plain_tot[0];
+            trust_totals8[4] = plain_tot[1];
+            trust_totals8[5] = plain_tot[2];
+        } else if (dv.d_trust_tot && sh.status == BRX_OK) {
+            unsigned long long t5[5] = {0, 0, 0, 0, 0};
+            if (hipMemcpyAsync(t5, dv.d_trust_tot, sizeof t5, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+                set_error("read stream: the trust totals did not come back");
+                sh.fail(BRX_ERR_HIP);
+            }
+            for (int i = 0; i < 5; i++)
+                trust_totals8[i] = t5[i];
+            trust_totals8[5] = t5[4] - t5[3] * (uint64_t)(k - 1); // every piece holds at least k bases
+        }
+    }
     if (sh.status != BRX_OK) {
         set_error("%s", sh.message.c_str());
         return sh.status;
+    }
+    return BRX_OK;
+}
+
+// what the _reads_fd entries refuse before anything is read
+int check_reads_args(const char *me, int format, const brx_trust_opts_t *opts)
+{
+    if (format != BRX_READS_FASTA && format != BRX_READS_FASTQ) {
+        set_error("%s: format %d (0 FASTA, 1 FASTQ)", me, format);
+        return BRX_ERR_ARG;
+    }
+    if (opts && opts->min_quality > 93) {
+        set_error("%s: min_quality=%u (Phred+33 qualities end at 93)", me, (unsigned)opts->min_quality);
+        return BRX_ERR_ARG;
     }
     return BRX_OK;
 }
@@ -1102,35 +1251,53 @@ int brx_run_correction_fd_pass(const brx_set_t *set, const brx_method_t *methods
     return run_correction_impl(set, methods, n_methods, second_pass, in_fd, out_fd, max_batch_records, oo, stats8, cover_totals8);
 }
 
-int brx_set_insert_fasta_fd(brx_set_t *set, int in_fd, uint32_t max_batch_records, uint64_t *stats8)
+int brx_set_insert_reads_fd(brx_set_t *set, int in_fd, int format, uint32_t max_batch_records, const brx_trust_opts_t *opts,
+                            uint64_t *stats8, uint64_t *trust_totals8)
 {
     if (!set) {
         set_error("null set");
         return BRX_ERR_ARG;
     }
+    BRX_TRY(check_reads_args("brx_set_insert_reads_fd", format, opts));
     BRX_TRY(use_device(set->device));
     hipStream_t s = nullptr;
     BRX_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    int st = stream_fasta_batches(set->device, in_fd, max_batch_records, s, stats8,
-                                  [&](const uint8_t *d_b, const uint64_t *d_o, uint32_t n, uint64_t total, hipStream_t st_) {
-                                      return brx_set_insert_batch_device(set, d_b, d_o, n, total, st_);
-                                  });
+    auto consume = [&](const uint8_t *d_b, const uint64_t *d_o, uint32_t n, uint64_t total, hipStream_t st_) {
+        return brx_set_insert_batch_device(set, d_b, d_o, n, total, st_);
+    };
+    const int st = format == BRX_READS_FASTQ
+                       ? stream_read_batches<FastqBatcher>(set->device, in_fd, max_batch_records, s, opts, set->k, stats8, trust_totals8, consume)
+                       : stream_read_batches<FastaBatcher>(set->device, in_fd, max_batch_records, s, opts, set->k, stats8, trust_totals8, consume);
     (void)hipStreamDestroy(s);
     return st;
 }
 
-int brx_count_fasta_fd(brx_counter_t *c, int in_fd, uint32_t max_batch_records, uint64_t *stats8)
+int brx_set_insert_fasta_fd(brx_set_t *set, int in_fd, uint32_t max_batch_records, uint64_t *stats8)
+{
+    return brx_set_insert_reads_fd(set, in_fd, BRX_READS_FASTA, max_batch_records, nullptr, stats8, nullptr);
+}
+
+int brx_count_reads_fd(brx_counter_t *c, int in_fd, int format, uint32_t max_batch_records, const brx_trust_opts_t *opts,
+                       uint64_t *stats8, uint64_t *trust_totals8)
 {
     if (!c) {
         set_error("null counter");
         return BRX_ERR_ARG;
     }
+    BRX_TRY(check_reads_args("brx_count_reads_fd", format, opts));
     BRX_TRY(use_device(c->device));
     BRX_HIP(counter_join(c, c->stream)); // a reset still queued on the caller's stream comes first
-    return stream_fasta_batches(c->device, in_fd, max_batch_records, c->stream, stats8,
-                                [&](const uint8_t *d_b, const uint64_t *d_o, uint32_t n, uint64_t total, hipStream_t st_) {
-                                    return brx_set_count_add_batch_device(c, d_b, d_o, n, total, st_);
-                                });
+    auto consume = [&](const uint8_t *d_b, const uint64_t *d_o, uint32_t n, uint64_t total, hipStream_t st_) {
+        return brx_set_count_add_batch_device(c, d_b, d_o, n, total, st_);
+    };
+    return format == BRX_READS_FASTQ
+               ? stream_read_batches<FastqBatcher>(c->device, in_fd, max_batch_records, c->stream, opts, c->k, stats8, trust_totals8, consume)
+               : stream_read_batches<FastaBatcher>(c->device, in_fd, max_batch_records, c->stream, opts, c->k, stats8, trust_totals8, consume);
+}
+
+int brx_count_fasta_fd(brx_counter_t *c, int in_fd, uint32_t max_batch_records, uint64_t *stats8)
+{
+    return brx_count_reads_fd(c, in_fd, BRX_READS_FASTA, max_batch_records, nullptr, stats8, nullptr);
 }
 
 } // extern "C"

@@ -66,6 +66,92 @@ def combine_keys_device(d_a: Optional[int], na: int, d_b: Optional[int], nb: int
     return int(n.value), (int(s3[0]), int(s3[1]), int(s3[2]))
 
 
+def _trust_opts(min_quality: int, acgt_only: bool, min_len: int = 0) -> "_lib.TrustOpts":
+    """brx_trust_opts_t; min_quality is handed over as it is (0..255) so that the library's own refusal of 94 and more is seen"""
+    _check_u8(min_quality, "min_quality")
+    if not 0 <= int(min_len) < 1 << 32:
+        raise ValueError(f"min_len={min_len} does not fit 32 bits")
+    return _lib.TrustOpts(int(min_quality), 1 if acgt_only else 0, 0, int(min_len))
+
+
+def _read_opts(min_quality, acgt_only):
+    """the opts pointer of the _reads_fd entries: None (every k-mer, every byte a base) when nothing is asked for"""
+    if not min_quality and not acgt_only:
+        return None
+    return C.byref(_trust_opts(min_quality or 0, acgt_only))
+
+
+def _read_format(fmt) -> int:
+    if isinstance(fmt, str):
+        if fmt not in _lib.READ_FORMATS:
+            raise ValueError(f"read format {fmt!r}: one of {sorted(_lib.READ_FORMATS)}")
+        return _lib.READ_FORMATS[fmt]
+    return int(fmt)
+
+
+def _stream_stats(st, tot=None) -> dict:
+    d = {"records": int(st[0]), "bases_in": int(st[1]), "batches": int(st[3]), "ns_parse": int(st[4]), "ns_gpu": int(st[5]),
+         "ns_wall": int(st[7])}
+    if tot is not None:
+        from . import trust
+        d["trust"] = {name: int(tot[i]) for i, name in enumerate(trust.TOTALS)}
+    return d
+
+
+def trust_split_batch(bases: np.ndarray, quals: Optional[np.ndarray], offsets: np.ndarray, min_quality: int = 0,
+                      acgt_only: bool = True, min_len: int = 1, device: int = 0):
+    """(out uint8[], out_offsets uint64[p+1], piece_read uint32[p], piece_start uint64[p], stats trust.STATS_DTYPE[n]): the
+    trusted stretches of at least max(min_len, 1) bases of a bases / offsets batch, cut on the GPU (brx_trust_split_batch;
+    br_amd/trust.py states the definitions).  `quals` (or None) is laid out like `bases`"""
+    from . import trust
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if quals is not None:
+        quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        if quals.size != bases.size:
+            raise ValueError(f"{quals.size} qualities for {bases.size} bases")
+    n_reads = offsets.size - 1
+    opts = _trust_opts(min_quality, acgt_only, min_len)
+    st = np.zeros(n_reads, dtype=trust.STATS_DTYPE)
+    L = _lib.lib()
+    ob, oo = C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint64)()
+    pr, ps, n = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)(), C.c_uint32(0)
+    _lib.check(L.brx_trust_split_batch(bases.ctypes.data, quals.ctypes.data if quals is not None else None, offsets.ctypes.data,
+                                       n_reads, C.byref(opts), C.byref(ob), C.byref(oo), C.byref(pr), C.byref(ps), st.ctypes.data,
+                                       C.byref(n), device))
+    try:
+        p = n.value
+        out_off = np.ctypeslib.as_array(oo, shape=(p + 1,)).copy()
+        total = int(out_off[-1])
+        out = np.ctypeslib.as_array(ob, shape=(max(total, 1),))[:total].copy()
+        piece_read = np.ctypeslib.as_array(pr, shape=(max(p, 1),))[:p].copy()
+        piece_start = np.ctypeslib.as_array(ps, shape=(max(p, 1),))[:p].copy()
+    finally:
+        for q in (ob, oo, pr, ps):
+            L.brx_buf_free(C.cast(q, C.c_void_p))
+    return out, out_off, piece_read, piece_start, st
+
+
+def trust_split_batch_device(d_bases: Optional[int], d_quals: Optional[int], d_offsets: Optional[int], n_reads: int, total_bases: int,
+                             min_quality: int = 0, acgt_only: bool = True, min_len: int = 1, d_out: Optional[int] = None,
+                             out_cap: int = 0, d_out_offsets: Optional[int] = None, d_piece_read: Optional[int] = None,
+                             d_piece_start: Optional[int] = None, piece_cap: int = 0, d_stats: Optional[int] = None, device: int = 0,
+                             stream: Optional[int] = None) -> Tuple[int, int]:
+    """(pieces, bytes) of the split form written to the caller's device buffers (brx_trust_split_batch_device); capacities
+    of 0 with no outputs ask for the sizes.  A BrxError of status BRX_ERR_OVERFLOW carries them as `needed`"""
+    opts = _trust_opts(min_quality, acgt_only, min_len)
+    n, total = C.c_uint32(0), C.c_uint64(0)
+    st = _lib.lib().brx_trust_split_batch_device(d_bases, d_quals, d_offsets, n_reads, total_bases, C.byref(opts), d_out, out_cap,
+                                                 d_out_offsets, d_piece_read, d_piece_start, piece_cap, d_stats, C.byref(n),
+                                                 C.byref(total), device, stream)
+    try:
+        _lib.check(st)
+    except _lib.BrxError as e:
+        e.needed = (int(n.value), int(total.value))
+        raise
+    return int(n.value), int(total.value)
+
+
 class KmerSet:
     """trait KmerSet (src/set.rs:17-21)."""
 
@@ -132,6 +218,21 @@ class Pcon(KmerSet):
         st = (C.c_uint64 * 8)()
         with hostio.input_fd(f) as fd:
             _lib.check(_lib.lib().brx_set_insert_fasta_fd(s._h, fd, 0, st))
+        return s
+
+    @classmethod
+    def from_reads_file(cls, f, fmt, k: int, device: int = 0, min_quality: int = 0, acgt_only: bool = False) -> "Pcon":
+        """presence-only set of a FASTA or FASTQ stream (binary file object; fmt "fasta" / "fastq") through the native host
+        pipeline (brx_set_insert_reads_fd).  As the reference's from_fasta / from_fastq by default: every k-mer, every byte
+        a base; with min_quality > 0 or acgt_only only the k-mers of the trusted stretches (br_amd/trust.py) are inserted.
+        The stream's statistics and trust totals are left in `read_stats`"""
+        from . import hostio
+        s = cls.new(k, device)
+        st, tot = (C.c_uint64 * 8)(), (C.c_uint64 * 8)()
+        opts = _read_opts(min_quality, acgt_only)
+        with hostio.input_fd(f) as fd:
+            _lib.check(_lib.lib().brx_set_insert_reads_fd(s._h, fd, _read_format(fmt), 0, opts, st, tot))
+        s.read_stats = _stream_stats(st, tot)
         return s
 
     @classmethod
@@ -432,6 +533,20 @@ class Counter:
             _lib.check(_lib.lib().brx_count_fasta_fd(self._h, fd, 0, st))
         return {"records": int(st[0]), "bases_in": int(st[1]), "batches": int(st[3]), "ns_parse": int(st[4]),
                 "ns_gpu": int(st[5]), "ns_wall": int(st[7])}
+
+    def count_reads(self, f, fmt="fastq", min_quality: int = 0, acgt_only: bool = True, max_batch_records: int = 0) -> dict:
+        """count the records of a FASTQ or FASTA stream (binary file object) through the native host pipeline
+        (brx_count_reads_fd).  Only the k-mers none of whose bases is untrusted are counted: a base is untrusted when it is
+        not ACGTacgt (acgt_only) or its quality lies below min_quality (Phred+33; FASTQ only) -- br_amd/trust.py.  With
+        min_quality 0 and acgt_only off this is count_fasta's rule: every k-mer, every byte a base.  Returns count_fasta's
+        dict plus "trust": bases, non_acgt, low_quality, pieces, kept_bases, kmers summed over the stream"""
+        from . import hostio
+        st, tot = (C.c_uint64 * 8)(), (C.c_uint64 * 8)()
+        opts = _read_opts(min_quality, acgt_only)
+        fmt_id = _read_format(fmt)
+        with hostio.input_fd(f) as fd:
+            _lib.check(_lib.lib().brx_count_reads_fd(self._h, fd, fmt_id, max_batch_records, opts, st, tot))
+        return _stream_stats(st, tot)
 
     def add_batch_device(self, d_bases: int, d_offsets: int, n_reads: int, total_bases: int,
                          stream: Optional[int] = None) -> None:

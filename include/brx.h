@@ -226,6 +226,55 @@ int brx_set_cover_split_batch(const brx_set_t *set, const uint8_t *bases, const 
                               uint8_t **out_bases, uint64_t **out_offsets, uint32_t **piece_read, uint64_t **piece_start,
                               uint32_t *n_pieces);
 
+/* ---- trusted stretches: the parts of a read worth counting.  No counterpart in the reference -----------------------
+ * The reference counts every k-mer of every record, and nuc2bit gives every byte a 2-bit code: a stretch of N becomes a
+ * homopolymer k-mer counted once per position, a k-mer over a Q2 base counts like one over Q40 bases.  That stays the
+ * default; the entries below switch it off.  br_amd/trust.py states the definitions in numpy.
+ * For a read s of n bytes, an optional quality string q of n bytes (Phred+33, the only encoding), a floor min_quality
+ * (0..93) and acgt_only:
+ *   letter[j]   s[j] is one of ACGTacgt;
+ *   good[j]     min_quality == 0, or q is absent, or q[j] >= 33 + min_quality (a byte below 33 fails any floor above 0);
+ *   trusted[j]  (letter[j] or not acgt_only) and good[j];
+ *   a STRETCH is a maximal run of trusted bases;
+ *   the SPLIT form with min_len is the stretches of at least max(min_len, 1) bases, reads in order, the stretches of a
+ *     read in order of their start, each a piece of its own -- the shape of the coverage split form.  With min_len = k the
+ *     k-mers of the pieces are exactly the k-mers of the read none of whose bases is untrusted; with min_quality == 0 and
+ *     acgt_only == 0 every base is trusted and the split form is the batch itself, empty reads dropped.
+ * The batch is cut by position (tiles of 1024 bases, a wave each); a lane takes 16 aligned bytes of bases and 16 of
+ * qualities per step, nothing is probed, and trusted[] is recomputed by the second pass instead of being stored: 2 bytes
+ * read per base and pass, at most 1 written.  Statistics are integer sums and depend on neither geometry nor timing.
+ * Profile timers "trust" (work list, both passes, scans) and "trust_copy" (keep, layout, copy).                          */
+typedef struct brx_trust_opts {
+    uint8_t min_quality; /* 0..93; 0: no floor                                              */
+    uint8_t acgt_only;   /* non-zero: a byte that is not ACGTacgt is untrusted              */
+    uint16_t reserved;   /* 0                                                               */
+    uint32_t min_len;    /* split form; the _fd entries below set it to k themselves        */
+} brx_trust_opts_t;
+typedef struct brx_trust_stats {
+    uint32_t bases;       /* n                                                  */
+    uint32_t non_acgt;    /* not letter[], whatever acgt_only says              */
+    uint32_t low_quality; /* letter[] and not good[], whatever acgt_only says   */
+    uint32_t pieces;      /* stretches of at least max(min_len, 1) bases        */
+    uint32_t kept_bases;  /* their bases                                        */
+} brx_trust_stats_t;
+/* Split form of a device batch on `device`.  d_quals (may be NULL: no qualities) is laid out like d_bases.  Outputs and
+ * bounds as for brx_set_cover_split_batch_device: *out_total <= total_bases, *n_pieces <= n_reads + total_bases /
+ * (max(min_len, 1) + 1); BRX_ERR_OVERFLOW with the needed values in *n_pieces / *out_total, and nothing written (d_stats
+ * included), if piece_cap or out_cap is too small -- a call with both 0 and NULL outputs asks for the sizes.  d_stats (may be
+ * NULL): n_reads entries.  Follows the stream contract above: the inputs need only be ready in the order of `stream`, the
+ * call returns after its kernels have completed, scratch comes from the pool per call, so any number of host threads may
+ * call it at once.  BRX_ERR_ARG, the cause named: null opts / offsets / bases / n_pieces / out_total, min_quality > 93, a
+ * batch too large for one call.                                                                                           */
+int brx_trust_split_batch_device(const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offsets, uint32_t n_reads,
+                                 uint64_t total_bases, const brx_trust_opts_t *opts, uint8_t *d_out, uint64_t out_cap,
+                                 uint64_t *d_out_offsets, uint32_t *d_piece_read, uint64_t *d_piece_start, uint32_t piece_cap,
+                                 brx_trust_stats_t *d_stats, uint32_t *n_pieces, uint64_t *out_total, int device, void *stream);
+/* same on host buffers (offsets[0] == 0; quals may be NULL; stats may be NULL, else n_reads entries of the caller's); the
+ * four outputs (*n_pieces + 1 offsets) are allocated by the library: release with brx_buf_free                             */
+int brx_trust_split_batch(const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint32_t n_reads,
+                          const brx_trust_opts_t *opts, uint8_t **out_bases, uint64_t **out_offsets, uint32_t **piece_read,
+                          uint64_t **piece_start, brx_trust_stats_t *stats, uint32_t *n_pieces, int device);
+
 /* ---- set build by counting: src/main.rs:72-115 -------------------------------------------
  * Counter::<u8>::new(k) -> count_fasta -> Solid::from_count(k, counts, abundance).
  * k must be odd (Fasta::kmer_size forces it, src/cli.rs:277-279).
@@ -615,6 +664,24 @@ int brx_count_fasta_fd(brx_counter_t *c, int in_fd, uint32_t max_batch_records, 
 /* Pcon::from_fasta / Hash::from_fasta (src/set/pcon.rs:47-112, src/set/hash.rs:40-60): every record of the stream
  * inserted presence-only (`br solid -f fasta`, `br large-kmer -f fasta`)                                          */
 int brx_set_insert_fasta_fd(brx_set_t *set, int in_fd, uint32_t max_batch_records, uint64_t *stats8);
+/* The same two over FASTA or FASTQ, optionally through the trusted stretches ("trusted stretches" above; no counterpart
+ * in the reference, whose FASTQ readers are src/set/pcon.rs:114-181).  FASTQ: records of four lines -- '@' + a non-empty
+ * name that does not start with whitespace, the sequence, a line that starts with '+', qualities of the sequence's length;
+ * trailing \r / \n are stripped, a missing final newline is fine, an empty sequence is a valid record, and the first
+ * malformed or truncated record ends the stream silently after the records before it (br_amd/fasta.py
+ * read_fastq_sequences states the same rules).  A record is never split between batches.
+ * opts == NULL: every k-mer of every record, every byte a base -- with BRX_READS_FASTA that is brx_count_fasta_fd /
+ * brx_set_insert_fasta_fd, same launches, same result.  opts != NULL: every batch is cut into its trusted stretches of at
+ * least k bases on the device (opts->min_len is ignored: the entries set it to k) and the pieces are counted / inserted;
+ * FASTA has no qualities, so only acgt_only can bite there.
+ * trust_totals8 (may be NULL): bases, non_acgt, low_quality, pieces, kept_bases, k-mers counted, 0, 0 -- summed over the
+ * stream; with opts == NULL nothing is classified: non_acgt and low_quality are 0, pieces = the records of at least k bases,
+ * kept_bases = their bases.  BRX_ERR_ARG for a format other than the two and for min_quality > 93, before anything is read. */
+enum { BRX_READS_FASTA = 0, BRX_READS_FASTQ = 1 };
+int brx_count_reads_fd(brx_counter_t *c, int in_fd, int format, uint32_t max_batch_records, const brx_trust_opts_t *opts,
+                       uint64_t *stats8, uint64_t *trust_totals8);
+int brx_set_insert_reads_fd(brx_set_t *set, int in_fd, int format, uint32_t max_batch_records, const brx_trust_opts_t *opts,
+                            uint64_t *stats8, uint64_t *trust_totals8);
 
 /* ---- synthetic reads: deterministic, identical on host and device ----------
  * genome: i.i.d. uniform ACGT of length genome_len (seed); read r: window of read_len
