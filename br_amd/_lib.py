@@ -20,6 +20,7 @@ BRX_ERR_FORMAT = -5
 
 METHOD_IDS = {"one": 0, "two": 1, "graph": 2, "greedy": 3, "gap_size": 4, "gap-size": 4}
 COUNT_AUTO, COUNT_DENSE, COUNT_SORTED, COUNT_TABLE = 0, 1, 2, 3
+COUNTOP_ADD, COUNTOP_MAX, COUNTOP_MIN, COUNTOP_SUB = 0, 1, 2, 3
 
 
 class BrxError(RuntimeError):
@@ -126,6 +127,17 @@ SIGNATURES = {
     "brx_keys_combine_device": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_int, _vp, C.c_uint64, _u64p, _u64p, _vp]),
     "brx_set_combine": (C.c_int, [_vp, _vp, C.c_int, _pp, _u64p]),
     "brx_set_compare": (C.c_int, [_vp, _vp, _u64p]),
+    "brx_counts_combine_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_int, C.c_uint8, _vp, _vp, C.c_uint64,
+                                            _u64p, _u64p, _vp]),
+    "brx_counts_load_fd": (C.c_int, [C.c_int, C.c_int, _pp, _u64p]),
+    "brx_counts_from_counter": (C.c_int, [_vp, C.c_uint8, _pp, _u64p]),
+    "brx_counts_save_fd": (C.c_int, [_vp, C.c_uint8, C.c_int, _u64p]),
+    "brx_counts_info": (C.c_int, [_vp, _u64p]),
+    "brx_counts_device": (C.c_int, [_vp, _pp, _pp, _u64p]),
+    "brx_counts_combine": (C.c_int, [_vp, _vp, C.c_int, C.c_uint8, _pp, _u64p]),
+    "brx_counts_spectrum": (C.c_int, [_vp, _u64p]),
+    "brx_counts_finish": (C.c_int, [_vp, C.c_uint8, _pp, _u64p]),
+    "brx_counts_free": (None, [_vp]),
     "brx_comm_unique_id":(C.c_int, [_vp]),
     "brx_comm_init": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _pp]),
     "brx_comm_init_all": (C.c_int, [C.c_int, C.POINTER(C.c_int), _pp]),

@@ -43,6 +43,17 @@ Not in the reference, like `--device` (include/brx.h "coverage"; a base is cover
                                sniffed, of the same k as the set in use:
                                  python -m br_amd -i reads.fa -o corr.fa --set-or illumina.keys --set-minus mito.keys \
                                      --save-set final.keys -c one fasta -i reads.fa -k 21 -a 3
+    count -i A.keys --counts-add PATH | --counts-minus PATH | --counts-min PATH | --counts-max PATH
+                               combine the count file given with `count -i` with the count file in PATH (gz / bz2 / xz sniffed,
+                               the same k) -- add the counts up to 255, subtract them (a k-mer stays while its count stays
+                               positive), keep the smaller or the larger count (br_amd/countops.py).  Each is repeatable; they
+                               are applied left to right in command-line order.  The files are merged as sorted lists on the
+                               GPU, no counting table is built; -a or a threshold selector then pick the solid k-mers of the
+                               combined list, and --save-counts / --save-min-count (also accepted behind `count`) write it.
+                               A list answers no lookups: --abundance-report is refused.  Shards counted apart, summed, with
+                               a contaminant's counts taken off:
+                                 python -m br_amd -i reads.fa -o corr.fa -c one count -i shard0.keys --counts-add shard1.keys \
+                                     --counts-minus mito.keys -a 3 --save-counts job.keys
     fastq -i R.fq [-i ...] -k K (-a N | first-minimum | ...) [-q MINQ] [--all-bytes]
                                a sub-command like `fasta` that counts FASTQ reads (gz / bz2 / xz sniffed), and only the k-mers
                                none of whose bases is untrusted: a base is untrusted when it is not ACGTacgt or its quality
@@ -71,7 +82,7 @@ from typing import BinaryIO, List, Optional
 from . import _lib, abundance, fasta, keyfile, spectrum, strand, trust
 from .correct import build_methods
 from .driver import run_correction
-from .set import Counter, Pcon
+from .set import Counter, CountList, Pcon
 
 METHOD_NAMES = ["one", "two", "graph", "greedy", "gap-size"]  # clap ValueEnum kebab-case of CorrectionMethod
 
@@ -169,6 +180,64 @@ class SetOpAction(argparse.Action):
         setattr(namespace, self.dest, ops)
 
 
+COUNT_FLAGS = {"--counts-add": "add", "--counts-minus": "sub", "--counts-min": "min", "--counts-max": "max"}
+
+
+class CountOpAction(argparse.Action):
+    """--counts-add / --counts-minus / --counts-min / --counts-max PATH: SetOpAction's twin, one list args.count_ops"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        ops = list(getattr(namespace, self.dest, None) or [])
+        ops.append((COUNT_FLAGS[option_string], option_string, values))
+        setattr(namespace, self.dest, ops)
+
+
+def load_count_list(flag: str, path: str, dev: int) -> CountList:
+    """the count list of `count -i` or of a --counts-* operand: a count file, told by its magic after decompression"""
+    try:
+        with open_input(path) as f:
+            if not keyfile.is_keyfile(f.peek(8)[:8]):
+                raise SystemExit("Error: %s %s: not a key file.  --counts-add / --counts-minus / --counts-min / --counts-max combine "
+                                 "count files (--save-counts writes one); a pcon count table is not a sorted list" % (flag, path))
+            return CountList.from_keyfile(f, dev)
+    except (_lib.BrxError, OSError) as e:
+        raise SystemExit(f"Error: {flag} {path}: {e}")
+
+
+def build_set_from_lists(args, counts_path: Optional[str]) -> Pcon:
+    """the list route of `count`: the count file of -i combined with every --counts-* operand, left to right; the threshold
+    from -a or from the combined list's spectrum; --save-counts writes the combined list; the solid set is its finish"""
+    if args.abundance_report is not None:
+        raise SystemExit("Error: --abundance-report asks a k-mer counter about single k-mers, and --counts-* work on count lists, "
+                         "which answer no lookups: save the combined counts (--save-counts) and run `count -i` on that file")
+    lst = load_count_list("count -i", args.sub_inputs, args.device)
+    for name, flag, path in args.count_ops:
+        other = load_count_list(flag, path, args.device)
+        if other.k != lst.k:
+            raise SystemExit("Error: %s %s: k = %d, the counts in use have k = %d" % (flag, path, other.k, lst.k))
+        try:
+            lst = lst.combine(other, name)
+        except _lib.BrxError as e:
+            raise SystemExit(f"Error: {flag} {path}: {e}")
+    thr = args.abundance
+    if thr is None:
+        if args.abundance_selection is None:
+            raise SystemExit("Error: You must provide an abundance method or an abundance threshold")      # main.rs:109
+        thr = spectrum.get_threshold(lst.spectrum(), args.abundance_selection, getattr(args, "percent", 0.0))
+        if thr is None:
+            raise SystemExit("Error: Can't compute minimal abundance")                  # error.rs ComputeAbundanceThreshold
+    if thr < lst.floor - 1:
+        raise SystemExit("Error: the combined counts hold only the k-mers counted at least %d times, so the set of abundance %d would "
+                         "miss members; the lowest threshold they support is %d" % (lst.floor, thr, lst.floor - 1))
+    if counts_path is not None:
+        try:
+            with open(counts_path, "wb") as f:
+                lst.save(f, 1 if args.save_min_count is None else args.save_min_count)
+        except _lib.BrxError as e:
+            raise SystemExit(f"Error: --save-counts: {e}")
+    return lst.finish(thr)
+
+
 def load_operand(path: str, dev: int) -> Pcon:
     """the set of a --set-* operand: a key file (told by its magic after decompression; the counts of a count file are
     ignored) or else a .solid stream"""
@@ -261,6 +330,14 @@ def parser() -> argparse.ArgumentParser:
     c = sub.add_parser("count", help="With Count")
     c.add_argument("-i", "--inputs", dest="sub_inputs", required=True)
     c.add_argument("-a", "--abundance", type=u8, default=None)
+    for flag, what in (("--counts-add", "add the counts of"), ("--counts-minus", "subtract the counts of"),
+                       ("--counts-min", "keep the smaller of each count and that of"), ("--counts-max", "keep the larger of each count and that of")):
+        c.add_argument(flag, action=CountOpAction, dest="count_ops", default=None, metavar="PATH",
+                       help=what + " the count file in PATH (the same k); -i must be a count file too.  Repeatable, applied in "
+                            "command-line order, merged as sorted lists without a counting table (not in the reference)")
+    # (the two top-level flags are also taken behind `count`, where a command line that combines count files has its paths)
+    c.add_argument("--save-counts", default=argparse.SUPPRESS, metavar="PATH", help="as in front of the sub-command")
+    c.add_argument("--save-min-count", type=u8, default=argparse.SUPPRESS, metavar="N", help="as in front of the sub-command")
     abundance_methods(c)
     f = sub.add_parser("fasta", help="With Fasta")
     f.add_argument("-i", "--inputs", dest="sub_inputs", action="append", required=True)
@@ -440,7 +517,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     second_pass = second_pass_of(args)
     abund_paths = abundance_reports(args)
     counts_path = save_counts_of(args)
-    if abund_paths is None and counts_path is None:
+    if getattr(args, "count_ops", None):
+        kmer_set = build_set_from_lists(args, counts_path)
+    elif abund_paths is None and counts_path is None:
         kmer_set = build_set(args)
     else:
         # the threshold is known, nothing is corrected yet: the reads to be corrected, asked about their k-mers' counts

@@ -347,6 +347,26 @@ int abund_refuse_partitioned(const char *what, int k);
 int trust_totals_add(const brx_trust_stats_t *d_stats, uint32_t n_reads, unsigned long long *d_tot5, hipStream_t s);
 }
 
+// A count list (include/brx.h "count lists"): immutable once handed out, so it needs no lock and no stream of its own.
+struct brx_counts {
+    int k = 0;
+    int device = 0;
+    uint8_t floor = 1;            // every count is at least this; k-mers seen fewer times are unknown
+    uint64_t n = 0;               // entries
+    brx::DevBuf<uint64_t> d_keys; // strictly ascending; both empty when n == 0
+    brx::DevBuf<uint8_t> d_cnts;
+};
+
+namespace brx {
+// The merge of two count lists into arrays sized from pass 1 (brx_setops.hip; timer "count_merge"): d_kout and, with
+// want_counts, d_cout receive exactly *n_out entries (both reset when there are none); *both (may be null) = |A n B|.
+// min_count is 1 .. 256 (256 keeps nothing: count > 255).  An empty B with BRX_COUNTOP_ADD is the compaction `count >=
+// min_count`.  BRX_ERR_ARG for lists that do not ascend strictly or hold a 0 count.  Returns after `s` has been synchronised.
+int counts_merge(const char *me, const uint64_t *d_ka, const uint8_t *d_ca, uint64_t na, const uint64_t *d_kb, const uint8_t *d_cb,
+                 uint64_t nb, int op, uint32_t min_count, bool want_counts, hipStream_t s, DevBuf<uint64_t> &d_kout,
+                 DevBuf<uint8_t> &d_cout, uint64_t *n_out, uint64_t *both);
+}
+
 struct brx_chain {
     const brx_set *set = nullptr;
     int device = 0;

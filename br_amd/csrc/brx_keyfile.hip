@@ -19,7 +19,8 @@
 //            the first key (saturating, so that nothing wraps) and checks key < 2^(2k-1) and count >= max(1, floor);
 //            order_check_kernel compares every block's first key with the key before it.
 //   load     pairs into a counting table through table_merge_kernel (tab_merge_pairs, brx_counttable.hip), keys into a
-//            set as the key list a finish leaves.
+//            set as the key list a finish leaves; or the pairs as they are into a count list (brx_counts_load_fd; its
+//            from_counter is the `list` step above, its save the `pack` step; the merge of two lists is brx_setops.hip's).
 // The file passes through two page-locked pieces of BRX_KEYFILE_SLICE_KB KiB (default 8192), one being filled or drained
 // by the fd while the other is copied.
 #include "brx_internal.hpp"
@@ -1095,9 +1096,9 @@ int table_counter_only(const char *me, brx_counter *c)
 // The count view of a partitioned counter (the caller holds its lock and has seen part_lookup_ready) compacted into two
 // arrays out of `ws`: the keys counted at least `floor` times, rising, and their count bytes; *n_out of them (none: the
 // arrays stay null).  The view is only read.  Returns after `s` has been synchronised.
-int list_view(const brx_counter *c, uint8_t floor, hipStream_t s, DevScratch &ws, uint64_t **d_keys, uint8_t **d_cnts, uint64_t *n_out)
+int list_view(const char *me, const brx_counter *c, uint8_t floor, hipStream_t s, DevScratch &ws, uint64_t **d_keys, uint8_t **d_cnts,
+              uint64_t *n_out)
 {
-    const char *me = "brx_counter_save_fd";
     *d_keys = nullptr;
     *d_cnts = nullptr;
     *n_out = 0;
@@ -1156,6 +1157,61 @@ int list_view(const brx_counter *c, uint8_t floor, hipStream_t s, DevScratch &ws
     BRX_HIP(hipStreamSynchronize(s));
     *n_out = total;
     return BRX_OK;
+}
+
+// The listing half of a save, for brx_counter_save_fd and brx_counts_from_counter (the caller holds the counter's lock and
+// has made its device current): the k-mers counted at least *floor = max(min_count, 1, the counter's floor) times, rising,
+// with their count bytes, in two arrays out of `ws` (none: the arrays stay null).  A partitioned counter compacts its count
+// view and is never floored, a table counter is listed and sorted; the refusals are the save's.  The counter is only read.
+// Joins the counter's stream `s`; returns after `s` has been synchronised.
+int counter_list(const char *me, brx_counter *c, uint8_t min_count, hipStream_t s, DevScratch &ws, uint64_t **d_keys, uint8_t **d_cnts,
+                 uint64_t *n_out, uint8_t *floor)
+{
+    *d_keys = nullptr;
+    *d_cnts = nullptr;
+    *n_out = 0;
+    if (min_count < 1)
+        min_count = 1;
+    if (c->strategy == BRX_COUNT_SORTED) {
+        // the count view is the file's content in the file's order: compacted, packed, written; never floored
+        if (!part_lookup_ready(c)) {
+            set_error("%s: a partitioned counter saves its count view: build it first (brx_counter_lookup_prepare; every call that "
+                      "counts, finishes or resets drops it), or count with the table count strategy (BRX_COUNT_TABLE)", me);
+            return BRX_ERR_UNSUPPORTED;
+        }
+        BRX_HIP(counter_join(c, s));
+        *floor = min_count;
+        return list_view(me, c, min_count, s, ws, d_keys, d_cnts, n_out);
+    }
+    BRX_TRY(table_counter_only(me, c));
+    BRX_HIP(counter_join(c, s));
+    const uint8_t have = tab_floor(c);
+    *floor = have > min_count ? have : min_count;
+    uint64_t info[4];
+    BRX_TRY(tab_info(c, info, s));
+    const uint64_t *lines = nullptr;
+    const uint32_t *counts = nullptr;
+    uint32_t log_lines = 0, m = 0;
+    tab_view(c, &lines, &counts, &log_lines, &m);
+    const uint64_t cap = lines ? info[2] : 0;
+    if (!cap)
+        return BRX_OK;
+    u64 *d_n = nullptr;
+    BRX_TRY(ws.get(d_keys, cap));
+    BRX_TRY(ws.get(d_cnts, cap));
+    BRX_TRY(ws.get(&d_n, 1));
+    BRX_HIP(hipMemsetAsync(d_n, 0, 8, s));
+    const uint64_t n_slots = 8ull << log_lines;
+    BRX_TRY(table_list(lines, counts, n_slots, *floor, *d_keys, *d_cnts, cap, d_n, s));
+    u64 got = 0;
+    BRX_HIP(hipMemcpyAsync(&got, d_n, 8, hipMemcpyDeviceToHost, s));
+    BRX_HIP(hipStreamSynchronize(s));
+    if (got > cap) {
+        set_error("%s: %llu entries listed from a table of %llu k-mers", me, got, (u64)cap);
+        return BRX_ERR_HIP;
+    }
+    *n_out = got;
+    return sort_pairs(*d_keys, *d_cnts, got, (uint32_t)(2 * c->k - 1), s);
 }
 
 } // namespace
@@ -1232,71 +1288,17 @@ int brx_counter_save_fd(brx_counter_t *c, uint8_t min_count, int out_fd, uint64_
     auto t0 = Clock::now();
     BRX_TRY(use_device(c->device));
     std::lock_guard<std::mutex> g(c->mu);
-    if (c->strategy == BRX_COUNT_SORTED) {
-        // the count view is the file's content in the file's order: compacted, packed, written; never floored
-        if (!part_lookup_ready(c)) {
-            set_error("%s: a partitioned counter saves its count view: build it first (brx_counter_lookup_prepare; every call that "
-                      "counts, finishes or resets drops it), or count with the table count strategy (BRX_COUNT_TABLE)", me);
-            return BRX_ERR_UNSUPPORTED;
-        }
-        hipStream_t s = c->stream;
-        BRX_HIP(counter_join(c, c->stream));
-        const uint8_t floor = min_count < 1 ? 1 : min_count;
-        DevScratch ws;
-        uint64_t *d_keys = nullptr;
-        uint8_t *d_cnts = nullptr;
-        uint64_t n = 0;
-        auto t1 = Clock::now();
-        BRX_TRY(list_view(c, floor, s, ws, &d_keys, &d_cnts, &n));
-        st8[4] = ns_since(t1);
-        uint8_t one = 0; // (as below: an empty count file still carries the flag)
-        const int st = pack_and_write(c->k, d_keys, n ? d_cnts : &one, n, floor, out_fd, s, st8);
-        st8[0] = n;
-        st8[7] = ns_since(t0);
-        if (stats8)
-            memcpy(stats8, st8, sizeof st8);
-        return st;
-    }
-    BRX_TRY(table_counter_only(me, c));
     hipStream_t s = c->stream;
-    BRX_HIP(counter_join(c, c->stream));
-    const uint8_t have = tab_floor(c);
-    if (min_count < 1)
-        min_count = 1;
-    const uint8_t floor = have > min_count ? have : min_count;
-    uint64_t info[4];
-    BRX_TRY(tab_info(c, info, s));
-    const uint64_t *lines = nullptr;
-    const uint32_t *counts = nullptr;
-    uint32_t log_lines = 0, m = 0;
-    tab_view(c, &lines, &counts, &log_lines, &m);
-    const uint64_t cap = lines ? info[2] : 0;
     DevScratch ws;
     uint64_t *d_keys = nullptr;
     uint8_t *d_cnts = nullptr;
-    u64 *d_n = nullptr;
     uint64_t n = 0;
+    uint8_t floor = 1;
     auto t1 = Clock::now();
-    if (cap) {
-        BRX_TRY(ws.get(&d_keys, cap));
-        BRX_TRY(ws.get(&d_cnts, cap));
-        BRX_TRY(ws.get(&d_n, 1));
-        BRX_HIP(hipMemsetAsync(d_n, 0, 8, s));
-        const uint64_t n_slots = 8ull << log_lines;
-        BRX_TRY(table_list(lines, counts, n_slots, floor, d_keys, d_cnts, cap, d_n, s));
-        u64 got = 0;
-        BRX_HIP(hipMemcpyAsync(&got, d_n, 8, hipMemcpyDeviceToHost, s));
-        BRX_HIP(hipStreamSynchronize(s));
-        if (got > cap) {
-            set_error("%s: %llu entries listed from a table of %llu k-mers", me, got, (u64)cap);
-            return BRX_ERR_HIP;
-        }
-        n = got;
-        BRX_TRY(sort_pairs(d_keys, d_cnts, n, (uint32_t)(2 * c->k - 1), s));
-    }
+    BRX_TRY(counter_list(me, c, min_count, s, ws, &d_keys, &d_cnts, &n, &floor));
     st8[4] = ns_since(t1);
     uint8_t one = 0; // (an empty count file still carries the flag: the counts pointer only has to be non-null)
-    int st = pack_and_write(c->k, d_keys, n ? d_cnts : &one, n, floor, out_fd, s, st8);
+    const int st = pack_and_write(c->k, d_keys, n ? d_cnts : &one, n, floor, out_fd, s, st8);
     st8[0] = n;
     st8[7] = ns_since(t0);
     if (stats8)
@@ -1442,6 +1444,134 @@ int brx_set_load_fd(int in_fd, int device, brx_set_t **out, uint64_t *stats8)
     if (stats8)
         memcpy(stats8, st8, sizeof st8);
     return BRX_OK;
+}
+
+// ---- count lists (include/brx.h "count lists"): the entries that read and write files; the merge is brx_setops.hip's --------
+int brx_counts_load_fd(int in_fd, int device, brx_counts_t **out, uint64_t *stats8)
+{
+    const char *me = "brx_counts_load_fd";
+    if (!out || in_fd < 0) {
+        set_error("%s: null out or bad descriptor", me);
+        return BRX_ERR_ARG;
+    }
+    *out = nullptr;
+    uint64_t st8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto t0 = Clock::now();
+    BRX_TRY(use_device(device));
+    KeyHeader h;
+    BRX_TRY(read_header(in_fd, &h));
+    if (!h.with_counts) {
+        set_error("%s: a set file (keys without counts) cannot be loaded as a count list", me);
+        return BRX_ERR_FORMAT;
+    }
+    hipStream_t s = nullptr;
+    BRX_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    brx_counts *l = new brx_counts;
+    l->k = h.k;
+    l->device = device;
+    l->floor = h.floor;
+    l->n = h.n;
+    const int st = read_blocks(in_fd, h, true, s, l->d_keys, l->d_cnts, st8);
+    (void)hipStreamSynchronize(s);
+    (void)hipStreamDestroy(s);
+    if (st != BRX_OK) {
+        delete l;
+        return st;
+    }
+    *out = l;
+    st8[0] = h.n;
+    st8[7] = ns_since(t0);
+    if (stats8)
+        memcpy(stats8, st8, sizeof st8);
+    return BRX_OK;
+}
+
+int brx_counts_from_counter(brx_counter_t *c, uint8_t min_count, brx_counts_t **out, uint64_t *stats8)
+{
+    const char *me = "brx_counts_from_counter";
+    if (!c || !out) {
+        set_error("%s: null counter or out", me);
+        return BRX_ERR_ARG;
+    }
+    *out = nullptr;
+    uint64_t st8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto t0 = Clock::now();
+    BRX_TRY(use_device(c->device));
+    std::lock_guard<std::mutex> g(c->mu);
+    hipStream_t s = c->stream;
+    DevScratch ws;
+    uint64_t *d_keys = nullptr;
+    uint8_t *d_cnts = nullptr;
+    uint64_t n = 0;
+    uint8_t floor = 1;
+    BRX_TRY(counter_list(me, c, min_count, s, ws, &d_keys, &d_cnts, &n, &floor));
+    st8[4] = ns_since(t0);
+    // the list owns arrays of its own size (a table counter's listing is sized for every k-mer it holds)
+    brx_counts *l = new brx_counts;
+    l->k = c->k;
+    l->device = c->device;
+    l->floor = floor;
+    l->n = n;
+    auto copy = [&]() -> int {
+        if (!n)
+            return BRX_OK;
+        BRX_TRY(l->d_keys.reserve(n, 0, "keys of a count list"));
+        BRX_TRY(l->d_cnts.reserve(n, 0, "counts of a count list"));
+        BRX_HIP(hipMemcpyAsync(l->d_keys, d_keys, n * 8, hipMemcpyDeviceToDevice, s));
+        BRX_HIP(hipMemcpyAsync(l->d_cnts, d_cnts, n, hipMemcpyDeviceToDevice, s));
+        BRX_HIP(hipStreamSynchronize(s)); // the listing goes back to the pool below
+        return BRX_OK;
+    };
+    const int st = copy();
+    if (st != BRX_OK) {
+        (void)hipStreamSynchronize(s);
+        delete l;
+        return st;
+    }
+    *out = l;
+    st8[0] = n;
+    st8[7] = ns_since(t0);
+    if (stats8)
+        memcpy(stats8, st8, sizeof st8);
+    return BRX_OK;
+}
+
+int brx_counts_save_fd(const brx_counts_t *l, uint8_t min_count, int out_fd, uint64_t *stats8)
+{
+    const char *me = "brx_counts_save_fd";
+    if (!l || out_fd < 0) {
+        set_error("%s: null count list or bad descriptor", me);
+        return BRX_ERR_ARG;
+    }
+    uint64_t st8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto t0 = Clock::now();
+    BRX_TRY(use_device(l->device));
+    hipStream_t s = nullptr;
+    BRX_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    const uint64_t *d_keys = l->d_keys;
+    const uint8_t *d_cnts = l->d_cnts;
+    uint64_t n = l->n;
+    uint8_t floor = l->floor;
+    DevBuf<uint64_t> d_kept;
+    DevBuf<uint8_t> d_kept_cnts;
+    int st = BRX_OK;
+    if (min_count > floor) { // one compaction: the merge with an empty B
+        floor = min_count;
+        st = counts_merge(me, l->d_keys, l->d_cnts, l->n, nullptr, nullptr, 0, BRX_COUNTOP_ADD, floor, true, s, d_kept, d_kept_cnts, &n, nullptr);
+        d_keys = d_kept;
+        d_cnts = d_kept_cnts;
+        st8[4] = ns_since(t0);
+    }
+    uint8_t one = 0; // (an empty count file still carries the flag: the counts pointer only has to be non-null)
+    if (st == BRX_OK)
+        st = pack_and_write(l->k, d_keys, n ? d_cnts : &one, n, floor, out_fd, s, st8);
+    (void)hipStreamSynchronize(s);
+    (void)hipStreamDestroy(s);
+    st8[0] = n;
+    st8[7] = ns_since(t0);
+    if (stats8)
+        memcpy(stats8, st8, sizeof st8);
+    return st;
 }
 
 } // extern "C"

@@ -18,6 +18,16 @@
 //   pass 2   merge_write_kernel: the same merge, the kept keys compacted in LDS by a block scan of the threads' counts,
 //            then stored as one contiguous run per tile, 256 neighbouring keys per step.
 // The three launches share the profile timer "set_merge".  Blocks loop over tiles; the grid cap is read_grid()'s.
+//
+// Count lists (include/brx.h "count lists", br_amd/countops.py): add / max / min / sub of two sorted (key, count byte) lists,
+// the same split, tiles and serial merge with the count pieces in LDS beside the keys.
+//   pair     with ties A-first an equal pair is (key of A, key of B): it is decided where A's key is taken -- in_b and cb come
+//            off index 1 + j of B's pieces, possibly the halo BEHIND them -- and B's key of the pair yields nothing.
+//   keep     result >= min_count: a function of the counts, so pass 1 (count_merge_count_kernel) loads them too, and no size
+//            follows from |A|, |B|, |A n B|.  Pass 1 also refuses a 0 count.  Pass 2 (count_merge_write_kernel) compacts keys
+//            and counts in LDS, writes one run of each per tile and sums what it wrote: that must be the scanned total.
+//   LDS      pass 2: 2 x 2050 keys, 2048 staged keys, 2 x 2050 + 2048 count bytes: 55 KB static.
+// Timer "count_merge" for split, both passes and the scan; count_hist_kernel (a list's spectrum) under "count_hist".
 #include "brx_internal.hpp"
 
 #include <chrono>
@@ -224,6 +234,209 @@ __global__ __launch_bounds__(256) void merge_write_kernel(const u64 *__restrict_
     }
 }
 
+// ---- count lists: the same merge with a count byte per key -------------------------------------------------------------------
+constexpr uint32_t ERR_ZERO = 2u; // a 0 count in an input
+
+// min(255, ca + cb), max, min, ca - cb (0 where cb >= ca); a count of 0 stands for "absent"
+__device__ __forceinline__ uint32_t count_op(uint32_t op, uint32_t ca, uint32_t cb)
+{
+    if (op == (uint32_t)BRX_COUNTOP_ADD)
+        return ca + cb < 255u ? ca + cb : 255u;
+    if (op == (uint32_t)BRX_COUNTOP_MAX)
+        return ca > cb ? ca : cb;
+    if (op == (uint32_t)BRX_COUNTOP_MIN)
+        return ca < cb ? ca : cb;
+    return ca > cb ? ca - cb : 0u;
+}
+
+// The count pieces beside tile_load's key pieces, indexed alike: entry 1 + x = count x of the piece.  Of the halo only the
+// count BEHIND B's piece is ever read (an equal pair is decided where A's key is taken); it is loaded with the rest.
+__device__ __forceinline__ void tile_load_counts(const Tile &tl, const uint8_t *__restrict__ ca, uint64_t na, const uint8_t *__restrict__ cb,
+                                                 uint64_t nb, uint8_t *sca, uint8_t *scb)
+{
+    if (tl.ok) {
+        for (uint32_t x = threadIdx.x; x < tl.la + 2u; x += 256u) {
+            const uint64_t i = tl.a0 + x; // global index + 1
+            if (i >= 1 && i <= na)
+                sca[x] = ca[i - 1];
+        }
+        for (uint32_t x = threadIdx.x; x < tl.lb + 2u; x += 256u) {
+            const uint64_t j = tl.b0 + x;
+            if (j >= 1 && j <= nb)
+                scb[x] = cb[j - 1];
+        }
+    }
+    __syncthreads();
+}
+
+// Thread's MERGE_PER_THREAD positions of the tile: key[q], byte q of *cnt the result count, keep bit q of the result
+// (result >= min_count, min_count >= 1); *both = keys of A found in B.  The B key of an equal pair yields nothing.
+__device__ __forceinline__ uint32_t tile_merge_counts(const Tile &tl, uint64_t na, uint64_t nb, const u64 *sa, const u64 *sb, const uint8_t *sca,
+                                                      const uint8_t *scb, uint32_t op, uint32_t min_count, u64 key[MERGE_PER_THREAD], u64 *cnt,
+                                                      uint32_t *both)
+{
+    const uint32_t len = tl.la + tl.lb;
+    const uint32_t d = threadIdx.x * MERGE_PER_THREAD < len ? threadIdx.x * MERGE_PER_THREAD : len;
+    uint32_t i = merge_split<uint32_t>(sa + 1, tl.la, sb + 1, tl.lb, d), j = d - i;
+    uint32_t keep = 0, nboth = 0;
+    u64 cnts = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < MERGE_PER_THREAD; q++) {
+        key[q] = 0;
+        if (d + q >= len)
+            continue;
+        // (i + j = d + q < la + lb: at least one piece has a key left)
+        const bool take_a = i < tl.la && (j >= tl.lb || sa[1 + i] <= sb[1 + j]);
+        uint32_t r = 0;
+        if (take_a) {
+            const u64 x = sa[1 + i];
+            const bool in_b = tl.b0 + j < nb && sb[1 + j] == x; // (j == lb: the halo behind the piece, its count beside it)
+            key[q] = x;
+            r = count_op(op, sca[1 + i], in_b ? (uint32_t)scb[1 + j] : 0u);
+            nboth += in_b ? 1u : 0u;
+            i++;
+        } else {
+            const u64 x = sb[1 + j];
+            const bool in_a = tl.a0 + i > 0 && sa[i] == x; // (i == 0: the halo before the piece)
+            key[q] = x;
+            r = in_a ? 0u : count_op(op, 0u, scb[1 + j]); // (the pair was decided at A's key)
+            j++;
+        }
+        keep |= (r >= min_count ? 1u : 0u) << q;
+        cnts |= (u64)r << (8u * q);
+    }
+    *cnt = cnts;
+    *both = nboth;
+    return keep;
+}
+
+// pass 1.  ctl[0] += |A n B| of the tile, ctl[1] |= ERR_ORDER / ERR_ZERO
+__global__ __launch_bounds__(256) void count_merge_count_kernel(const u64 *__restrict__ a, const uint8_t *__restrict__ ca, uint64_t na,
+                                                                const u64 *__restrict__ b, const uint8_t *__restrict__ cb, uint64_t nb,
+                                                                const u64 *__restrict__ split, uint64_t n_tiles, uint32_t op, uint32_t min_count,
+                                                                u64 *__restrict__ counts, u64 *__restrict__ ctl)
+{
+    __shared__ u64 sa[MERGE_TILE + 2], sb[MERGE_TILE + 2];
+    __shared__ uint8_t sca[MERGE_TILE + 2], scb[MERGE_TILE + 2];
+    __shared__ uint32_t sh[4];
+    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) { // block-uniform
+        const Tile tl = tile_load(a, na, b, nb, split, t, sa, sb);
+        tile_load_counts(tl, ca, na, cb, nb, sca, scb);
+        uint32_t bad = tl.ok ? 0u : ERR_ORDER;
+        for (uint32_t x = threadIdx.x; x < tl.la; x += 256u) {
+            if (tl.a0 + x > 0 && sa[x] >= sa[1 + x]) // (x == 0: against the halo)
+                bad |= ERR_ORDER;
+            if (!sca[1 + x])
+                bad |= ERR_ZERO;
+        }
+        for (uint32_t x = threadIdx.x; x < tl.lb; x += 256u) {
+            if (tl.b0 + x > 0 && sb[x] >= sb[1 + x])
+                bad |= ERR_ORDER;
+            if (!scb[1 + x])
+                bad |= ERR_ZERO;
+        }
+        u64 key[MERGE_PER_THREAD], cnt = 0;
+        uint32_t both = 0;
+        const uint32_t keep = tile_merge_counts(tl, na, nb, sa, sb, sca, scb, op, min_count, key, &cnt, &both);
+        const uint32_t kept = block_sum((uint32_t)__popc(keep), sh);
+        const uint32_t n_both = block_sum(both, sh);
+        const uint32_t n_order = block_sum(bad & ERR_ORDER, sh);
+        const uint32_t n_zero = block_sum(bad & ERR_ZERO, sh);
+        if (threadIdx.x == 0) {
+            counts[t] = kept;
+            if (n_both)
+                atomicAdd(&ctl[0], (u64)n_both);
+            if (n_order || n_zero)
+                atomicOr(&ctl[1], (u64)((n_order ? ERR_ORDER : 0u) | (n_zero ? ERR_ZERO : 0u)));
+        }
+        __syncthreads(); // (the pieces are written again in the next trip)
+    }
+}
+
+// pass 2.  offs: the scanned counts; cout may be null (keys only); *written += what the tile stored.  Runs only after pass 1
+// has found both lists in order and free of 0 counts.
+__global__ __launch_bounds__(256) void count_merge_write_kernel(const u64 *__restrict__ a, const uint8_t *__restrict__ ca, uint64_t na,
+                                                                const u64 *__restrict__ b, const uint8_t *__restrict__ cb, uint64_t nb,
+                                                                const u64 *__restrict__ split, uint64_t n_tiles, uint32_t op, uint32_t min_count,
+                                                                const u64 *__restrict__ offs, u64 *__restrict__ kout, uint8_t *__restrict__ cout,
+                                                                uint64_t n_out, u64 *__restrict__ written)
+{
+    __shared__ u64 sa[MERGE_TILE + 2], sb[MERGE_TILE + 2], so[MERGE_TILE];
+    __shared__ uint8_t sca[MERGE_TILE + 2], scb[MERGE_TILE + 2], sco[MERGE_TILE];
+    __shared__ uint32_t sh[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) { // block-uniform
+        const Tile tl = tile_load(a, na, b, nb, split, t, sa, sb);
+        tile_load_counts(tl, ca, na, cb, nb, sca, scb);
+        u64 key[MERGE_PER_THREAD], cnt = 0;
+        uint32_t both = 0;
+        const uint32_t keep = tile_merge_counts(tl, na, nb, sa, sb, sca, scb, op, min_count, key, &cnt, &both);
+        // the thread's place among the kept entries of the tile: a wave scan, then the waves before
+        const uint32_t mine = (uint32_t)__popc(keep);
+        uint32_t inc = mine;
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(inc, o);
+            if (lane >= (uint32_t)o)
+                inc += y;
+        }
+        if (lane == 63u)
+            sh[wave] = inc;
+        __syncthreads();
+        uint32_t at = inc - mine;
+        for (uint32_t w = 0; w < wave; w++)
+            at += sh[w];
+        const uint32_t total = sh[0] + sh[1] + sh[2] + sh[3]; // <= MERGE_TILE: a bit per position
+#pragma unroll
+        for (uint32_t q = 0; q < MERGE_PER_THREAD; q++)
+            if ((keep >> q) & 1u) {
+                so[at] = key[q];
+                sco[at] = (uint8_t)(cnt >> (8u * q));
+                at++;
+            }
+        __syncthreads();
+        const uint64_t base = offs[t];
+        const uint32_t fits = base >= n_out ? 0u : n_out - base < total ? (uint32_t)(n_out - base) : total; // (total: the counts were taken over the same entries)
+        for (uint32_t x = threadIdx.x; x < fits; x += 256u)
+            kout[base + x] = so[x];
+        if (cout)
+            for (uint32_t x = threadIdx.x; x < fits; x += 256u)
+                cout[base + x] = sco[x];
+        if (threadIdx.x == 0 && fits)
+            atomicAdd(written, (u64)fits);
+        __syncthreads(); // (the pieces, so, sco and sh are written again in the next trip)
+    }
+}
+
+// The spectrum of a list: hist[v] += count bytes equal to v.  Bins per wave in LDS, flushed once per block.
+__global__ __launch_bounds__(256) void count_hist_kernel(const uint8_t *__restrict__ cnts, uint64_t n, u64 *__restrict__ hist)
+{
+    __shared__ u64 bins[4][256];
+    const uint32_t wave = threadIdx.x >> 6;
+    for (uint32_t w = 0; w < 4u; w++)
+        bins[w][threadIdx.x] = 0ull;
+    __syncthreads();
+    // the bytes before the first 16-byte border one by one, then 16 per load, then the rest
+    const uint64_t head = ((16u - (uint32_t)((uintptr_t)cnts & 15u)) & 15u) < n ? ((16u - (uint32_t)((uintptr_t)cnts & 15u)) & 15u) : n;
+    const uint64_t n_vec = (n - head) / 16u, tail = head + n_vec * 16u;
+    const uint64_t gtid = (uint64_t)blockIdx.x * 256u + threadIdx.x, stride = (uint64_t)gridDim.x * 256u;
+    if (gtid < head)
+        atomicAdd(&bins[wave][cnts[gtid]], 1ull);
+    if (gtid < n - tail)
+        atomicAdd(&bins[wave][cnts[tail + gtid]], 1ull);
+    const uint4 *vec = reinterpret_cast<const uint4 *>(cnts + head);
+    for (uint64_t i = gtid; i < n_vec; i += stride) {
+        const uint4 v = vec[i];
+        const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t q = 0; q < 16u; q++)
+            atomicAdd(&bins[wave][(w4[q >> 2] >> (8u * (q & 3u))) & 255u], 1ull);
+    }
+    __syncthreads();
+    const u64 sum = bins[0][threadIdx.x] + bins[1][threadIdx.x] + bins[2][threadIdx.x] + bins[3][threadIdx.x];
+    if (sum)
+        atomicAdd(&hist[threadIdx.x], sum);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------
 // Pass 1 and the scan of one combine; the scratch lives until the plan goes.
 struct MergePlan {
@@ -329,6 +542,158 @@ bool overlap(const void *p, uint64_t pn, const void *q, uint64_t qn)
     return p && q && pn && qn && p0 < q0 + qn * 8 && q0 < p0 + pn * 8;
 }
 
+bool overlap_bytes(const void *p, uint64_t pbytes, const void *q, uint64_t qbytes)
+{
+    const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
+    return p && q && pbytes && qbytes && p0 < q0 + qbytes && q0 < p0 + pbytes;
+}
+
+// ---- count lists ------------------------------------------------------------------------------------------------------------
+const char *const COUNTOP_NAMES = "BRX_COUNTOP_ADD 0, MAX 1, MIN 2, SUB 3";
+
+// Pass 1 and the scan of one count merge; the scratch lives until the plan goes.
+struct CountPlan {
+    DevScratch ws;
+    const u64 *d_ka = nullptr, *d_kb = nullptr;
+    const uint8_t *d_ca = nullptr, *d_cb = nullptr;
+    uint64_t na = 0, nb = 0, n_tiles = 0, total = 0, both = 0;
+    uint32_t op = 0, min_count = 1;
+    u64 *d_split = nullptr, *d_counts = nullptr, *d_ctl = nullptr; // ctl: [0] |A n B|, [1] error bits, [2] entries pass 2 wrote
+};
+
+// *plan: the size of the result and |A n B|; BRX_ERR_ARG when a list does not ascend strictly or holds a 0 count.  min_count
+// 1 .. 256.  Returns after `s` has been synchronised.
+int count_merge_count(const char *me, const uint64_t *d_ka, const uint8_t *d_ca, uint64_t na, const uint64_t *d_kb, const uint8_t *d_cb,
+                      uint64_t nb, int op, uint32_t min_count, hipStream_t s, CountPlan *plan)
+{
+    if (op < 0 || op > 3) {
+        set_error("%s: op=%d (%s)", me, op, COUNTOP_NAMES);
+        return BRX_ERR_ARG;
+    }
+    if (((!d_ka || !d_ca) && na) || ((!d_kb || !d_cb) && nb) || na > (1ull << 62) || nb > (1ull << 62)) {
+        set_error("%s: null keys or counts, or more than 2^62 entries", me);
+        return BRX_ERR_ARG;
+    }
+    if (min_count < 1u || min_count > 256u) {
+        set_error("%s: min_count=%u (1 to 256)", me, min_count);
+        return BRX_ERR_ARG;
+    }
+    plan->d_ka = (const u64 *)d_ka;
+    plan->d_ca = d_ca;
+    plan->d_kb = (const u64 *)d_kb;
+    plan->d_cb = d_cb;
+    plan->na = na;
+    plan->nb = nb;
+    plan->op = (uint32_t)op;
+    plan->min_count = min_count;
+    const uint64_t n_tiles = (na + nb + MERGE_TILE - 1) / MERGE_TILE;
+    plan->n_tiles = n_tiles;
+    if (!n_tiles)
+        return BRX_OK;
+    const uint64_t n_sums = keys_scan_sums(n_tiles);
+    u64 *d_sums = nullptr;
+    BRX_TRY(plan->ws.get(&plan->d_split, n_tiles + 1));
+    BRX_TRY(plan->ws.get(&plan->d_counts, n_tiles));
+    BRX_TRY(plan->ws.get(&d_sums, n_sums + 1));
+    BRX_TRY(plan->ws.get(&plan->d_ctl, 3));
+    BRX_HIP(hipMemsetAsync(plan->d_ctl, 0, 24, s));
+    u64 ctl[2] = {0, 0}, total = 0;
+    int st = BRX_OK;
+    hipError_t e = hipSuccess;
+    {
+        KernelTimer kt("count_merge", s);
+        merge_split_kernel<<<read_grid((n_tiles + 256) / 256, 256u * 16u), 256, 0, s>>>(plan->d_ka, na, plan->d_kb, nb, n_tiles, plan->d_split);
+        count_merge_count_kernel<<<read_grid(n_tiles, 256u * 16u), 256, 0, s>>>(plan->d_ka, d_ca, na, plan->d_kb, d_cb, nb, plan->d_split, n_tiles,
+                                                                               plan->op, min_count, plan->d_counts, plan->d_ctl);
+        if ((e = hipGetLastError()) == hipSuccess)
+            st = keys_scan_exclusive(plan->d_counts, n_tiles, d_sums, s);
+    }
+    if (st == BRX_OK && e == hipSuccess && (e = hipMemcpyAsync(ctl, plan->d_ctl, 16, hipMemcpyDeviceToHost, s)) == hipSuccess)
+        e = hipMemcpyAsync(&total, d_sums + n_sums, 8, hipMemcpyDeviceToHost, s);
+    const hipError_t e2 = hipStreamSynchronize(s); // the scratch may go back to the pool when the caller drops the plan
+    if (st != BRX_OK)
+        return st;
+    if (e != hipSuccess || e2 != hipSuccess) {
+        set_error("%s: count merge, pass 1: %s", me, hipGetErrorString(e != hipSuccess ? e : e2));
+        return BRX_ERR_HIP;
+    }
+    if (ctl[1] & ERR_ORDER) {
+        set_error("%s: the keys of an input do not ascend strictly (unordered or repeated keys)", me);
+        return BRX_ERR_ARG;
+    }
+    if (ctl[1] & ERR_ZERO) {
+        set_error("%s: a count of 0 in an input (a listed k-mer was seen at least once)", me);
+        return BRX_ERR_ARG;
+    }
+    // (what is kept depends on the counts: no size follows from |A|, |B| and |A n B| but the bounds)
+    if (ctl[0] > na || ctl[0] > nb || total > na + nb - ctl[0]) {
+        set_error("%s: count merge, pass 1: %llu entries kept, |A|=%llu |B|=%llu |A n B|=%llu", me, total, (u64)na, (u64)nb, ctl[0]);
+        return BRX_ERR_HIP;
+    }
+    plan->total = total;
+    plan->both = ctl[0];
+    return BRX_OK;
+}
+
+// pass 2 into d_kout and d_cout (may be null), plan->total entries each; returns after `s` has been synchronised
+int count_merge_write(const char *me, const CountPlan &plan, uint64_t *d_kout, uint8_t *d_cout, hipStream_t s)
+{
+    if (!plan.total)
+        return BRX_OK;
+    u64 written = 0;
+    hipError_t e1 = hipSuccess;
+    {
+        KernelTimer kt("count_merge", s);
+        count_merge_write_kernel<<<read_grid(plan.n_tiles, 256u * 16u), 256, 0, s>>>(plan.d_ka, plan.d_ca, plan.na, plan.d_kb, plan.d_cb, plan.nb,
+                                                                                    plan.d_split, plan.n_tiles, plan.op, plan.min_count,
+                                                                                    plan.d_counts, (u64 *)d_kout, d_cout, plan.total,
+                                                                                    plan.d_ctl + 2);
+        e1 = hipGetLastError();
+    }
+    if (e1 == hipSuccess)
+        e1 = hipMemcpyAsync(&written, plan.d_ctl + 2, 8, hipMemcpyDeviceToHost, s);
+    const hipError_t e2 = hipStreamSynchronize(s);
+    if (e1 != hipSuccess || e2 != hipSuccess) {
+        set_error("%s: count merge, pass 2: %s", me, hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+        return BRX_ERR_HIP;
+    }
+    if (written != plan.total) {
+        set_error("%s: count merge, pass 2 wrote %llu entries, the scan found %llu", me, written, (u64)plan.total);
+        return BRX_ERR_HIP;
+    }
+    return BRX_OK;
+}
+
+// The floor of `a op b` before min_count (include/brx.h "count lists", countops.result_floor): 0 = refused, message set
+uint32_t result_floor(const char *me, int op, uint32_t fa, uint32_t fb)
+{
+    if (op == BRX_COUNTOP_MAX || op == BRX_COUNTOP_MIN)
+        return fa > fb ? fa : fb;
+    if (op == BRX_COUNTOP_SUB) {
+        if (fb != 1u) {
+            set_error("%s: subtracting a list that kept only counts from %u up: the k-mers it no longer knows would be subtracted as 0", me,
+                      fb);
+            return 0u;
+        }
+        return fa;
+    }
+    if (fa != 1u || fb != 1u) {
+        set_error("%s: adding lists that kept only counts from %u and from %u up: two unknown parts could add up to a count that must be "
+                  "present (both floors must be 1)", me, fa, fb);
+        return 0u;
+    }
+    return 1u;
+}
+
+int list_ok(const char *me, const brx_counts *l)
+{
+    if (!l) {
+        set_error("%s: null count list", me);
+        return BRX_ERR_ARG;
+    }
+    return BRX_OK;
+}
+
 int operands_ok(const char *me, const brx_set *a, const brx_set *b)
 {
     if (!a || !b) {
@@ -388,7 +753,242 @@ struct OwnStream {
 
 } // namespace
 
+namespace brx {
+
+int counts_merge(const char *me, const uint64_t *d_ka, const uint8_t *d_ca, uint64_t na, const uint64_t *d_kb, const uint8_t *d_cb,
+                 uint64_t nb, int op, uint32_t min_count, bool want_counts, hipStream_t s, DevBuf<uint64_t> &d_kout,
+                 DevBuf<uint8_t> &d_cout, uint64_t *n_out, uint64_t *both)
+{
+    d_kout.reset();
+    d_cout.reset();
+    *n_out = 0;
+    CountPlan plan;
+    BRX_TRY(count_merge_count(me, d_ka, d_ca, na, d_kb, d_cb, nb, op, min_count, s, &plan));
+    if (both)
+        *both = plan.both;
+    if (!plan.total)
+        return BRX_OK;
+    BRX_TRY(d_kout.reserve(plan.total, 0, "keys of a count list"));
+    if (want_counts)
+        BRX_TRY(d_cout.reserve(plan.total, 0, "counts of a count list"));
+    const int st = count_merge_write(me, plan, d_kout, want_counts ? d_cout.get() : nullptr, s);
+    if (st != BRX_OK) {
+        d_kout.reset();
+        d_cout.reset();
+        return st;
+    }
+    *n_out = plan.total;
+    return BRX_OK;
+}
+
+} // namespace brx
+
 extern "C" {
+
+int brx_counts_combine_device(const uint64_t *d_ka, const uint8_t *d_ca, uint64_t na, const uint64_t *d_kb, const uint8_t *d_cb,
+                              uint64_t nb, int op, uint8_t min_count, uint64_t *d_kout, uint8_t *d_cout, uint64_t cap, uint64_t *n_out,
+                              uint64_t *sizes3, void *stream)
+{
+    const char *me = "brx_counts_combine_device";
+    if (!n_out || (!d_kout && (cap || d_cout))) {
+        set_error("%s: null n_out, or a capacity or a count array without a key array", me);
+        return BRX_ERR_ARG;
+    }
+    *n_out = 0;
+    if (overlap_bytes(d_kout, cap * 8, d_ka, na * 8) || overlap_bytes(d_kout, cap * 8, d_kb, nb * 8) || overlap_bytes(d_cout, cap, d_ca, na) ||
+        overlap_bytes(d_cout, cap, d_cb, nb)) {
+        set_error("%s: an output array overlaps an input", me);
+        return BRX_ERR_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CountPlan plan;
+    BRX_TRY(count_merge_count(me, d_ka, d_ca, na, d_kb, d_cb, nb, op, min_count ? min_count : 1u, s, &plan));
+    *n_out = plan.total;
+    if (sizes3) {
+        sizes3[0] = na;
+        sizes3[1] = nb;
+        sizes3[2] = plan.both;
+    }
+    if (!d_kout && !cap)
+        return BRX_OK; // the sizes only
+    if (cap < plan.total) {
+        set_error("%s: the result holds %llu entries, the output arrays %llu", me, (u64)plan.total, (u64)cap);
+        return BRX_ERR_ARG;
+    }
+    return count_merge_write(me, plan, d_kout, d_cout, s);
+}
+
+int brx_counts_info(const brx_counts_t *l, uint64_t *info4)
+{
+    const char *me = "brx_counts_info";
+    BRX_TRY(list_ok(me, l));
+    if (!info4) {
+        set_error("%s: null info4", me);
+        return BRX_ERR_ARG;
+    }
+    info4[0] = (uint64_t)l->k;
+    info4[1] = l->n;
+    info4[2] = l->floor;
+    info4[3] = (uint64_t)l->device;
+    return BRX_OK;
+}
+
+int brx_counts_device(const brx_counts_t *l, void **d_keys, void **d_counts, uint64_t *n)
+{
+    const char *me = "brx_counts_device";
+    BRX_TRY(list_ok(me, l));
+    if (!d_keys || !d_counts || !n) {
+        set_error("%s: null output", me);
+        return BRX_ERR_ARG;
+    }
+    *d_keys = l->n ? (void *)l->d_keys.get() : nullptr;
+    *d_counts = l->n ? (void *)l->d_cnts.get() : nullptr;
+    *n = l->n;
+    return BRX_OK;
+}
+
+void brx_counts_free(brx_counts_t *l) { delete l; }
+
+int brx_counts_combine(const brx_counts_t *a, const brx_counts_t *b, int op, uint8_t min_count, brx_counts_t **out, uint64_t *stats8)
+{
+    const char *me = "brx_counts_combine";
+    if (!out) {
+        set_error("%s: null out", me);
+        return BRX_ERR_ARG;
+    }
+    *out = nullptr;
+    BRX_TRY(list_ok(me, a));
+    BRX_TRY(list_ok(me, b));
+    if (a->k != b->k || a->device != b->device) {
+        set_error("%s: the operands differ: a has k = %d on device %d, b has k = %d on device %d", me, a->k, a->device, b->k, b->device);
+        return BRX_ERR_ARG;
+    }
+    if (op < 0 || op > 3) {
+        set_error("%s: op=%d (%s)", me, op, COUNTOP_NAMES);
+        return BRX_ERR_ARG;
+    }
+    uint32_t floor = result_floor(me, op, a->floor, b->floor);
+    if (!floor)
+        return BRX_ERR_ARG;
+    if (min_count > floor)
+        floor = min_count;
+    uint64_t st8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto t0 = Clock::now();
+    BRX_TRY(use_device(a->device));
+    OwnStream own;
+    BRX_HIP(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
+    brx_counts *res = new brx_counts;
+    res->k = a->k;
+    res->device = a->device;
+    res->floor = (uint8_t)floor;
+    const int st = counts_merge(me, a->d_keys, a->d_cnts, a->n, b->d_keys, b->d_cnts, b->n, op, floor, true, own.s, res->d_keys, res->d_cnts,
+                                &res->n, &st8[2]);
+    if (st == BRX_OK && res->n > set_nbits(a->k)) {
+        set_error("%s: %llu entries in the result, only %llu k-mers exist at k=%d", me, (u64)res->n, (u64)set_nbits(a->k), a->k);
+        delete res;
+        return BRX_ERR_HIP;
+    }
+    if (st != BRX_OK) {
+        delete res;
+        return st;
+    }
+    st8[0] = a->n;
+    st8[1] = b->n;
+    st8[3] = res->n;
+    st8[5] = st8[7] = ns_since(t0);
+    *out = res;
+    if (stats8)
+        memcpy(stats8, st8, sizeof st8);
+    return BRX_OK;
+}
+
+int brx_counts_spectrum(const brx_counts_t *l, uint64_t *hist256)
+{
+    const char *me = "brx_counts_spectrum";
+    BRX_TRY(list_ok(me, l));
+    if (!hist256) {
+        set_error("%s: null hist256", me);
+        return BRX_ERR_ARG;
+    }
+    memset(hist256, 0, 256 * sizeof(uint64_t));
+    if (l->n) {
+        BRX_TRY(use_device(l->device));
+        OwnStream own;
+        BRX_HIP(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
+        DevScratch ws;
+        u64 *d_hist = nullptr;
+        BRX_TRY(ws.get(&d_hist, 256));
+        BRX_HIP(hipMemsetAsync(d_hist, 0, 256 * 8, own.s));
+        {
+            KernelTimer kt("count_hist", own.s);
+            count_hist_kernel<<<read_grid((l->n + 256ull * 64ull - 1) / (256ull * 64ull), 256u * 16u), 256, 0, own.s>>>(l->d_cnts, l->n, d_hist);
+            BRX_HIP(hipGetLastError());
+        }
+        BRX_HIP(hipMemcpyAsync(hist256, d_hist, 256 * 8, hipMemcpyDeviceToHost, own.s));
+        BRX_HIP(hipStreamSynchronize(own.s));
+    }
+    uint64_t seen = 0;
+    for (int v = 1; v < 256; v++)
+        seen += hist256[v];
+    if (hist256[0] || seen != l->n) {
+        set_error("%s: the histogram holds %llu entries and %llu counts of 0, the list %llu entries", me, (u64)seen, (u64)hist256[0], (u64)l->n);
+        return BRX_ERR_HIP;
+    }
+    hist256[0] = set_nbits(l->k) - l->n;
+    return BRX_OK;
+}
+
+int brx_counts_finish(const brx_counts_t *l, uint8_t abundance, brx_set_t **out, uint64_t *stats8)
+{
+    const char *me = "brx_counts_finish";
+    if (!out) {
+        set_error("%s: null out", me);
+        return BRX_ERR_ARG;
+    }
+    *out = nullptr;
+    BRX_TRY(list_ok(me, l));
+    if ((uint32_t)abundance + 1u < l->floor) {
+        set_error("%s: the list kept only counts from %d up: a threshold below %d would miss members (abundance=%d)", me, (int)l->floor,
+                  (int)l->floor - 1, (int)abundance);
+        return BRX_ERR_ARG;
+    }
+    uint64_t st8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto t0 = Clock::now();
+    BRX_TRY(use_device(l->device));
+    OwnStream own;
+    BRX_HIP(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
+    hipStream_t s = own.s;
+    DevBuf<uint64_t> d_keys;
+    DevBuf<uint8_t> d_none;
+    uint64_t kept = 0;
+    // count > abundance over a sorted list is a compaction: the merge with an empty B, keys only
+    BRX_TRY(counts_merge(me, l->d_keys, l->d_cnts, l->n, nullptr, nullptr, 0, BRX_COUNTOP_ADD, (uint32_t)abundance + 1u, false, s, d_keys, d_none,
+                         &kept, nullptr));
+    st8[0] = l->n;
+    st8[1] = kept;
+    st8[4] = ns_since(t0);
+    auto t1 = Clock::now();
+    brx_set *set = nullptr;
+    int st = set_alloc_unwritten(l->k, l->device, &set);
+    if (st == BRX_OK)
+        st = set_build_from_keys(set, d_keys, kept, s, me);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (st == BRX_OK && e != hipSuccess) {
+        set_error("%s: building the set: %s", me, hipGetErrorString(e));
+        st = BRX_ERR_HIP;
+    }
+    if (st != BRX_OK) {
+        if (set)
+            brx_set_free(set);
+        return st;
+    }
+    st8[6] = ns_since(t1);
+    st8[7] = ns_since(t0);
+    *out = set;
+    if (stats8)
+        memcpy(stats8, st8, sizeof st8);
+    return BRX_OK;
+}
 
 int brx_keys_combine_device(const uint64_t *d_a, uint64_t na, const uint64_t *d_b, uint64_t nb, int op, uint64_t *d_out, uint64_t cap,
                             uint64_t *n_out, uint64_t *sizes3, void *stream)

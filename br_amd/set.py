@@ -66,6 +66,26 @@ def combine_keys_device(d_a: Optional[int], na: int, d_b: Optional[int], nb: int
     return int(n.value), (int(s3[0]), int(s3[1]), int(s3[2]))
 
 
+def combine_counts_device(d_ka: Optional[int], d_ca: Optional[int], na: int, d_kb: Optional[int], d_cb: Optional[int], nb: int, op,
+                          d_kout: Optional[int], d_cout: Optional[int], cap: int, min_count: int = 1,
+                          stream: Optional[int] = None) -> Tuple[int, Tuple[int, int, int]]:
+    """(size of the result, (|A|, |B|, |A n B|)) of two count lists on the device -- strictly ascending u64 keys, a u8 count
+    >= 1 each -- combined by `op` (a name of countops.OPS or a BRX_COUNTOP_* number), results below min_count dropped, into
+    d_kout / d_cout, which hold `cap` entries; d_cout None writes the keys only, d_kout None with cap 0 asks for the sizes
+    only (brx_counts_combine_device).  A BrxError carries `needed` where the library said how many entries there are"""
+    from . import countops
+    _check_u8(min_count, "min_count")
+    n, s3 = C.c_uint64(0), (C.c_uint64 * 3)()
+    st = _lib.lib().brx_counts_combine_device(d_ka, d_ca, na, d_kb, d_cb, nb, countops.op_id(op) if isinstance(op, str) else int(op),
+                                              min_count, d_kout, d_cout, cap, C.byref(n), s3, stream)
+    try:
+        _lib.check(st)
+    except _lib.BrxError as e:
+        e.needed = int(n.value)
+        raise
+    return int(n.value), (int(s3[0]), int(s3[1]), int(s3[2]))
+
+
 def _trust_opts(min_quality: int, acgt_only: bool, min_len: int = 0) -> "_lib.TrustOpts":
     """brx_trust_opts_t; min_quality is handed over as it is (0..255) so that the library's own refusal of 94 and more is seen"""
     _check_u8(min_quality, "min_quality")
@@ -496,6 +516,147 @@ class Pcon(KmerSet):
         fb = C.c_uint64(0)
         _lib.check(_lib.lib().brx_set_get_batch_indexed(self._h, ks.ctypes.data, len(ks), out.ctypes.data, C.byref(fb)))
         return out.astype(bool), fb.value
+
+
+class CountList:
+    """An immutable sorted list of (key, count) on one device: the content of a count file without a counting table
+    (include/brx.h "count lists", br_amd/countops.py).  Lists add, subtract, take the minimum and the maximum by a merge;
+    `spectrum()` and `finish(abundance)` give what a table counter that loaded the same file gives.  A list answers no
+    lookups: get_counts and the abundance calls stay the counters'."""
+
+    def __init__(self, handle: int, device: int):
+        self._h = C.c_void_p(handle)
+        self.device = device
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and self._h.value:
+                _lib.lib().brx_counts_free(self._h)
+                self._h = C.c_void_p(None)
+        except Exception:
+            pass
+
+    @classmethod
+    def from_keyfile(cls, f, device: int = 0) -> "CountList":
+        """the list of a count file (binary file object, any compression already undone; read sequentially, so pipes and
+        gzip objects work): k and floor from the header (brx_counts_load_fd).  A set file is refused"""
+        from . import hostio
+        h = C.c_void_p()
+        st = (C.c_uint64 * 8)()
+        with hostio.input_fd(f) as fd:
+            _lib.check(_lib.lib().brx_counts_load_fd(fd, device, C.byref(h), st))
+        l = cls(h.value, device)
+        l.keyfile_stats = _keyfile_stats(st)
+        return l
+
+    @classmethod
+    def from_counter(cls, counter: "Counter", min_count: int = 1) -> "CountList":
+        """the list `counter.save(f, min_count)` would write: a table counter, or a partitioned one after prepare_lookup();
+        the counter is only read (brx_counts_from_counter)"""
+        _check_u8(min_count, "min_count")
+        h = C.c_void_p()
+        _lib.check(_lib.lib().brx_counts_from_counter(counter._h, min_count, C.byref(h), None))
+        return cls(h.value, counter.device)
+
+    def save(self, f, min_count: int = 1) -> dict:
+        """write the list as a count file to the binary file object `f`, the entries below min_count dropped and the floor
+        raised to it (brx_counts_save_fd); a loaded file is saved byte for byte"""
+        from . import hostio
+        _check_u8(min_count, "min_count")
+        st = (C.c_uint64 * 8)()
+        with hostio.output_fd(f) as fd:
+            _lib.check(_lib.lib().brx_counts_save_fd(self._h, min_count, fd, st))
+        return _keyfile_stats(st)
+
+    def _info(self):
+        v = (C.c_uint64 * 4)()
+        _lib.check(_lib.lib().brx_counts_info(self._h, v))
+        return int(v[0]), int(v[1]), int(v[2])
+
+    @property
+    def k(self) -> int:
+        return self._info()[0]
+
+    @property
+    def n(self) -> int:
+        """entries"""
+        return self._info()[1]
+
+    @property
+    def floor(self) -> int:
+        """the smallest count the list kept (>= 1): k-mers seen fewer times are unknown to it"""
+        return self._info()[2]
+
+    def __len__(self) -> int:
+        return self.n
+
+    def device_arrays(self) -> Tuple[int, int, int]:
+        """(d_keys, d_counts, n): the list's u64 keys and u8 counts on the device (0, 0, 0 for an empty list), to be read
+        only, valid while the list lives"""
+        pk, pc, n = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+        _lib.check(_lib.lib().brx_counts_device(self._h, C.byref(pk), C.byref(pc), C.byref(n)))
+        return pk.value or 0, pc.value or 0, int(n.value)
+
+    def combine(self, other: "CountList", op, min_count: int = 1) -> "CountList":
+        """a new list, `self op other` (op: a name of countops.OPS or a BRX_COUNTOP_* number) with the results below
+        min_count dropped: same k and device; the floors follow countops.result_floor; both operands are only read
+        (brx_counts_combine)"""
+        from . import countops
+        if not isinstance(other, CountList):
+            raise TypeError("count lists combine with count lists")
+        _check_u8(min_count, "min_count")
+        h = C.c_void_p()
+        st = (C.c_uint64 * 8)()
+        _lib.check(_lib.lib().brx_counts_combine(self._h, other._h, countops.op_id(op), min_count, C.byref(h), st))
+        l = CountList(h.value, self.device)
+        l.combine_stats = {"a": int(st[0]), "b": int(st[1]), "both": int(st[2]), "entries": int(st[3]), "ns_merge": int(st[5]),
+                           "ns_wall": int(st[7])}
+        return l
+
+    def add(self, other: "CountList", min_count: int = 1) -> "CountList":
+        return self.combine(other, "add", min_count)
+
+    def maximum(self, other: "CountList", min_count: int = 1) -> "CountList":
+        return self.combine(other, "max", min_count)
+
+    def minimum(self, other: "CountList", min_count: int = 1) -> "CountList":
+        return self.combine(other, "min", min_count)
+
+    def subtract(self, other: "CountList", min_count: int = 1) -> "CountList":
+        return self.combine(other, "sub", min_count)
+
+    def __add__(self, other):
+        return self.combine(other, "add") if isinstance(other, CountList) else NotImplemented
+
+    def __sub__(self, other):
+        return self.combine(other, "sub") if isinstance(other, CountList) else NotImplemented
+
+    def spectrum(self) -> np.ndarray:
+        """uint64[256], Counter.spectrum() of a table counter that loaded the same file: bin 0 the k-mers not listed, the
+        bins below the floor 0 (brx_counts_spectrum)"""
+        h = np.zeros(256, dtype=np.uint64)
+        _lib.check(_lib.lib().brx_counts_spectrum(self._h, h.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return h
+
+    def finish(self, abundance: int) -> "Pcon":
+        """the solid set, count > abundance: the set Pcon.from_keyfile makes of those keys (brx_counts_finish).  A threshold
+        below floor - 1 is refused, as by a floored counter"""
+        _check_u8(abundance, "abundance")
+        h = C.c_void_p()
+        st = (C.c_uint64 * 8)()
+        _lib.check(_lib.lib().brx_counts_finish(self._h, abundance, C.byref(h), st))
+        s = Pcon(h.value, self.device)
+        s.finish_stats = {"entries": int(st[0]), "kept": int(st[1]), "ns_select": int(st[4]), "ns_build": int(st[6]),
+                          "ns_wall": int(st[7])}
+        return s
+
+    def to_numpy(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(keys uint64[n], counts uint8[n]) on the host: a copy by way of the list's file, for tests and small lists"""
+        from . import keyfile
+        f = io.BytesIO()
+        self.save(f)
+        _, keys, counts, _ = keyfile.decode(f.getvalue())
+        return keys, counts
 
 
 class Counter:

@@ -480,6 +480,82 @@ int brx_set_combine(const brx_set_t *a, const brx_set_t *b, int op, brx_set_t **
 /* sizes3 = |A|, |B|, |A n B| of two sets under the same rules: listing, sorting and pass 1 alone, nothing is built          */
 int brx_set_compare(const brx_set_t *a, const brx_set_t *b, uint64_t *sizes3);
 
+/* ---- count lists: add, subtract, min, max and threshold count files without a table.  No counterpart in the reference -------
+ * What set algebra is for sets, for counts.  A COUNT LIST is the content of a count file on one device: n keys (canonical
+ * k-mer >> 1), strictly ascending, and one count byte each, every count >= the list's FLOOR >= 1 (the smallest count that was
+ * kept; k-mers seen fewer times are unknown, as in a count file).  br_amd/countops.py states the operations in numpy.  With
+ * ca, cb the counts of a key in A and in B (0 when absent):
+ *     BRX_COUNTOP_ADD   min(255, ca + cb)   every key of either list
+ *     BRX_COUNTOP_MAX   max(ca, cb)         every key of either list
+ *     BRX_COUNTOP_MIN   min(ca, cb)         the keys of both
+ *     BRX_COUNTOP_SUB   ca - cb             the keys with ca > cb; a key of B alone never appears
+ * and a key whose result lies below min_count (0 means 1) is dropped.  Counts are bytes as they are: 255 means "255 or
+ * more", so a difference from or by a saturated count is a bound, not a value.
+ * The hot path (br_amd/csrc/brx_setops.hip) is set algebra's merge path with a count byte riding along: the same tiles of
+ * 2048 merged positions, the same border search, key pieces in LDS with one key of halo each side, 8 positions per thread;
+ * the count pieces lie beside the keys, B's with one count of halo behind it, because an equal pair is decided where A's key
+ * is taken and B's key of the pair yields nothing.  Whether a key is kept depends on the counts, so pass 1 merges the counts
+ * too; it also checks that both key lists ascend strictly and that no input count is 0.  A scan, then pass 2 compacts keys
+ * and counts in LDS and writes one run of each per tile; what pass 2 wrote must equal the scanned total.  One profile timer,
+ * "count_merge"; the byte histogram of a list runs under "count_hist".                                                       */
+#define BRX_COUNTOP_ADD 0
+#define BRX_COUNTOP_MAX 1
+#define BRX_COUNTOP_MIN 2
+#define BRX_COUNTOP_SUB 3 /* A minus B */
+/* The raw operation, the twin of brx_keys_combine_device with the same stream contract: (d_ka, d_ca)[0 .. na) and (d_kb,
+ * d_cb)[0 .. nb) are read in the order of `stream`, the call returns after `stream` has been synchronised.  Either list may
+ * be empty, A and B may be the same arrays.  d_cout may be NULL (keys only).  sizes3 (may be NULL) receives |A|, |B|, |A n B|.
+ * d_kout == NULL with cap == 0 asks for *n_out and sizes3 only.  A cap smaller than the result is BRX_ERR_ARG with *n_out set
+ * to what is needed; unordered or repeated keys, a 0 count in an input, a bad op and an output that overlaps an input (keys
+ * against keys, counts against counts) are BRX_ERR_ARG with *n_out = 0; the outputs are untouched in all these cases.        */
+int brx_counts_combine_device(const uint64_t *d_ka, const uint8_t *d_ca, uint64_t na, const uint64_t *d_kb, const uint8_t *d_cb,
+                              uint64_t nb, int op, uint8_t min_count /* 0 means 1 */, uint64_t *d_kout,
+                              uint8_t *d_cout /* may be NULL */, uint64_t cap, uint64_t *n_out, uint64_t *sizes3 /* may be NULL */,
+                              void *stream);
+/* The object: an immutable count list on one device.  Every entry below is host-path: it works on a stream of its own and
+ * returns complete; a list may be read by any number of host threads at once.
+ * NOT supported: looking single k-mers up in a list (get_counts and abundance stay the counters'), lists across ranks, lists
+ * of dense or merged counters, and turning a list back into a table counter other than through its file.                    */
+typedef struct brx_counts brx_counts_t;
+/* The list of a count file, any odd k from 5 to 31, floor from the header; the descriptor is read sequentially, never
+ * sought.  Every malformed stream brx_counter_load_fd refuses is refused with the same status and message; a set file (no
+ * counts) is BRX_ERR_FORMAT.  *out stays NULL on failure.  stats8 as for brx_counter_load_fd ([4] is 0: nothing is merged).  */
+int brx_counts_load_fd(int in_fd, int device, brx_counts_t **out, uint64_t *stats8);
+/* The list brx_counter_save_fd would write with this min_count: a table counter is listed and sorted, a partitioned one
+ * hands over its count view (brx_counter_lookup_prepare first); dense and merged counters, and a partitioned counter without
+ * a view, are BRX_ERR_UNSUPPORTED in the save's words.  Floor: max(the counter's floor, min_count, 1).  The counter is only
+ * read; takes its lock and joins its stream as the save does.  stats8: [0] entries, [4] ns listing + sorting, [7] ns wall.    */
+int brx_counts_from_counter(brx_counter_t *c, uint8_t min_count /* 0 means 1 */, brx_counts_t **out, uint64_t *stats8);
+/* The count file of the list, the bytes of keyfile.encode(k, keys, counts, floor): a load followed by a save reproduces the
+ * file.  min_count above the list's floor drops the smaller counts first (one compaction) and becomes the file's floor.
+ * stats8 as for brx_counter_save_fd ([4]: ns of that compaction).                                                            */
+int brx_counts_save_fd(const brx_counts_t *l, uint8_t min_count /* 0 means 1 */, int out_fd, uint64_t *stats8);
+/* info4: [0] k, [1] entries, [2] floor, [3] device                                                                           */
+int brx_counts_info(const brx_counts_t *l, uint64_t *info4);
+/* the list's device arrays (u64 keys, u8 counts; both NULL for an empty list), valid until the list is freed; read only      */
+int brx_counts_device(const brx_counts_t *l, void **d_keys, void **d_counts, uint64_t *n);
+/* A new list, `a op b`.  Same k and device (BRX_ERR_ARG otherwise, the message names both); a == b is allowed; both are only
+ * read.  Floors, with fa, fb the operands' (br_amd/countops.py result_floor states the same):
+ *     MAX, MIN   the result's floor is max(fa, fb), and the result is exact from there up: a value at or above it needs
+ *                the key present with that count in an operand (MAX) or in both (MIN);
+ *     SUB        needs fb == 1 (BRX_ERR_ARG: the k-mers B no longer knows would be subtracted as 0); the floor is fa;
+ *     ADD        needs fa == fb == 1 (BRX_ERR_ARG, as brx_counter_load_fd refuses it: two unknown parts could add up to a
+ *                count that must be present).
+ * Results below max(that floor, min_count) are dropped, and that maximum is the new list's floor.  The output arrays are
+ * sized from pass 1 (9 bytes per entry); the peak is both operands plus the result.
+ * stats8 (may be NULL): [0] |A|, [1] |B|, [2] |A n B|, [3] |result|, [4] 0, [5] ns merging, [6] 0, [7] ns wall.               */
+int brx_counts_combine(const brx_counts_t *a, const brx_counts_t *b, int op, uint8_t min_count /* 0 means 1 */, brx_counts_t **out,
+                       uint64_t *stats8);
+/* hist256[v] = entries with count v for v >= 1 (bins below the floor are 0, as a floored counter reports them), hist256[0] =
+ * 2^(2k-1) - entries: the 256 numbers brx_counter_spectrum gives a table counter that loaded the same file.                   */
+int brx_counts_spectrum(const brx_counts_t *l, uint64_t *hist256);
+/* The solid set: the keys with count > abundance (strict), exactly the set brx_set_load_fd makes from those keys (k >= 21:
+ * sparse with its chained index; k <= 19: bits written, key list kept from k = 15; an empty result is a valid empty set).
+ * abundance < floor - 1 is BRX_ERR_ARG, as for a floored counter.
+ * stats8 (may be NULL): [0] entries, [1] kept, [2] 0, [3] 0, [4] ns selecting, [5] 0, [6] ns building the set, [7] ns wall.   */
+int brx_counts_finish(const brx_counts_t *l, uint8_t abundance, brx_set_t **out, uint64_t *stats8);
+void brx_counts_free(brx_counts_t *l);
+
 /* ---- multi-GPU: reads shard over the GPUs, the set is exchanged ONCE -----------------------------
  * The reference is one process with rayon threads over shared memory (src/main.rs:30-33, src/lib.rs:72-139); on N
  * GPUs every rank counts and later corrects its own block of the reads, and the single exchange step is the k-mer
