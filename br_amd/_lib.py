@@ -111,6 +111,9 @@ SIGNATURES = {
     "brx_counter_add_partitioned_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
     "brx_counter_table_info": (C.c_int, [_vp, _u64p, _vp]),
     "brx_counter_merge_state": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "brx_counter_set_slice": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
+    "brx_counter_slice": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "brx_counter_slice_stats": (C.c_int, [_vp, _u64p, _vp]),
     "brx_counter_free": (None, [_vp]),
     "brx_counter_abundance_batch_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint8, _vp, _vp, _vp, _vp]),
     "brx_counter_abundance_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint8, _vp, _vp, _vp]),

@@ -63,6 +63,13 @@ Not in the reference, like `--device` (include/brx.h "coverage"; a base is cover
                                --save-set and --set-* work as with `fasta`.  One line of totals goes to stderr:
                                  python -m br_amd -i reads.fa -o corr.fa --save-set illumina.keys -c one \
                                      fastq -i illumina.fq.gz -k 21 -q 20 first-minimum
+    fasta | fastq ... --count-parts P
+                               count in P sweeps over the inputs (1 <= P <= 4096), each in a hash table sized for the P-th of
+                               the k-mers it owns (br_amd/parts.py), and join the sweeps' count lists: jobs whose k-mers do not
+                               fit one table.  Any odd k from 5 to 31; the same set, --save-counts file and correction as
+                               without the flag.  A sweep's list keeps the k-mers counted at least --save-min-count times with
+                               --save-counts, otherwise more than A times with -a A -- with -a, only solid k-mers are ever kept
+                               between sweeps -- otherwise all of them.  Lists answer no lookups: --abundance-report is refused
     fasta ... --skip-non-acgt  count only the k-mers of ACGTacgt bases (off by default: the reference counts every byte)
     solid | large-kmer -f fastq|fasta ... [-q MINQ] [--skip-non-acgt]
                                the same two switches for the presence-only sets
@@ -79,7 +86,7 @@ import lzma
 import sys
 from typing import BinaryIO, List, Optional
 
-from . import _lib, abundance, fasta, keyfile, spectrum, strand, trust
+from . import _lib, abundance, fasta, keyfile, parts, spectrum, strand, trust
 from .correct import build_methods
 from .driver import run_correction
 from .set import Counter, CountList, Pcon
@@ -238,6 +245,69 @@ def build_set_from_lists(args, counts_path: Optional[str]) -> Pcon:
     return lst.finish(thr)
 
 
+def count_parts(text: str) -> int:
+    """argparse type for --count-parts: 1 .. 4096 sweeps"""
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"invalid int value: {text!r}")
+    if not 1 <= v <= parts.MAX_PARTS:
+        raise argparse.ArgumentTypeError(f"{v} is not in 1..{parts.MAX_PARTS}")
+    return v
+
+
+COUNT_PARTS_HELP = ("count in P sweeps over the inputs (1 <= P <= 4096), each sweep in a hash table (BRX_COUNT_TABLE) sized for "
+                    "the P-th of the k-mers it owns, and join the sweeps' count lists: for jobs whose k-mers do not fit one table; "
+                    "any odd k from 5 to 31; the same set, counts and correction.  Between sweeps a list keeps the k-mers counted "
+                    "at least --save-min-count times with --save-counts, otherwise more than A times with -a A -- with -a, only "
+                    "solid k-mers are ever kept between sweeps -- otherwise all of them: a selector's threshold is not known "
+                    "until the last sweep (not in the reference)")
+
+
+def build_set_in_parts(args, counts_path: Optional[str]) -> Pcon:
+    """the --count-parts route of `fasta` and `fastq`: parts.count_in_parts, the threshold from -a or from the summed
+    spectrum, --save-counts writes the joined list, the solid set is its finish"""
+    if args.abundance_report is not None:
+        raise SystemExit("Error: --abundance-report asks a k-mer counter about single k-mers, and --count-parts keeps count lists, "
+                         "which answer no lookups: save the joined counts (--save-counts) and run `count -i` on that file")
+    k = fasta_kmer_size(args.kmer_size)
+    if not 5 <= k <= 31:
+        raise SystemExit("Error: --count-parts counts through the hash table, which takes odd k from 5 to 31 (k=%d)" % k)
+    if args.abundance is None and args.abundance_selection is None:
+        raise SystemExit("Error: You must provide an abundance method or an abundance threshold")  # main.rs:109
+    if counts_path is not None:
+        floor = max(1, args.save_min_count or 1)
+    elif args.abundance is not None:
+        floor = min(255, args.abundance + 1)
+    else:
+        floor = 1
+    fastq = args.subcommand == "fastq"
+    try:
+        lst, spec, st = parts.count_in_parts(args.sub_inputs, k, args.count_parts, args.device, floor, "fastq" if fastq else "fasta",
+                                             args.min_quality if fastq else 0, (not args.all_bytes) if fastq else args.skip_non_acgt)
+    except _lib.BrxError as e:
+        raise SystemExit(f"Error: --count-parts: {e}")
+    if fastq:  # (every sweep sees the same reads: the first one's totals)
+        sys.stderr.write("fastq: %(bases)d bases, %(non_acgt)d not ACGT, %(low_quality)d below the quality floor, "
+                         "%(pieces)d trusted stretches of %(kept_bases)d bases, %(kmers)d k-mers counted\n" % st["trust"])
+    thr = args.abundance
+    if thr is None:
+        thr = spectrum.get_threshold(spec, args.abundance_selection, getattr(args, "percent", 0.0))
+        if thr is None:
+            raise SystemExit("Error: Can't compute minimal abundance")                  # error.rs ComputeAbundanceThreshold
+    if thr < lst.floor - 1:
+        raise SystemExit("Error: the counts are saved with --save-min-count %d: k-mers seen fewer times are not kept between the "
+                         "sweeps, so the set of abundance %d would miss members; the lowest threshold they support is %d"
+                         % (lst.floor, thr, lst.floor - 1))
+    if counts_path is not None:
+        try:
+            with open(counts_path, "wb") as f:
+                lst.save(f, floor)
+        except _lib.BrxError as e:
+            raise SystemExit(f"Error: --save-counts: {e}")
+    return lst.finish(thr)
+
+
 def load_operand(path: str, dev: int) -> Pcon:
     """the set of a --set-* operand: a key file (told by its magic after decompression; the counts of a count file are
     ignored) or else a .solid stream"""
@@ -345,6 +415,7 @@ def parser() -> argparse.ArgumentParser:
     f.add_argument("-a", "--abundance", type=u8, default=None)
     f.add_argument("--skip-non-acgt", action="store_true",
                    help="count only the k-mers of ACGTacgt bases (not in the reference, which counts every byte)")
+    f.add_argument("--count-parts", type=count_parts, default=None, metavar="P", help=COUNT_PARTS_HELP)
     abundance_methods(f)
     fq = sub.add_parser("fastq", help="With Fastq: count the trusted stretches of FASTQ reads (not in the reference)")
     fq.add_argument("-i", "--inputs", dest="sub_inputs", action="append", required=True)
@@ -353,6 +424,7 @@ def parser() -> argparse.ArgumentParser:
     fq.add_argument("-q", "--min-quality", type=min_quality, default=0, metavar="MINQ",
                     help="skip the k-mers over a base of Phred quality below MINQ (Phred+33; default 0: no floor)")
     fq.add_argument("--all-bytes", action="store_true", help="count every byte as a base, as `fasta` does (default: ACGTacgt only)")
+    fq.add_argument("--count-parts", type=count_parts, default=None, metavar="P", help=COUNT_PARTS_HELP)
     abundance_methods(fq)
     s = sub.add_parser("solid", help="With Solid")
     s.add_argument("-i", "--input", dest="sub_input", required=True)
@@ -519,6 +591,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     counts_path = save_counts_of(args)
     if getattr(args, "count_ops", None):
         kmer_set = build_set_from_lists(args, counts_path)
+    elif getattr(args, "count_parts", None) is not None:
+        kmer_set = build_set_in_parts(args, counts_path)
     elif abund_paths is None and counts_path is None:
         kmer_set = build_set(args)
     else:

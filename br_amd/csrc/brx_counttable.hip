@@ -15,6 +15,9 @@
 //            leaves at k = 21: the probe index is built from the list on first use.  A set with a bit vector (k <= 19)
 //            gets its bits written in the same pass.
 //   spectrum table_spectrum_kernel: bins 1..255 from the counters.
+//   slice    brx_counter_set_slice: only the k-mers one part of P owns are counted (flat_count_slice_kernel compacts them in
+//            LDS so that full waves walk), and the table is sized for them (tab_add_batch_slice: flat_slice_census_kernel
+//            counts the batch's k-mers of the part when the bound below does not fit).  Everything else reads the table.
 //
 // The exact number of distinct keys lives on the device (d_nkeys) and is read back -- one synchronisation of the stream
 // -- only when the bound "keys known + bases counted since" no longer fits under the load limit, and by finish.
@@ -40,6 +43,11 @@ struct TabState {
     // after brx_counter_load_fd of a file that kept only counts >= floor: the k-mers seen fewer times are unknown, so
     // nothing can be added and no set with a threshold below floor - 1 can be finished until the counter is reset
     uint8_t floor = 1;
+    // brx_counter_set_slice: the counter counts only the k-mers `part` of `parts` owns (table_owner_of); parts 1: all of them.
+    // d_slice, allocated with the first slice: [0, 4) what brx_counter_slice_stats reports, [4, 6) the sizing pass's answer
+    uint32_t part = 0, parts = 1;
+    DevBuf<unsigned long long> d_slice;
+    uint64_t seen_unwalked = 0;    // valid k-mers of the batches that held none of the part: no count kernel ran for them
 };
 
 } // namespace brx
@@ -308,6 +316,44 @@ int tab_reset(brx_counter *c, hipStream_t s)
     t->keys_known = t->pending = t->bases_total = 0;
     t->merged_world = t->merged_rank = 0;
     t->floor = 1;
+    if (t->d_slice)
+        BRX_HIP(hipMemsetAsync(t->d_slice, 0, 6 * 8, s));
+    t->seen_unwalked = 0; // (the slice itself stays)
+    return BRX_OK;
+}
+
+// A batch into a sliced counter.  While "every base is a new key" fits the table nothing is asked; when it does not, or
+// there is no table, the sizing pass counts the batch's k-mers of the part and the table is sized for the keys known plus
+// that number: a P-th of the loose bound, which is what the slice is for.
+static int tab_add_batch_slice(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
+                               hipStream_t s)
+{
+    TabState *t = c->tab;
+    uint64_t bound = total_bases; // k-mers of the part in this batch, at most
+    if (!t->d_lines || !fits_half(t->log_lines, t->keys_known + t->pending + total_bases)) {
+        BRX_HIP(hipMemsetAsync(t->d_slice + 4, 0, 2 * 8, s));
+        {
+            KernelTimer kt("tab_census", s);
+            BRX_TRY(flat_slice_census(d_bases, d_offsets, n_reads, total_bases, c->k, t->part, t->parts, t->d_slice + 4, s));
+        }
+        unsigned long long got[2] = {0, 0};
+        BRX_HIP(hipMemcpyAsync(got, t->d_slice + 4, 2 * 8, hipMemcpyDeviceToHost, s));
+        BRX_TRY(read_keys(t, s)); // (one synchronisation for both)
+        bound = got[0];
+        if (!bound) { // nothing of the part: no table is made for it, and none is walked
+            t->seen_unwalked += got[1];
+            return BRX_OK;
+        }
+        if (!t->d_lines || !fits_half(t->log_lines, t->keys_known + bound))
+            BRX_TRY(regrow(c, t->keys_known + bound, s));
+    }
+    {
+        KernelTimer kt("tab_count", s);
+        BRX_TRY(flat_table_count_slice(d_bases, d_offsets, n_reads, total_bases, c->k, t->d_lines, t->d_counts, 32u - t->log_lines, t->m,
+                                       t->part, t->parts, t->d_nkeys, t->d_slice, s));
+    }
+    t->pending += bound;
+    t->bases_total += bound;
     return BRX_OK;
 }
 
@@ -326,6 +372,8 @@ int tab_add_batch(brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offs
     }
     if (!n_reads || !total_bases)
         return BRX_OK;
+    if (t->parts > 1u)
+        return tab_add_batch_slice(c, d_bases, d_offsets, n_reads, total_bases, s);
     // every k-mer of the batch could be new
     if (!t->d_lines || !fits_half(t->log_lines, t->keys_known + t->pending + total_bases)) {
         if (t->pending)
@@ -496,6 +544,68 @@ int tab_merge_pairs(brx_counter *c, const uint64_t *d_keys, const uint8_t *d_cnt
     BRX_HIP(hipMemcpyAsync(&sum, d_sum, 8, hipMemcpyDeviceToHost, s));
     BRX_TRY(read_keys(t, s));
     t->bases_total += sum; // (the counts in the table add up to no more: tab_finish_into's bound on the list holds)
+    return BRX_OK;
+}
+
+int tab_set_slice(brx_counter *c, uint32_t part, uint32_t parts)
+{
+    TabState *t = c->tab;
+    if (t->merged_world) {
+        set_error("brx_counter_set_slice: the counter holds the k-mers rank %d of a merge over %d ranks owns; brx_counter_reset it first",
+                  t->merged_rank, t->merged_world);
+        return BRX_ERR_ARG;
+    }
+    if (t->floor > 1) {
+        set_error("brx_counter_set_slice: the counter holds a key file that kept only counts from %d up; brx_counter_reset it first",
+                  (int)t->floor);
+        return BRX_ERR_ARG;
+    }
+    if (t->keys_known || t->pending || t->bases_total) {
+        set_error("brx_counter_set_slice: the counter holds %s%llu k-mers (%llu occurrences at most); a slice is set on an empty counter: "
+                  "brx_counter_reset it first", t->pending ? "at least " : "", (unsigned long long)t->keys_known,
+                  (unsigned long long)t->bases_total);
+        return BRX_ERR_ARG;
+    }
+    if (parts > 1u && !t->d_slice) {
+        BRX_TRY(t->d_slice.reserve(6, 0, "slice statistics"));
+        BRX_HIP(zero_now(t->d_slice, 6 * 8)); // (done on return: the next batch may come on any stream)
+    }
+    if (t->d_lines) {
+        // the zeroing a reset queued (on the caller's stream: its mark; or on the counter's own) ends before the table goes
+        if (c->ev_pending.exchange(false))
+            BRX_HIP(hipEventSynchronize(c->ev));
+        BRX_HIP(hipStreamSynchronize(c->stream));
+        free_table(t);
+    }
+    t->peak_bytes = 0;
+    t->seen_unwalked = 0; // (batches that held nothing of the old part left nothing else behind)
+    t->part = parts > 1u ? part : 0u;
+    t->parts = parts;
+    return BRX_OK;
+}
+
+bool tab_slice(const brx_counter *c, uint32_t *part, uint32_t *parts)
+{
+    const TabState *t = c->tab;
+    if (part)
+        *part = t ? t->part : 0u;
+    if (parts)
+        *parts = t ? t->parts : 1u;
+    return t && t->parts > 1u;
+}
+
+int tab_slice_stats(brx_counter *c, uint64_t *stats4, hipStream_t s)
+{
+    TabState *t = c->tab;
+    stats4[0] = stats4[1] = stats4[2] = stats4[3] = 0;
+    if (t->parts <= 1u || !t->d_slice)
+        return BRX_OK;
+    unsigned long long v[4] = {0, 0, 0, 0};
+    BRX_HIP(hipMemcpyAsync(v, t->d_slice, 4 * 8, hipMemcpyDeviceToHost, s));
+    BRX_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < 4; i++)
+        stats4[i] = v[i];
+    stats4[0] += t->seen_unwalked;
     return BRX_OK;
 }
 

@@ -745,6 +745,11 @@ int table_args(const brx_comm *cm, const brx_counter_t *c, bool want_merged, con
         set_error("%s: the counter does not use the table count strategy (BRX_COUNT_TABLE)", what);
         return BRX_ERR_UNSUPPORTED;
     }
+    uint32_t part = 0, parts = 1;
+    if (tab_slice(c, &part, &parts)) {
+        set_error("%s: the counter counts slice %u of %u of its reads' k-mers; a slice is not a rank's shard", what, part, parts);
+        return BRX_ERR_ARG;
+    }
     int w = 0, r = 0;
     const bool merged = tab_merged(c, &w, &r);
     if (want_merged && (!merged || w != cm->world || r != cm->rank)) {

@@ -164,6 +164,13 @@ int flat_presence_insert(const uint8_t *d_bases, const uint64_t *d_offsets, uint
 // counting into a chained table with a u32 counter per slot (brx_partbuild.hip: flat_count_kernel)
 int flat_table_count(const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases, int k, uint64_t *table,
                      uint32_t *counts, uint32_t line_shift, uint32_t m, unsigned long long *d_new, hipStream_t s);
+// the same for a sliced counter (flat_count_slice_kernel: the k-mers `part` of `parts` owns, compacted in LDS so that
+// only full waves walk), and the sizing pass without the table (d_out2: k-mers of the part, valid k-mers)
+int flat_table_count_slice(const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases, int k, uint64_t *table,
+                           uint32_t *counts, uint32_t line_shift, uint32_t m, uint32_t part, uint32_t parts, unsigned long long *d_new,
+                           unsigned long long *d_stats4, hipStream_t s);
+int flat_slice_census(const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases, int k, uint32_t part,
+                      uint32_t parts, unsigned long long *d_out2, hipStream_t s);
 // sets of this k have no bit vector
 inline bool sparse_k(int k) { return k >= 21; }
 // the set must be probed through its (chained) index: it has no bit vector, or not right now
@@ -301,6 +308,12 @@ int set_list_keys(const brx_set *set, hipStream_t s, DevBuf<uint64_t> &d_out, ui
 int set_build_from_keys(brx_set *set, DevBuf<uint64_t> &d_keys, uint64_t n, hipStream_t s, const char *me);
 void tab_set_merged(brx_counter *c, int world, int rank);
 bool tab_merged(const brx_counter *c, int *world, int *rank);
+// Sliced counting (include/brx.h "sliced counting").  tab_set_slice: the counter must hold nothing (the caller holds its
+// lock); the table it may still have is given back, so every slice sizes its own, and the peak starts again.  tab_slice:
+// true for parts > 1.  tab_slice_stats synchronises `s`.
+int tab_set_slice(brx_counter *c, uint32_t part, uint32_t parts);
+bool tab_slice(const brx_counter *c, uint32_t *part, uint32_t *parts);
+int tab_slice_stats(brx_counter *c, uint64_t *stats4, hipStream_t s);
 int tab_reset(brx_counter *c, hipStream_t s);
 int tab_spectrum(brx_counter *c, hipStream_t s, unsigned long long *d_hist);
 // the rest of what brx_set.hip's counter entries call: the counting table (brx_counttable.hip) ...

@@ -1318,6 +1318,12 @@ int brx_counter_load_fd(brx_counter_t *c, int in_fd, uint64_t *stats8)
     BRX_TRY(use_device(c->device));
     std::lock_guard<std::mutex> g(c->mu);
     BRX_TRY(table_counter_only(me, c));
+    uint32_t part = 0, parts = 1;
+    if (tab_slice(c, &part, &parts)) {
+        set_error("%s: the counter counts slice %u of %u and a file's keys are not filtered; brx_counter_set_slice(c, 0, 1) makes it an "
+                  "ordinary counter", me, part, parts);
+        return BRX_ERR_ARG;
+    }
     hipStream_t s = c->stream;
     BRX_HIP(counter_join(c, c->stream)); // a reset still queued on the caller's stream comes first
     if (tab_floor(c) > 1) {

@@ -645,6 +645,130 @@ __global__ __launch_bounds__(256) void flat_count_kernel(L1Args a, uint64_t *__r
         atomicAdd(n_new, (unsigned long long)added);
 }
 
+// ---- sliced counting (brx_counter_set_slice): only the k-mers with table_owner_of(hash, parts) == part ----------------
+// flat_count_kernel's tiles and rounds of 256 positions.  The walk into the table is a chain of dependent 64-byte probes
+// and costs a wave about the same with one lane active as with 64, so a filter in front of it would make each of the
+// `parts` sweeps as dear as a whole count.  Instead every wave keeps a ring of SLICE_QUEUE forward k-mers in LDS: a round
+// appends the k-mers of the part among its 64 positions (ballot + prefix), and as soon as 64 are queued the wave takes
+// them out and walks them with every lane busy.  At most 63 stay behind a walk and a round adds at most 64: 127 < 128,
+// so a tile in which every k-mer belongs to the part (a homopolymer read) fits like any other.  The ring lives through
+// the tiles of the block's range and only its last, partial content is walked by a partial wave.  A wave's LDS
+// instructions execute in order, so its own appends are visible to its own reads without a barrier; the ring is the
+// wave's alone.  No block barrier beyond the tile's.
+constexpr uint32_t SLICE_QUEUE = 128;
+
+// this lane's position of the round: is its k-mer valid, and the part's (then `kmer` holds it)
+__device__ __forceinline__ bool slice_take(const L1Args &a, const uint32_t *pk, const uint32_t *bnd, uint32_t p, uint32_t n_here,
+                                           uint32_t part, uint32_t parts, uint64_t &kmer, uint32_t &seen)
+{
+    if (p >= n_here || !l1_valid(bnd, p, a.k))
+        return false;
+    seen++;
+    kmer = kmer_at(pk, p, a.k);
+    return table_owner_of(khash(kmer, a.k), parts) == part;
+}
+
+// stats4 (brx_counter_slice_stats): valid k-mers seen, k-mers of the part, wave trips into the walk, waves launched
+__global__ __launch_bounds__(256) void flat_count_slice_kernel(L1Args a, uint64_t *__restrict__ lines, uint32_t *__restrict__ counts,
+                                                               uint32_t line_shift, uint32_t m, uint32_t w, uint32_t part, uint32_t parts,
+                                                               unsigned long long *__restrict__ n_new,
+                                                               unsigned long long *__restrict__ stats4)
+{
+    __shared__ uint32_t pk[PACK_WORDS];
+    __shared__ uint32_t bnd[BND_WORDS];
+    __shared__ uint32_t sh_r0[2];
+    __shared__ uint64_t queue[4][SLICE_QUEUE];
+    uint64_t *q = queue[threadIdx.x >> 6];
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    uint32_t added = 0, seen = 0;
+    uint32_t head = 0, queued = 0, trips = 0; // wave-uniform
+    unsigned long long walked = 0;            // wave-uniform
+    uint32_t lo, hi;
+    l1_range(a.n_items, lo, hi);
+    for (uint32_t item = lo; item < hi; item++) {
+        uint32_t n_here;
+        l1_prepare(a, item, pk, bnd, sh_r0, n_here, item == lo);
+        for (uint32_t p0 = 0; p0 < n_here; p0 += 256) { // (block-uniform: every lane of the wave is in every round)
+            uint64_t kmer = 0;
+            const bool mine = slice_take(a, pk, bnd, p0 + threadIdx.x, n_here, part, parts, kmer, seen);
+            const unsigned long long mask = __ballot(mine);
+            if (mine)
+                q[(head + queued + (uint32_t)__popcll(mask & below)) & (SLICE_QUEUE - 1u)] = kmer;
+            queued += (uint32_t)__popcll(mask);
+            if (queued >= 64u) { // wave-uniform
+                __builtin_amdgcn_wave_barrier();
+                const uint64_t mer = q[(head + lane) & (SLICE_QUEUE - 1u)];
+                __builtin_amdgcn_wave_barrier();
+                head = (head + 64u) & (SLICE_QUEUE - 1u);
+                queued -= 64u;
+                bool fresh;
+                const uint64_t slot = table_find_or_claim(lines, line_shift, m, w, a.k, mer, fresh);
+                added += fresh ? 1u : 0u;
+                table_count_bump(counts + slot);
+                walked += 64ull;
+                trips++;
+            }
+        }
+        __syncthreads();
+    }
+    if (queued) { // what is left at the end of the range: the one walk of a partial wave
+        __builtin_amdgcn_wave_barrier();
+        if (lane < queued) {
+            bool fresh;
+            const uint64_t slot = table_find_or_claim(lines, line_shift, m, w, a.k, q[(head + lane) & (SLICE_QUEUE - 1u)], fresh);
+            added += fresh ? 1u : 0u;
+            table_count_bump(counts + slot);
+        }
+        walked += queued;
+        trips++;
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        added += __shfl_down(added, d);
+        seen += __shfl_down(seen, d);
+    }
+    if (lane == 0u) {
+        if (added)
+            atomicAdd(n_new, (unsigned long long)added);
+        if (seen)
+            atomicAdd(stats4 + 0, (unsigned long long)seen);
+        if (walked)
+            atomicAdd(stats4 + 1, walked);
+        if (trips)
+            atomicAdd(stats4 + 2, (unsigned long long)trips);
+        atomicAdd(stats4 + 3, 1ull);
+    }
+}
+
+// the sizing pass of a sliced counter: the same tiles and the same owner test without the table.  out2[0] grows by the
+// batch's k-mers of the part (occurrences), out2[1] by its valid k-mers
+__global__ __launch_bounds__(256) void flat_slice_census_kernel(L1Args a, uint32_t part, uint32_t parts, unsigned long long *__restrict__ out2)
+{
+    __shared__ uint32_t pk[PACK_WORDS];
+    __shared__ uint32_t bnd[BND_WORDS];
+    __shared__ uint32_t sh_r0[2];
+    uint32_t owned = 0, seen = 0;
+    uint32_t lo, hi;
+    l1_range(a.n_items, lo, hi);
+    for (uint32_t item = lo; item < hi; item++) {
+        uint32_t n_here;
+        l1_prepare(a, item, pk, bnd, sh_r0, n_here, item == lo);
+        for (uint32_t p = threadIdx.x; p < n_here; p += 256) {
+            uint64_t kmer;
+            owned += slice_take(a, pk, bnd, p, n_here, part, parts, kmer, seen) ? 1u : 0u;
+        }
+        __syncthreads();
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        owned += __shfl_down(owned, d);
+        seen += __shfl_down(seen, d);
+    }
+    if ((threadIdx.x & 63) == 0 && seen) {
+        atomicAdd(out2 + 0, (unsigned long long)owned);
+        atomicAdd(out2 + 1, (unsigned long long)seen);
+    }
+}
+
 // shared by the scatter kernels: block scan of cntv -> lofs/lcur (all in LDS), in two halves around one barrier so that
 // a caller with a barrier of its own there can share it
 __device__ __forceinline__ void scan_bins_begin(uint32_t B, const uint32_t *cntv, uint32_t *sh_wsum, uint32_t &mine, uint32_t &incl)
@@ -1898,6 +2022,53 @@ int flat_table_count(const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t
     a.n_items = (uint32_t)n_items64;
     a.k = k;
     flat_count_kernel<<<read_grid(a.n_items, 4096u), 256, 0, s>>>(a, table, counts, line_shift, m, (uint32_t)k - m + 1u, d_new);
+    BRX_HIP(hipGetLastError());
+    return BRX_OK;
+}
+
+// the tiles of a batch for the two sliced passes below
+static int slice_args(const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases, int k, L1Args &a)
+{
+    const uint64_t n_items64 = (total_bases + L1_TILE - 1) / L1_TILE;
+    if (n_items64 >= (1ull << 32)) {
+        set_error("batch of %llu bases is too large for one counting pass; split it", (unsigned long long)total_bases);
+        return BRX_ERR_UNSUPPORTED;
+    }
+    memset(&a, 0, sizeof(a));
+    a.bases = d_bases;
+    a.offsets = d_offsets;
+    a.n_reads = n_reads;
+    a.total = total_bases;
+    a.n_items = (uint32_t)n_items64;
+    a.k = k;
+    return BRX_OK;
+}
+
+// flat_table_count for a sliced counter (see flat_count_slice_kernel): only the k-mers `part` of `parts` owns; d_stats4
+// grows as brx_counter_slice_stats describes
+int flat_table_count_slice(const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases, int k, uint64_t *table,
+                           uint32_t *counts, uint32_t line_shift, uint32_t m, uint32_t part, uint32_t parts, unsigned long long *d_new,
+                           unsigned long long *d_stats4, hipStream_t s)
+{
+    if (!total_bases || !n_reads)
+        return BRX_OK;
+    L1Args a;
+    BRX_TRY(slice_args(d_bases, d_offsets, n_reads, total_bases, k, a));
+    flat_count_slice_kernel<<<read_grid(a.n_items, 4096u), 256, 0, s>>>(a, table, counts, line_shift, m, (uint32_t)k - m + 1u, part, parts,
+                                                                        d_new, d_stats4);
+    BRX_HIP(hipGetLastError());
+    return BRX_OK;
+}
+
+// the sizing pass (see flat_slice_census_kernel): d_out2[0] += the batch's k-mers of the part, d_out2[1] += its valid k-mers
+int flat_slice_census(const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases, int k, uint32_t part,
+                      uint32_t parts, unsigned long long *d_out2, hipStream_t s)
+{
+    if (!total_bases || !n_reads)
+        return BRX_OK;
+    L1Args a;
+    BRX_TRY(slice_args(d_bases, d_offsets, n_reads, total_bases, k, a));
+    flat_slice_census_kernel<<<read_grid(a.n_items, 4096u), 256, 0, s>>>(a, part, parts, d_out2);
     BRX_HIP(hipGetLastError());
     return BRX_OK;
 }

@@ -948,6 +948,54 @@ int brx_counter_merge_state(brx_counter_t *c, int *world, int *rank)
     return BRX_OK;
 }
 
+int brx_counter_set_slice(brx_counter_t *c, uint32_t part, uint32_t parts)
+{
+    if (!c) {
+        set_error("brx_counter_set_slice: null counter");
+        return BRX_ERR_ARG;
+    }
+    if (c->strategy != BRX_COUNT_TABLE) {
+        set_error("brx_counter_set_slice: only a counter of the table count strategy (BRX_COUNT_TABLE) counts in slices; this one is %s",
+                  c->strategy == BRX_COUNT_DENSE ? "dense" : "partitioned");
+        return BRX_ERR_UNSUPPORTED;
+    }
+    if (parts < 1u || parts > 4096u || part >= parts) {
+        set_error("brx_counter_set_slice: part %u of %u (1 <= parts <= 4096, part < parts)", part, parts);
+        return BRX_ERR_ARG;
+    }
+    BRX_TRY(use_device(c->device));
+    std::lock_guard<std::mutex> g(c->mu);
+    return tab_set_slice(c, part, parts);
+}
+
+int brx_counter_slice(brx_counter_t *c, uint32_t *part, uint32_t *parts)
+{
+    if (!c || !part || !parts) {
+        set_error("brx_counter_slice: null argument");
+        return BRX_ERR_ARG;
+    }
+    *part = 0;
+    *parts = 1;
+    if (c->strategy == BRX_COUNT_TABLE) {
+        std::lock_guard<std::mutex> g(c->mu);
+        (void)tab_slice(c, part, parts);
+    }
+    return BRX_OK;
+}
+
+int brx_counter_slice_stats(brx_counter_t *c, uint64_t *stats4, void *stream)
+{
+    if (!c || !stats4) {
+        set_error("brx_counter_slice_stats: null argument");
+        return BRX_ERR_ARG;
+    }
+    stats4[0] = stats4[1] = stats4[2] = stats4[3] = 0;
+    if (c->strategy != BRX_COUNT_TABLE)
+        return BRX_OK;
+    BRX_TRY(use_device(c->device));
+    return tab_slice_stats(c, stats4, (hipStream_t)stream);
+}
+
 int brx_set_extract_keys_device(const brx_set_t *set, uint64_t first_hash, uint64_t n_hashes, uint64_t *d_out, uint64_t cap,
                                 uint64_t *n_out, void *stream)
 {

@@ -829,6 +829,30 @@ class Counter:
     def reset(self, stream: Optional[int] = None) -> None:
         _lib.check(_lib.lib().brx_counter_reset(self._h, stream))
 
+    # ---- sliced counting (include/brx.h "sliced counting", br_amd/parts.py) -------------------------------------------
+    def set_slice(self, part: int, parts: int) -> None:
+        """count only the k-mers `part` of `parts` owns (dist.table_owner of the k-mer's hash) from here on: a table counter
+        that holds nothing, new or reset since (brx_counter_set_slice).  parts 1 .. 4096; parts == 1 makes it an ordinary
+        counter again.  reset() keeps the slice; everything that reads the counter describes the slice"""
+        if not (0 <= int(part) < 2 ** 32 and 0 <= int(parts) < 2 ** 32):
+            raise _lib.BrxError(_lib.BRX_ERR_ARG, f"set_slice: part {part} of {parts}")
+        _lib.check(_lib.lib().brx_counter_set_slice(self._h, int(part), int(parts)))
+
+    @property
+    def slice(self) -> Tuple[int, int]:
+        """(part, parts); (0, 1) for a counter that is not sliced"""
+        p, n = C.c_uint32(0), C.c_uint32(1)
+        _lib.check(_lib.lib().brx_counter_slice(self._h, C.byref(p), C.byref(n)))
+        return int(p.value), int(n.value)
+
+    def slice_stats(self, stream: Optional[int] = None) -> dict:
+        """what the sliced count kernel did since the last reset (all 0 for an unsliced counter): valid k-mers seen, k-mers
+        of the part (walked into the table), wave trips into the walk, waves launched.  The part's k-mers are compacted
+        before the walk, so trips <= walked // 64 + waves"""
+        v = (C.c_uint64 * 4)()
+        _lib.check(_lib.lib().brx_counter_slice_stats(self._h, v, stream))
+        return {"seen": int(v[0]), "walked": int(v[1]), "trips": int(v[2]), "waves": int(v[3])}
+
     # ---- abundance (include/brx.h "abundance", br_amd/abundance.py: no counterpart in the reference) ----
     def abundance_batch(self, bases: np.ndarray, offsets: np.ndarray, abundance: int = 0, profile: bool = True,
                         hist: bool = False):

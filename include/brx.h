@@ -332,6 +332,35 @@ int brx_counter_table_info(brx_counter_t *c, uint64_t *info4, void *stream);
 /* *world, *rank (rank may be NULL) the counter was merged over by brx_exchange_table_merge; *world = 0 for a counter that is
  * not merged (never merged, reset since, or of another strategy)                                                        */
 int brx_counter_merge_state(brx_counter_t *c, int *world, int *rank);
+
+/* ---- sliced counting: a job larger than one counting table, counted part by part (br_amd/parts.py) -----------------
+ * A table counter sliced as (part, parts) counts exactly the k-mers with
+ *     brx_exchange_table_owner(hash, parts) == part,   hash = canonical(kmer) >> 1
+ * and ignores the rest, so `parts` sweeps over the same reads count every k-mer once, each sweep in a table sized for its
+ * share.  The lists of the sweeps (brx_counts_from_counter) have disjoint keys; their BRX_COUNTOP_MAX is the job's list.
+ *   set_slice    parts 1 .. 4096, part < parts (BRX_ERR_ARG otherwise); parts == 1: an ordinary counter again.  Only on a
+ *                table counter that holds nothing -- new, or brx_counter_reset since -- BRX_ERR_ARG otherwise, the message
+ *                naming what it holds; dense and partitioned counters: BRX_ERR_UNSUPPORTED.  The table an emptied counter
+ *                still has is given back (waits for the reset's zeroing), so every slice sizes its own, and the peak of
+ *                brx_counter_table_info starts again.  brx_counter_reset keeps the slice.
+ *   answers      everything that reads the counter describes the slice: spectrum (bins 1..255 the slice's, bin 0 =
+ *                2^(2k-1) - its keys), finish[_into], table_info, brx_counter_save_fd and brx_counts_from_counter (a slice's
+ *                file is a valid count file), get_counts and the abundance entries (0 for the k-mers of other parts).
+ *   refusals     brx_counter_load_fd into a sliced counter (a file's keys are not filtered) and brx_exchange_table_merge /
+ *                _spectrum / _table_finish on one (a slice is not a rank's shard): BRX_ERR_ARG.
+ *   sizing       an unsliced table is sized for "every base of the batch is a new key".  A sliced one, whenever that bound
+ *                does not fit the table it has (or it has none), first counts the batch's k-mers of the part in a pass
+ *                without the table -- one number back, one synchronisation of the stream -- and sizes for the keys known
+ *                plus that number: the smallest 2^L lines with 7 * 2^L >= 3 * need, L >= 12.  A batch that holds nothing of
+ *                the part makes no table.
+ *   slice        *part, *parts; 0, 1 for a counter never sliced or of another strategy.
+ *   slice_stats  cumulative since the last reset, all 0 for an unsliced counter (synchronises `stream`): [0] valid k-mers
+ *                seen, [1] k-mers of the part, i.e. walked into the table, [2] wave trips into the walk, [3] waves launched
+ *                by the sliced count kernel.  The surviving k-mers are compacted before the walk, so only full waves walk
+ *                but for one last trip per wave: stats[2] <= stats[1] / 64 + stats[3].                                   */
+int brx_counter_set_slice(brx_counter_t *c, uint32_t part, uint32_t parts);
+int brx_counter_slice(brx_counter_t *c, uint32_t *part, uint32_t *parts);
+int brx_counter_slice_stats(brx_counter_t *c, uint64_t *stats4, void *stream);
 void brx_counter_free(brx_counter_t *c);
 
 /* ---- abundance: how often the k-mers of a read were counted.  No counterpart in the reference ---------------------
