@@ -141,6 +141,13 @@ SIGNATURES = {
     "brx_counts_spectrum": (C.c_int, [_vp, _u64p]),
     "brx_counts_finish": (C.c_int, [_vp, C.c_uint8, _pp, _u64p]),
     "brx_counts_free": (None, [_vp]),
+    "brx_counts_lookup_prepare": (C.c_int, [_vp, C.c_int]),
+    "brx_counts_lookup_info": (C.c_int, [_vp, _u64p]),
+    "brx_counts_lookup_directory": (C.c_int, [_vp, _pp, _u64p]),
+    "brx_counts_lookup_drop": (C.c_int, [_vp]),
+    "brx_counts_abundance_batch_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint8, _vp, _vp, _vp, _vp]),
+    "brx_counts_abundance_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint8, _vp, _vp, _vp]),
+    "brx_counts_get_counts": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
     "brx_comm_unique_id":(C.c_int, [_vp]),
     "brx_comm_init": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _pp]),
     "brx_comm_init_all": (C.c_int, [C.c_int, C.POINTER(C.c_int), _pp]),
@@ -231,6 +238,19 @@ def check(status: int) -> None:
         L = lib()
         msg = (L.brx_last_error() or b"").decode(errors="replace") or L.brx_strerror(status).decode()
         raise BrxError(status, msg)
+
+
+def copy_to_host(d_ptr: int, out) -> None:
+    """a blocking copy of out.nbytes bytes of device memory into the numpy array `out`, through the HIP runtime libbrx.so
+    itself is linked against (the symbol is looked up through the library's own dependencies): for the read-only views the
+    ABI hands out for checks"""
+    if not out.nbytes:
+        return
+    f = lib().hipMemcpy
+    f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    e = f(out.ctypes.data, d_ptr, out.nbytes, 2)  # hipMemcpyDeviceToHost
+    if e:
+        raise BrxError(-3, f"hipMemcpy to the host: HIP error {e}")
 
 
 def device_count() -> int:

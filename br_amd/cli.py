@@ -50,8 +50,8 @@ Not in the reference, like `--device` (include/brx.h "coverage"; a base is cover
                                are applied left to right in command-line order.  The files are merged as sorted lists on the
                                GPU, no counting table is built; -a or a threshold selector then pick the solid k-mers of the
                                combined list, and --save-counts / --save-min-count (also accepted behind `count`) write it.
-                               A list answers no lookups: --abundance-report is refused.  Shards counted apart, summed, with
-                               a contaminant's counts taken off:
+                               A list answers no lookups as it is: --abundance-report is refused unless --list-lookup is
+                               given (below).  Shards counted apart, summed, with a contaminant's counts taken off:
                                  python -m br_amd -i reads.fa -o corr.fa -c one count -i shard0.keys --counts-add shard1.keys \
                                      --counts-minus mito.keys -a 3 --save-counts job.keys
     fastq -i R.fq [-i ...] -k K (-a N | first-minimum | ...) [-q MINQ] [--all-bytes]
@@ -69,7 +69,18 @@ Not in the reference, like `--device` (include/brx.h "coverage"; a base is cover
                                fit one table.  Any odd k from 5 to 31; the same set, --save-counts file and correction as
                                without the flag.  A sweep's list keeps the k-mers counted at least --save-min-count times with
                                --save-counts, otherwise more than A times with -a A -- with -a, only solid k-mers are ever kept
-                               between sweeps -- otherwise all of them.  Lists answer no lookups: --abundance-report is refused
+                               between sweeps -- otherwise all of them.  Lists answer no lookups as they are:
+                               --abundance-report is refused unless --list-lookup is given (below)
+    --list-lookup              in front of the sub-command, with `count` or with `fasta` / `fastq` --count-parts: the count list
+                               gets a lookup directory (bucket offsets into its sorted keys, about half a byte per k-mer beside
+                               the list's 9) and --abundance-report is written from it (include/brx.h "lookups in a count
+                               list").  `fasta|fastq ... --count-parts P --list-lookup --abundance-report R`: the sweeps keep
+                               every k-mer whatever -a or --save-min-count say, --save-min-count is applied when --save-counts
+                               writes the file; report, set, count file and corrected reads are those of the same command
+                               without --count-parts.  `count -i A.keys [--counts-* ...] --list-lookup [--abundance-report R]`
+                               takes the list route even with no --counts-*: -i must be a key file, no counting table is built,
+                               the report uses the threshold in use.  A slower lookup than the table's (README "Count lists"):
+                               it is for the jobs that have no table
     fasta ... --skip-non-acgt  count only the k-mers of ACGTacgt bases (off by default: the reference counts every byte)
     solid | large-kmer -f fastq|fasta ... [-q MINQ] [--skip-non-acgt]
                                the same two switches for the presence-only sets
@@ -211,14 +222,44 @@ def load_count_list(flag: str, path: str, dev: int) -> CountList:
         raise SystemExit(f"Error: {flag} {path}: {e}")
 
 
-def build_set_from_lists(args, counts_path: Optional[str]) -> Pcon:
+def list_lookup_of(args) -> bool:
+    """--list-lookup: only where a count list is kept -- `fasta` / `fastq` with --count-parts, and `count`, which it sends down
+    the list route"""
+    if not args.list_lookup:
+        return False
+    if args.subcommand not in COUNTING:
+        raise SystemExit("Error: --list-lookup looks k-mers up in a count list, and `%s` keeps none: use it with `count`, or with "
+                         "`fasta` / `fastq` --count-parts" % args.subcommand)
+    if args.subcommand != "count" and getattr(args, "count_parts", None) is None:
+        raise SystemExit("Error: --list-lookup looks k-mers up in a count list, and `%s` without --count-parts keeps a counter, "
+                         "no list: --abundance-report asks the counter there, as it is" % args.subcommand)
+    return True
+
+
+def write_list_reports(lst: CountList, threshold: int, args, abund_paths) -> None:
+    """--list-lookup: the list gets its lookup directory, and every --abundance-report is written from it"""
+    if not abund_paths:
+        return
+    try:
+        lst.prepare_lookup()
+        for src, dst in zip(args.inputs, abund_paths):
+            with open_input(src) as f, open(dst, "wb") as rep:
+                write_abundance_report(lst, threshold, f, rep, args.record_buffer or 8192)
+        lst.drop_lookup()  # (the directory's memory goes back before the set is built)
+    except _lib.BrxError as e:
+        raise SystemExit(f"Error: --list-lookup: {e}")
+
+
+def build_set_from_lists(args, counts_path: Optional[str], abund_paths=None) -> Pcon:
     """the list route of `count`: the count file of -i combined with every --counts-* operand, left to right; the threshold
-    from -a or from the combined list's spectrum; --save-counts writes the combined list; the solid set is its finish"""
-    if args.abundance_report is not None:
+    from -a or from the combined list's spectrum; --save-counts writes the combined list; with --list-lookup the
+    --abundance-report is written from the combined list; the solid set is its finish"""
+    if args.abundance_report is not None and not args.list_lookup:
         raise SystemExit("Error: --abundance-report asks a k-mer counter about single k-mers, and --counts-* work on count lists, "
-                         "which answer no lookups: save the combined counts (--save-counts) and run `count -i` on that file")
+                         "which answer no lookups: save the combined counts (--save-counts) and run `count -i` on that file.  "
+                         "Or pass --list-lookup: the combined list then gets a lookup directory and the report is written from it")
     lst = load_count_list("count -i", args.sub_inputs, args.device)
-    for name, flag, path in args.count_ops:
+    for name, flag, path in args.count_ops or []:
         other = load_count_list(flag, path, args.device)
         if other.k != lst.k:
             raise SystemExit("Error: %s %s: k = %d, the counts in use have k = %d" % (flag, path, other.k, lst.k))
@@ -242,6 +283,8 @@ def build_set_from_lists(args, counts_path: Optional[str]) -> Pcon:
                 lst.save(f, 1 if args.save_min_count is None else args.save_min_count)
         except _lib.BrxError as e:
             raise SystemExit(f"Error: --save-counts: {e}")
+    if args.list_lookup:
+        write_list_reports(lst, thr, args, abund_paths)
     return lst.finish(thr)
 
 
@@ -264,19 +307,24 @@ COUNT_PARTS_HELP = ("count in P sweeps over the inputs (1 <= P <= 4096), each sw
                     "until the last sweep (not in the reference)")
 
 
-def build_set_in_parts(args, counts_path: Optional[str]) -> Pcon:
+def build_set_in_parts(args, counts_path: Optional[str], abund_paths=None) -> Pcon:
     """the --count-parts route of `fasta` and `fastq`: parts.count_in_parts, the threshold from -a or from the summed
-    spectrum, --save-counts writes the joined list, the solid set is its finish"""
-    if args.abundance_report is not None:
+    spectrum, --save-counts writes the joined list, the solid set is its finish.  With --list-lookup the sweeps keep every
+    k-mer, --save-min-count is applied at the save, and the --abundance-report is written from the joined list"""
+    if args.abundance_report is not None and not args.list_lookup:
         raise SystemExit("Error: --abundance-report asks a k-mer counter about single k-mers, and --count-parts keeps count lists, "
-                         "which answer no lookups: save the joined counts (--save-counts) and run `count -i` on that file")
+                         "which answer no lookups: save the joined counts (--save-counts) and run `count -i` on that file.  "
+                         "Or pass --list-lookup: the joined list then gets a lookup directory and the report is written from it")
     k = fasta_kmer_size(args.kmer_size)
     if not 5 <= k <= 31:
         raise SystemExit("Error: --count-parts counts through the hash table, which takes odd k from 5 to 31 (k=%d)" % k)
     if args.abundance is None and args.abundance_selection is None:
         raise SystemExit("Error: You must provide an abundance method or an abundance threshold")  # main.rs:109
-    if counts_path is not None:
-        floor = max(1, args.save_min_count or 1)
+    save_floor = max(1, args.save_min_count or 1)
+    if args.list_lookup:
+        floor = 1  # a report counts every k-mer of a read: nothing may be dropped between the sweeps
+    elif counts_path is not None:
+        floor = save_floor
     elif args.abundance is not None:
         floor = min(255, args.abundance + 1)
     else:
@@ -302,9 +350,11 @@ def build_set_in_parts(args, counts_path: Optional[str]) -> Pcon:
     if counts_path is not None:
         try:
             with open(counts_path, "wb") as f:
-                lst.save(f, floor)
+                lst.save(f, max(floor, save_floor))
         except _lib.BrxError as e:
             raise SystemExit(f"Error: --save-counts: {e}")
+    if args.list_lookup:
+        write_list_reports(lst, thr, args, abund_paths)
     return lst.finish(thr)
 
 
@@ -389,6 +439,10 @@ def parser() -> argparse.ArgumentParser:
                         "where its partitioned counter saves its count view (not in the reference)")
     p.add_argument("--save-min-count", type=u8, default=None, metavar="N",
                    help="keep only the k-mers counted at least N times in --save-counts (default 1)")
+    p.add_argument("--list-lookup", action="store_true",
+                   help="with `count`, or `fasta` / `fastq` --count-parts: keep the counts as a count list that answers lookups "
+                        "(a bucket directory of about half a byte per k-mer beside it), so that --abundance-report is written "
+                        "from the list; `count -i` must then be a key file (not in the reference)")
     sub = p.add_subparsers(dest="subcommand", required=True)
 
     def abundance_methods(sp):
@@ -561,9 +615,10 @@ def presence_set(path: str, fmt: str, k: int, dev: int, min_q: int = 0, skip_non
             raise SystemExit(f"Error: {e}")
 
 
-def write_abundance_report(cnt: Counter, threshold: int, f: BinaryIO, rep: BinaryIO, batch_records: int) -> None:
+def write_abundance_report(cnt, threshold: int, f: BinaryIO, rep: BinaryIO, batch_records: int) -> None:
     """one TSV line (abundance.report_line) per record of the FASTA stream `f`, in input order: the records go through
-    Counter.abundance_batch in batches of batch_records, statistics only"""
+    the abundance_batch of `cnt` -- a Counter, or a CountList after prepare_lookup -- in batches of batch_records, statistics
+    only"""
     from .set import pack_reads
     rep.write(abundance.REPORT_HEADER)
 
@@ -589,10 +644,11 @@ def main(argv: Optional[List[str]] = None) -> int:
     second_pass = second_pass_of(args)
     abund_paths = abundance_reports(args)
     counts_path = save_counts_of(args)
-    if getattr(args, "count_ops", None):
-        kmer_set = build_set_from_lists(args, counts_path)
+    list_lookup = list_lookup_of(args)
+    if getattr(args, "count_ops", None) or (list_lookup and args.subcommand == "count"):
+        kmer_set = build_set_from_lists(args, counts_path, abund_paths)
     elif getattr(args, "count_parts", None) is not None:
-        kmer_set = build_set_in_parts(args, counts_path)
+        kmer_set = build_set_in_parts(args, counts_path, abund_paths)
     elif abund_paths is None and counts_path is None:
         kmer_set = build_set(args)
     else:

@@ -15,7 +15,11 @@ means "255 or more", so `sub` from or by a saturated count is a bound, not a val
 
 `combine` is the expected value of the GPU path (include/brx.h "count lists", br_amd/csrc/brx_setops.hip:
 brx_counts_combine_device, brx_counts_combine), `spectrum` that of brx_counts_spectrum, `select` that of brx_counts_finish,
-`result_floor` the floor rule of brx_counts_combine -- as setops.py is for set algebra: no GPU and no library needed."""
+`result_floor` the floor rule of brx_counts_combine -- as setops.py is for set algebra: no GPU and no library needed.
+
+A list answers lookups through a DIRECTORY of bucket offsets into its sorted keys (include/brx.h "lookups in a count list",
+br_amd/csrc/brx_listlookup.hip): `auto_log2_buckets` is the bucket count brx_counts_lookup_prepare chooses, `directory` the
+array it builds, `lookup` what brx_counts_get_counts and the abundance calls of a list answer."""
 from __future__ import annotations
 
 from typing import Tuple
@@ -101,6 +105,50 @@ def select(keys, counts, abundance: int) -> np.ndarray:
     """the keys with count > abundance (strict, as every finish of the project)"""
     keys, counts = _list(keys, counts)
     return keys[counts.astype(np.int64) > int(abundance)]
+
+
+MAX_LOG2_BUCKETS = 30   # the largest directory a list takes: 2^30 + 1 offsets
+KEYS_PER_BUCKET = 16    # the mean the chosen directory aims at: 16 u64 keys are one 128-byte request
+
+
+def max_log2_buckets(k: int) -> int:
+    """the largest log2 of the bucket count at this k: a bucket holds at least one possible key"""
+    return min(2 * int(k) - 1, MAX_LOG2_BUCKETS)
+
+
+def auto_log2_buckets(n: int, k: int) -> int:
+    """the d brx_counts_lookup_prepare chooses for n keys: the smallest d >= 0 with 16 * 2^d >= n, capped at min(2k-1, 30)"""
+    d = 0
+    while d < max_log2_buckets(k) and (KEYS_PER_BUCKET << d) < int(n):
+        d += 1
+    return d
+
+
+def directory(keys, k: int, log2_buckets: int) -> np.ndarray:
+    """uint64[2^d + 1], the lookup directory of a list's ascending keys (all below 2^(2k-1)): entry b is the number of keys
+    < (b << shift), shift = (2k-1) - d, so bucket b is keys[dir[b] : dir[b + 1]] and the last entry is n"""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    d = int(log2_buckets)
+    if not 0 <= d <= max_log2_buckets(k):
+        raise ValueError(f"count list: log2_buckets={log2_buckets} (0..{max_log2_buckets(k)} at k={k})")
+    if keys.size and int(keys[-1]) >> (2 * int(k) - 1):
+        raise ValueError(f"count list: a key of 2^{2 * int(k) - 1} or more at k={k}")
+    shift = 2 * int(k) - 1 - d
+    borders = np.arange((1 << d) + 1, dtype=np.uint64) << np.uint64(shift)
+    return np.searchsorted(keys, borders, side="left").astype(np.uint64)
+
+
+def lookup(keys, counts, hashes) -> np.ndarray:
+    """uint8 per entry of `hashes` (canonical k-mer >> 1): the count beside that key, 0 where the list does not hold it --
+    what brx_counts_get_counts and the abundance calls of a list answer, whatever the directory"""
+    keys, counts = _list(keys, counts)
+    hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
+    out = np.zeros(hashes.size, dtype=np.uint8)
+    if keys.size:
+        pos = np.minimum(np.searchsorted(keys, hashes, side="left"), keys.size - 1)
+        hit = keys[pos] == hashes
+        out[hit] = counts[pos[hit]]
+    return out
 
 
 def result_floor(op, floor_a: int, floor_b: int) -> int:

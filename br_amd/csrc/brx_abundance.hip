@@ -20,6 +20,9 @@
 //   partitioned    the count view that brx_counter_lookup_prepare built (brx_partbuild.hip: final_view_kernel): the last
 //                  level's bucket h >> 12 holds its distinct keys h & 4095 sorted, at most 4096 of them, then padding;
 //                  two neighbouring offsets, a binary search of at most 12 steps, the count byte beside the key.
+//   count list     the directory that brx_counts_lookup_prepare built (brx_listlookup.hip): bucket khash >> shift is
+//                  keys[dir[b] .. dir[b + 1]), 16 keys in the mean; two neighbouring offsets, a binary search over the whole
+//                  bucket however large it is, the count byte beside the key.
 // A wave bins its counts into a 256-bin histogram of its own in LDS (one LDS atomic per position) and afterwards adds
 // the bins that are not zero to the read's row in global memory: integer atomic adds, so nothing depends on the launch
 // geometry or on timing.  abund_stats_kernel, a wave per read, turns the 256 bins into the statistics: a prefix sum over
@@ -31,7 +34,7 @@ using namespace brx;
 
 namespace {
 
-enum { SRC_NONE = 0, SRC_DENSE = 1, SRC_TABLE = 2, SRC_PART = 3 }; // what answers: nothing counted yet, the u8 table, the counting table, a partitioned counter's view
+enum { SRC_NONE = 0, SRC_DENSE = 1, SRC_TABLE = 2, SRC_PART = 3, SRC_LIST = 4 }; // what answers: nothing counted yet, the u8 table, the counting table, a partitioned counter's view, a count list's directory
 
 struct AbundArgs {
     // the counter
@@ -42,6 +45,10 @@ struct AbundArgs {
     const uint16_t *vkeys;  // count view of a partitioned counter: sorted low 12 bits per bucket, 0xFFFF behind them
     const uint8_t *vcounts; // min(255, count) beside every key
     const uint64_t *voff;   // bucket b = vkeys[voff[b] .. voff[b + 1])
+    const uint64_t *lkeys;  // count list: every key, ascending
+    const uint8_t *lcnts;   // the count beside every key
+    const uint64_t *ldir;   // bucket b = lkeys[ldir[b] .. ldir[b + 1]), b = key >> lshift
+    uint32_t lshift;
     int k;
     uint32_t abundance;
     // the batch
@@ -77,6 +84,20 @@ __device__ __forceinline__ uint32_t abund_count(const AbundArgs &a, uint64_t km)
         }
         // (lo == s + 4096 only if all 4096 keys are there and smaller, which key <= 4095 rules out)
         return lo < e && a.vkeys[lo] == key ? a.vcounts[lo] : 0u;
+    }
+    if (SRC == SRC_LIST) {
+        const uint64_t h = khash(km, a.k); // < 2^(2k-1), so its bucket is one of the directory's
+        const uint64_t b = h >> a.lshift;
+        const uint64_t e = a.ldir[b + 1];
+        uint64_t lo = a.ldir[b], hi = e;
+        while (lo < hi) { // first key >= h of the bucket, whatever its size
+            const uint64_t mid = lo + ((hi - lo) >> 1);
+            if (a.lkeys[mid] < h)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        return lo < e && a.lkeys[lo] == h ? a.lcnts[lo] : 0u;
     }
     const uint64_t rc = revcomp(km, a.k);
     const uint64_t key = (((popc64(km) & 1) ? rc : km) >> 1) + 1ull;
@@ -252,10 +273,20 @@ int abund_view(const brx_counter *c, const char *what, AbundArgs &a, int &src)
     return BRX_ERR_UNSUPPORTED;
 }
 
-int abund_enqueue(const brx_counter *c, AbundArgs &a, uint64_t total_bases, DevScratch &sc, hipStream_t s)
+// the same for a prepared count list; the caller holds its lookup lock shared
+void abund_view_list(const ListView &l, AbundArgs &a, int &src)
 {
-    int src = SRC_NONE;
-    BRX_TRY(abund_view(c, "abundance", a, src));
+    a.k = l.k;
+    a.lkeys = l.keys;
+    a.lcnts = l.cnts;
+    a.ldir = l.dir;
+    a.lshift = l.shift;
+    src = l.n ? SRC_LIST : SRC_NONE;
+}
+
+// `a` holds the view of what answers (src) and the batch
+int abund_enqueue(AbundArgs &a, int src, uint64_t total_bases, DevScratch &sc, hipStream_t s)
+{
     const uint32_t n_reads = a.n_reads;
     uint64_t tile_bound = 0;
     BRX_TRY(tile_list_enqueue(a.tl, a.offsets, n_reads, total_bases, "abundance", "abund_tiles", sc, tile_bound, s));
@@ -272,6 +303,8 @@ int abund_enqueue(const brx_counter *c, AbundArgs &a, uint64_t total_bases, DevS
             abund_kernel<SRC_PART><<<grid, 256, 0, s>>>(a);
         else if (src == SRC_DENSE)
             abund_kernel<SRC_DENSE><<<grid, 256, 0, s>>>(a);
+        else if (src == SRC_LIST)
+            abund_kernel<SRC_LIST><<<grid, 256, 0, s>>>(a);
         else
             abund_kernel<SRC_NONE><<<grid, 256, 0, s>>>(a);
     }
@@ -294,11 +327,15 @@ int abund_refuse_partitioned(const char *what, int k)
     return BRX_ERR_UNSUPPORTED;
 }
 
-int abund_batch(const brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
-                uint8_t abundance, uint8_t *d_profile, uint32_t *d_hist, brx_abund_stats_t *d_stats, hipStream_t s)
+} // namespace brx
+
+namespace {
+
+// the body of abund_batch and abund_batch_list: `a` holds the view of what answers
+int abund_run(AbundArgs &a, int src, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
+              uint8_t abundance, uint8_t *d_profile, uint32_t *d_hist, brx_abund_stats_t *d_stats, hipStream_t s)
 {
     DevScratch sc;
-    AbundArgs a{};
     a.abundance = abundance;
     a.n_reads = n_reads;
     a.bases = d_bases;
@@ -306,7 +343,7 @@ int abund_batch(const brx_counter *c, const uint8_t *d_bases, const uint64_t *d_
     a.profile = d_profile;
     a.hist = d_hist;
     a.stats = d_stats;
-    int st = abund_enqueue(c, a, total_bases, sc, s);
+    int st = abund_enqueue(a, src, total_bases, sc, s);
     // the scratch goes back to the pool when this returns: nothing of the call may still be running then
     const hipError_t e = hipStreamSynchronize(s);
     if (st == BRX_OK && e != hipSuccess) {
@@ -316,11 +353,8 @@ int abund_batch(const brx_counter *c, const uint8_t *d_bases, const uint64_t *d_
     return st;
 }
 
-int abund_get_counts(const brx_counter *c, const uint64_t *d_kmers, uint32_t n, uint8_t *d_out, hipStream_t s)
+int abund_get_run(const AbundArgs &a, int src, const uint64_t *d_kmers, uint32_t n, uint8_t *d_out, hipStream_t s)
 {
-    AbundArgs a{};
-    int src = SRC_NONE;
-    BRX_TRY(abund_view(c, "get_counts", a, src));
     const uint32_t grid = (n + 255u) / 256u;
     if (src == SRC_TABLE)
         abund_get_kernel<SRC_TABLE><<<grid, 256, 0, s>>>(a, d_kmers, n, d_out);
@@ -328,10 +362,68 @@ int abund_get_counts(const brx_counter *c, const uint64_t *d_kmers, uint32_t n, 
         abund_get_kernel<SRC_PART><<<grid, 256, 0, s>>>(a, d_kmers, n, d_out);
     else if (src == SRC_DENSE)
         abund_get_kernel<SRC_DENSE><<<grid, 256, 0, s>>>(a, d_kmers, n, d_out);
+    else if (src == SRC_LIST)
+        abund_get_kernel<SRC_LIST><<<grid, 256, 0, s>>>(a, d_kmers, n, d_out);
     else
         abund_get_kernel<SRC_NONE><<<grid, 256, 0, s>>>(a, d_kmers, n, d_out);
     BRX_HIP(hipGetLastError());
     return BRX_OK;
+}
+
+} // namespace
+
+namespace brx {
+
+int abund_empty_batch(uint32_t n_reads, uint64_t total_bases, uint8_t *d_profile, uint32_t *d_hist, brx_abund_stats_t *d_stats,
+                      hipStream_t s, bool *done)
+{
+    *done = true;
+    if (!n_reads || (!d_profile && !d_hist && !d_stats))
+        return BRX_OK;
+    if (!total_bases) { // reads without bases: no k-mers, and no kernel
+        if (d_hist)
+            BRX_HIP(hipMemsetAsync(d_hist, 0, (uint64_t)n_reads * 1024ull, s));
+        if (d_stats)
+            BRX_HIP(hipMemsetAsync(d_stats, 0, (uint64_t)n_reads * sizeof(brx_abund_stats_t), s));
+        BRX_HIP(hipStreamSynchronize(s));
+        return BRX_OK;
+    }
+    *done = false;
+    return BRX_OK;
+}
+
+int abund_batch(const brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
+                uint8_t abundance, uint8_t *d_profile, uint32_t *d_hist, brx_abund_stats_t *d_stats, hipStream_t s)
+{
+    AbundArgs a{};
+    int src = SRC_NONE;
+    BRX_TRY(abund_view(c, "abundance", a, src));
+    return abund_run(a, src, d_bases, d_offsets, n_reads, total_bases, abundance, d_profile, d_hist, d_stats, s);
+}
+
+int abund_batch_list(const ListView &l, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
+                     uint8_t abundance, uint8_t *d_profile, uint32_t *d_hist, brx_abund_stats_t *d_stats, hipStream_t s)
+{
+    AbundArgs a{};
+    int src = SRC_NONE;
+    abund_view_list(l, a, src);
+    return abund_run(a, src, d_bases, d_offsets, n_reads, total_bases, abundance, d_profile, d_hist, d_stats, s);
+}
+
+int abund_get_counts(const brx_counter *c, const uint64_t *d_kmers, uint32_t n, uint8_t *d_out, hipStream_t s)
+{
+    AbundArgs a{};
+    int src = SRC_NONE;
+    BRX_TRY(abund_view(c, "get_counts", a, src));
+    return abund_get_run(a, src, d_kmers, n, d_out, s);
+}
+
+int abund_get_counts_list(const ListView &l, const uint64_t *d_kmers, uint32_t n, uint8_t *d_out, hipStream_t s)
+{
+    AbundArgs a{};
+    int src = SRC_NONE;
+    abund_view_list(l, a, src);
+    return abund_get_run(a, src, d_kmers, n, d_out, s);
 }
 
 } // namespace brx

@@ -355,17 +355,9 @@ static int abund_check(const char *what, const brx_counter_t *c, const void *bas
 static int abund_batch_locked(brx_counter_t *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
                               uint8_t abundance, uint8_t *d_profile, uint32_t *d_hist, brx_abund_stats_t *d_stats, hipStream_t s)
 {
-    if (!n_reads || (!d_profile && !d_hist && !d_stats))
-        return BRX_OK;
-    if (!total_bases) { // reads without bases: no k-mers, and no kernel
-        if (d_hist)
-            BRX_HIP(hipMemsetAsync(d_hist, 0, (uint64_t)n_reads * 1024ull, s));
-        if (d_stats)
-            BRX_HIP(hipMemsetAsync(d_stats, 0, (uint64_t)n_reads * sizeof(brx_abund_stats_t), s));
-        BRX_HIP(hipStreamSynchronize(s));
-        return BRX_OK;
-    }
-    return abund_batch(c, d_bases, d_offsets, n_reads, total_bases, abundance, d_profile, d_hist, d_stats, s);
+    bool done = false;
+    BRX_TRY(abund_empty_batch(n_reads, total_bases, d_profile, d_hist, d_stats, s, &done));
+    return done ? BRX_OK : abund_batch(c, d_bases, d_offsets, n_reads, total_bases, abundance, d_profile, d_hist, d_stats, s);
 }
 
 int brx_counter_abundance_batch_device(brx_counter_t *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads,

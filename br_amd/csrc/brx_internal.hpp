@@ -5,6 +5,7 @@
 #include <stdarg.h>
 #include <atomic>
 #include <mutex>
+#include <shared_mutex>
 #include <string>
 #include <vector>
 
@@ -354,13 +355,20 @@ bool part_lookup_shape(const brx_counter *c, uint64_t *n_buckets, uint64_t *n_po
 int abund_batch(const brx_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
                 uint8_t abundance, uint8_t *d_profile, uint32_t *d_hist, brx_abund_stats_t *d_stats, hipStream_t s);
 int abund_get_counts(const brx_counter *c, const uint64_t *d_kmers, uint32_t n, uint8_t *d_out, hipStream_t s);
+// what every batch entry does with a batch that has no k-mers to look up, before it asks for a view: *done = true when
+// that was all -- no reads or no output asked for: nothing; reads without bases: histograms and statistics zeroed on `s`,
+// which is synchronised
+int abund_empty_batch(uint32_t n_reads, uint64_t total_bases, uint8_t *d_profile, uint32_t *d_hist, brx_abund_stats_t *d_stats,
+                      hipStream_t s, bool *done);
 // sets the error of a partitioned counter that has no count view, returns BRX_ERR_UNSUPPORTED
 int abund_refuse_partitioned(const char *what, int k);
 // trusted stretches (brx_trust.hip): adds the five columns of n_reads statistics rows to d_tot5[0 .. 5), enqueued on `s`
 int trust_totals_add(const brx_trust_stats_t *d_stats, uint32_t n_reads, unsigned long long *d_tot5, hipStream_t s);
 }
 
-// A count list (include/brx.h "count lists"): immutable once handed out, so it needs no lock and no stream of its own.
+// A count list (include/brx.h "count lists"): keys and counts are immutable once handed out, so they need no lock and no
+// stream of their own.  The lookup directory (brx_listlookup.hip) is the one thing that comes and goes: prepare and drop
+// hold lk_mu exclusively, the lookups hold it shared for as long as their kernels run, every other entry ignores it.
 struct brx_counts {
     int k = 0;
     int device = 0;
@@ -368,9 +376,46 @@ struct brx_counts {
     uint64_t n = 0;               // entries
     brx::DevBuf<uint64_t> d_keys; // strictly ascending; both empty when n == 0
     brx::DevBuf<uint8_t> d_cnts;
+    mutable std::shared_mutex lk_mu;
+    int lk_log2 = -1;             // log2 of the directory's buckets; -1: no directory, lookups refuse
+    brx::DevBuf<uint64_t> d_dir;  // 2^lk_log2 + 1 offsets: d_dir[b] = number of keys < (b << (2k-1 - lk_log2))
+    uint64_t lk_fullest = 0;      // keys in the fullest bucket
 };
 
 namespace brx {
+// what the host-path entries of lists and set algebra share (brx_setops.hip, brx_listlookup.hip): the null check, and a
+// stream of the call's own that is synchronised and destroyed when the call returns
+inline int list_ok(const char *me, const brx_counts *l)
+{
+    if (!l) {
+        set_error("%s: null count list", me);
+        return BRX_ERR_ARG;
+    }
+    return BRX_OK;
+}
+struct OwnStream {
+    hipStream_t s = nullptr;
+    ~OwnStream()
+    {
+        if (s) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamDestroy(s);
+        }
+    }
+};
+// What a lookup reads of a prepared list (the caller holds lk_mu shared), and the two lookups over it (brx_abundance.hip):
+// abund_batch / abund_get_counts with the list in the counter's place.
+struct ListView {
+    int k;
+    const uint64_t *keys;
+    const uint8_t *cnts;
+    const uint64_t *dir;
+    uint32_t shift; // bucket of key x = x >> shift
+    uint64_t n;
+};
+int abund_batch_list(const ListView &l, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads, uint64_t total_bases,
+                     uint8_t abundance, uint8_t *d_profile, uint32_t *d_hist, brx_abund_stats_t *d_stats, hipStream_t s);
+int abund_get_counts_list(const ListView &l, const uint64_t *d_kmers, uint32_t n, uint8_t *d_out, hipStream_t s);
 // The merge of two count lists into arrays sized from pass 1 (brx_setops.hip; timer "count_merge"): d_kout and, with
 // want_counts, d_cout receive exactly *n_out entries (both reset when there are none); *both (may be null) = |A n B|.
 // min_count is 1 .. 256 (256 keeps nothing: count > 255).  An empty B with BRX_COUNTOP_ADD is the compaction `count >=

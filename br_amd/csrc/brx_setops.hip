@@ -685,15 +685,6 @@ uint32_t result_floor(const char *me, int op, uint32_t fa, uint32_t fb)
     return 1u;
 }
 
-int list_ok(const char *me, const brx_counts *l)
-{
-    if (!l) {
-        set_error("%s: null count list", me);
-        return BRX_ERR_ARG;
-    }
-    return BRX_OK;
-}
-
 int operands_ok(const char *me, const brx_set *a, const brx_set *b)
 {
     if (!a || !b) {
@@ -739,17 +730,6 @@ int operands_list(const brx_set *a, const brx_set *b, hipStream_t s, Operands *o
     o->d_b = o->keys_b;
     return BRX_OK;
 }
-
-struct OwnStream {
-    hipStream_t s = nullptr;
-    ~OwnStream()
-    {
-        if (s) {
-            (void)hipStreamSynchronize(s);
-            (void)hipStreamDestroy(s);
-        }
-    }
-};
 
 } // namespace
 

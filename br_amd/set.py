@@ -521,8 +521,10 @@ class Pcon(KmerSet):
 class CountList:
     """An immutable sorted list of (key, count) on one device: the content of a count file without a counting table
     (include/brx.h "count lists", br_amd/countops.py).  Lists add, subtract, take the minimum and the maximum by a merge;
-    `spectrum()` and `finish(abundance)` give what a table counter that loaded the same file gives.  A list answers no
-    lookups: get_counts and the abundance calls stay the counters'."""
+    `spectrum()` and `finish(abundance)` give what a table counter that loaded the same file gives.  A list answers
+    lookups -- get_counts and the abundance calls, with Counter's signatures -- once `prepare_lookup()` has built its
+    bucket directory, about n/2 bytes beside the list's 9n; a k-mer that is not listed answers 0, which for a list of floor
+    f > 1 means "counted fewer than f times, or never"."""
 
     def __init__(self, handle: int, device: int):
         self._h = C.c_void_p(handle)
@@ -657,6 +659,74 @@ class CountList:
         self.save(f)
         _, keys, counts, _ = keyfile.decode(f.getvalue())
         return keys, counts
+
+    # ---- lookups (include/brx.h "lookups in a count list", countops.directory / lookup) ----
+    def prepare_lookup(self, log2_buckets: Optional[int] = None) -> None:
+        """build the lookup directory: 2^d + 1 offsets into the sorted keys, d = log2_buckets or countops.auto_log2_buckets(n,
+        k) (brx_counts_lookup_prepare).  The d already in place: nothing is done; another d: rebuilt"""
+        d = -1 if log2_buckets is None else int(log2_buckets)
+        if d < -1:
+            raise ValueError(f"log2_buckets={log2_buckets}")
+        _lib.check(_lib.lib().brx_counts_lookup_prepare(self._h, d))
+
+    def lookup_info(self) -> dict:
+        v = (C.c_uint64 * 4)()
+        _lib.check(_lib.lib().brx_counts_lookup_info(self._h, v))
+        return {"ready": bool(v[0]), "log2_buckets": int(v[1]), "directory_bytes": int(v[2]), "fullest_bucket": int(v[3])}
+
+    @property
+    def lookup_ready(self) -> bool:
+        """whether the abundance calls and get_counts would answer"""
+        return self.lookup_info()["ready"]
+
+    def lookup_directory(self) -> np.ndarray:
+        """the directory as uint64[2^d + 1] on the host (a copy, for checks): countops.directory(keys, k, d)"""
+        p, n = C.c_void_p(), C.c_uint64(0)
+        _lib.check(_lib.lib().brx_counts_lookup_directory(self._h, C.byref(p), C.byref(n)))
+        out = np.zeros(int(n.value), dtype=np.uint64)
+        _lib.copy_to_host(p.value, out)
+        return out
+
+    def drop_lookup(self) -> None:
+        """free the directory; the lookups refuse again"""
+        _lib.check(_lib.lib().brx_counts_lookup_drop(self._h))
+
+    def abundance_batch(self, bases: np.ndarray, offsets: np.ndarray, abundance: int = 0, profile: bool = True,
+                        hist: bool = False):
+        """Counter.abundance_batch from the list (brx_counts_abundance_batch): after prepare_lookup()"""
+        from . import abundance as ab
+        _check_u8(abundance, "abundance")
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        pr = np.zeros(bases.size, dtype=np.uint8) if profile else None
+        hi = np.zeros((n, 256), dtype=np.uint32) if hist else None
+        st = np.zeros(n, dtype=ab.STATS_DTYPE)
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        _lib.check(_lib.lib().brx_counts_abundance_batch(self._h, bases.ctypes.data, offsets.ctypes.data, n, abundance,
+                                                         ptr(pr), ptr(hi), ptr(st)))
+        return pr, hi, st
+
+    def abundance_batch_device(self, d_bases: int, d_offsets: int, n_reads: int, total_bases: int, abundance: int = 0,
+                               d_profile: Optional[int] = None, d_hist: Optional[int] = None, d_stats: Optional[int] = None,
+                               stream: Optional[int] = None) -> None:
+        _check_u8(abundance, "abundance")
+        _lib.check(_lib.lib().brx_counts_abundance_batch_device(self._h, d_bases, d_offsets, n_reads, total_bases, abundance,
+                                                                d_profile, d_hist, d_stats, stream))
+
+    def abundance_reads(self, reads: Sequence[bytes], abundance: int = 0):
+        """(list of per-read uint8 arrays of length kmers, stats array) of `reads`"""
+        from . import abundance as ab
+        bases, offs = pack_reads(reads)
+        pr, _, st = self.abundance_batch(bases, offs, abundance)
+        return ab.unpack_profile(pr, offs, self.k), st
+
+    def get_counts(self, kmers: Sequence[int]) -> np.ndarray:
+        """uint8 count of every forward k-mer (of its canonical form), 0 where it is not listed: Counter.get_counts' twin"""
+        km = np.ascontiguousarray(np.asarray(kmers, dtype=np.uint64))
+        out = np.zeros(km.size, dtype=np.uint8)
+        _lib.check(_lib.lib().brx_counts_get_counts(self._h, km.ctypes.data, km.size, out.ctypes.data))
+        return out
 
 
 class Counter:

@@ -543,8 +543,10 @@ int brx_counts_combine_device(const uint64_t *d_ka, const uint8_t *d_ca, uint64_
                               void *stream);
 /* The object: an immutable count list on one device.  Every entry below is host-path: it works on a stream of its own and
  * returns complete; a list may be read by any number of host threads at once.
- * NOT supported: looking single k-mers up in a list (get_counts and abundance stay the counters'), lists across ranks, lists
- * of dense or merged counters, and turning a list back into a table counter other than through its file.                    */
+ * A list answers lookups (get_counts, abundance) once brx_counts_lookup_prepare has built its bucket directory, about n/2
+ * bytes beside the list's 9n: see "lookups in a count list" below.
+ * NOT supported: lists across ranks, lists of dense or merged counters, and turning a list back into a table counter other
+ * than through its file.                                                                                                    */
 typedef struct brx_counts brx_counts_t;
 /* The list of a count file, any odd k from 5 to 31, floor from the header; the descriptor is read sequentially, never
  * sought.  Every malformed stream brx_counter_load_fd refuses is refused with the same status and message; a set file (no
@@ -584,6 +586,44 @@ int brx_counts_spectrum(const brx_counts_t *l, uint64_t *hist256);
  * stats8 (may be NULL): [0] entries, [1] kept, [2] 0, [3] 0, [4] ns selecting, [5] 0, [6] ns building the set, [7] ns wall.   */
 int brx_counts_finish(const brx_counts_t *l, uint8_t abundance, brx_set_t **out, uint64_t *stats8);
 void brx_counts_free(brx_counts_t *l);
+/* Lookups in a count list.  A sorted key list with a count byte beside each key lacks only an entry point: the LOOKUP
+ * DIRECTORY.  For the list's n ascending keys (all below 2^(2k-1)) and 2^d buckets, shift = (2k-1) - d:
+ *     dir[b] = number of keys < (b << shift), b = 0 .. 2^d (u64 offsets; dir[2^d] = n),
+ * and a lookup of key x = canonical k-mer >> 1 reads dir[x >> shift] and dir[(x >> shift) + 1], searches keys[lo .. hi) and
+ * reads the count byte beside the key it found.  The search takes a bucket of any size: a list that skews into one bucket is
+ * slow, never wrong.  br_amd/countops.py states directory, choice of d and lookup in numpy.
+ * prepare: log2_buckets < 0 chooses d as the smallest d >= 0 with 16 * 2^d >= n, capped at min(2k-1, 30) -- a mean of at most
+ * 16 keys, one 128-byte request, per bucket, and about n/2 bytes of directory; a caller's own d is taken from 0 to that cap
+ * (BRX_ERR_ARG above it).  One launch of its own (br_amd/csrc/brx_listlookup.hip, profile timer "list_dir"): a thread per
+ * bucket border searches its lower bound, no workgroup waits for another.  Host-path like every list entry: a stream of its
+ * own, complete on return.  The d already in place: nothing is done; another d: the directory is rebuilt.  An empty list
+ * prepares to a directory of zeros and answers zeros.
+ * info4: [0] 1 if lookups answer, [1] log2 buckets, [2] directory bytes, [3] keys in the fullest bucket (all 0 without a
+ * directory).  directory: the device array and its 2^d + 1 entries, read only, valid until the next prepare / drop
+ * (BRX_ERR_UNSUPPORTED without one).  drop: frees the directory; lookups refuse again.
+ * prepare and drop take the list's lookup lock exclusively, the lookups below take it shared, so a prepared list is looked
+ * up from any number of host threads at once; every other list entry ignores the directory and gives what it gave without
+ * one.  brx_counts_combine's result has no directory.
+ * The lookups are the twins of brx_counter_abundance_batch_device / _batch / brx_counter_get_counts ("abundance" above) with
+ * the same definitions of profile, histogram and statistics, NULL outputs, n_reads == 0 and total_bases == 0, and for the
+ * _device form the same stream contract (enqueued on `stream`, complete on return); the host forms work on a stream of their
+ * own.  count[i] is the list's byte for the k-mer, 0 for a k-mer that is not listed: for a list of floor f > 1 a 0 means
+ * "counted fewer than f times, or never".  Without a directory they return BRX_ERR_UNSUPPORTED and name
+ * brx_counts_lookup_prepare: nothing builds it implicitly, as with the partitioned counter's count view.
+ * Measured on the bench's 1 Gbp (tools/list_lookup_bench.py, profiles/list_lookup_bench.json; ms per Gbp, median of 5): at
+ * k = 19 / 21 / 25, 582 / 625 / 698 M entries under 2^26 buckets (537 MB), list_dir 12.4; abundance statistics from the list
+ * 105.3 / 105.8 / 107.1 against 17.1 / 18.1 / 30.7 from the table counter and 126.3 / 88.3 from the partitioned view (k = 19 /
+ * 21).  A list is 3.5x to 6.2x slower to ask than the table: it is for the jobs that have no table (DESIGN.md sections 4, 10). */
+int brx_counts_lookup_prepare(brx_counts_t *l, int log2_buckets /* < 0: chosen from n */);
+int brx_counts_lookup_info(const brx_counts_t *l, uint64_t *info4);
+int brx_counts_lookup_directory(const brx_counts_t *l, void **d_dir, uint64_t *entries);
+int brx_counts_lookup_drop(brx_counts_t *l);
+int brx_counts_abundance_batch_device(const brx_counts_t *l, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n_reads,
+                                      uint64_t total_bases, uint8_t abundance, uint8_t *d_profile, uint32_t *d_hist,
+                                      brx_abund_stats_t *d_stats, void *stream);
+int brx_counts_abundance_batch(const brx_counts_t *l, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                               uint8_t abundance, uint8_t *profile, uint32_t *hist, brx_abund_stats_t *stats);
+int brx_counts_get_counts(const brx_counts_t *l, const uint64_t *forward_kmers, uint32_t n, uint8_t *out);
 
 /* ---- multi-GPU: reads shard over the GPUs, the set is exchanged ONCE -----------------------------
  * The reference is one process with rayon threads over shared memory (src/main.rs:30-33, src/lib.rs:72-139); on N
