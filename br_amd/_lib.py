@@ -138,6 +138,8 @@ SIGNATURES = {
     "brx_counts_info": (C.c_int, [_vp, _u64p]),
     "brx_counts_device": (C.c_int, [_vp, _pp, _pp, _u64p]),
     "brx_counts_combine": (C.c_int, [_vp, _vp, C.c_int, C.c_uint8, _pp, _u64p]),
+    "brx_counts_joint_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, _u64p, _vp]),
+    "brx_counts_compare": (C.c_int, [_vp, _vp, _u64p, _u64p]),
     "brx_counts_spectrum": (C.c_int, [_vp, _u64p]),
     "brx_counts_finish": (C.c_int, [_vp, C.c_uint8, _pp, _u64p]),
     "brx_counts_free": (None, [_vp]),

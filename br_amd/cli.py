@@ -54,6 +54,20 @@ Not in the reference, like `--device` (include/brx.h "coverage"; a base is cover
                                given (below).  Shards counted apart, summed, with a contaminant's counts taken off:
                                  python -m br_amd -i reads.fa -o corr.fa -c one count -i shard0.keys --counts-add shard1.keys \
                                      --counts-minus mito.keys -a 3 --save-counts job.keys
+    count -i A.keys [--counts-* ...] --counts-compare PATH --compare-report PATH
+                               put the counts in use -- after every --counts-* flag -- side by side with the count file in PATH
+                               (gz / bz2 / xz sniffed, the same k) and write a TSV report: the k-mers of either, both, each one
+                               alone and their Jaccard index, how much of PATH's k-mers the solid k-mers cover (completeness),
+                               the share of the solid k-mers' occurrences PATH does not vouch for, as a per-base error rate and
+                               QV (Merqury's k-mer survival formula), then the joint spectrum itself: one line `ca cb kmers`
+                               per pair of counts (br_amd/countops.py compare_report; include/brx.h "count lists").  A k-mer of
+                               the counts in use counts as kept where the set being built keeps it (count > threshold), a k-mer
+                               of PATH as vouched for wherever it is listed.  Each flag needs the other; either takes the list
+                               route: -i must be a key file, no counting table is built.  Set, corrected reads and
+                               --save-counts file are those of the same command without the two flags.  How good was a
+                               correction, given a trusted count file:
+                                 python -m br_amd -i reads.fa -o corr.fa -c one count -i corrected.keys \
+                                     --counts-compare illumina.keys --compare-report qv.tsv -a 0
     fastq -i R.fq [-i ...] -k K (-a N | first-minimum | ...) [-q MINQ] [--all-bytes]
                                a sub-command like `fasta` that counts FASTQ reads (gz / bz2 / xz sniffed), and only the k-mers
                                none of whose bases is untrusted: a base is untrusted when it is not ACGTacgt or its quality
@@ -97,7 +111,7 @@ import lzma
 import sys
 from typing import BinaryIO, List, Optional
 
-from . import _lib, abundance, fasta, keyfile, parts, spectrum, strand, trust
+from . import _lib, abundance, countops, fasta, keyfile, parts, spectrum, strand, trust
 from .correct import build_methods
 from .driver import run_correction
 from .set import Counter, CountList, Pcon
@@ -236,6 +250,17 @@ def list_lookup_of(args) -> bool:
     return True
 
 
+def compare_of(args) -> bool:
+    """--counts-compare PATH --compare-report PATH behind `count`: each needs the other; either sends `count` down the list
+    route"""
+    given = getattr(args, "counts_compare", None) is not None, getattr(args, "compare_report", None) is not None
+    if given[0] != given[1]:
+        raise SystemExit("Error: --counts-compare names the count file to compare with and --compare-report the file the "
+                         "report goes to: %s was given without %s" % (("--counts-compare", "--compare-report") if given[0] else
+                                                                      ("--compare-report", "--counts-compare")))
+    return given[0]
+
+
 def write_list_reports(lst: CountList, threshold: int, args, abund_paths) -> None:
     """--list-lookup: the list gets its lookup directory, and every --abundance-report is written from it"""
     if not abund_paths:
@@ -253,7 +278,8 @@ def write_list_reports(lst: CountList, threshold: int, args, abund_paths) -> Non
 def build_set_from_lists(args, counts_path: Optional[str], abund_paths=None) -> Pcon:
     """the list route of `count`: the count file of -i combined with every --counts-* operand, left to right; the threshold
     from -a or from the combined list's spectrum; --save-counts writes the combined list; with --list-lookup the
-    --abundance-report is written from the combined list; the solid set is its finish"""
+    --abundance-report is written from the combined list; with --counts-compare the --compare-report is written from the
+    joint spectrum of the combined list and that file; the solid set is its finish"""
     if args.abundance_report is not None and not args.list_lookup:
         raise SystemExit("Error: --abundance-report asks a k-mer counter about single k-mers, and --counts-* work on count lists, "
                          "which answer no lookups: save the combined counts (--save-counts) and run `count -i` on that file.  "
@@ -267,6 +293,11 @@ def build_set_from_lists(args, counts_path: Optional[str], abund_paths=None) -> 
             lst = lst.combine(other, name)
         except _lib.BrxError as e:
             raise SystemExit(f"Error: {flag} {path}: {e}")
+    compare = None
+    if compare_of(args):
+        compare = load_count_list("--counts-compare", args.counts_compare, args.device)
+        if compare.k != lst.k:
+            raise SystemExit("Error: --counts-compare %s: k = %d, the counts in use have k = %d" % (args.counts_compare, compare.k, lst.k))
     thr = args.abundance
     if thr is None:
         if args.abundance_selection is None:
@@ -285,6 +316,15 @@ def build_set_from_lists(args, counts_path: Optional[str], abund_paths=None) -> 
             raise SystemExit(f"Error: --save-counts: {e}")
     if args.list_lookup:
         write_list_reports(lst, thr, args, abund_paths)
+    if compare is not None:
+        # A: the combined list, a k-mer kept where the set being built keeps it; B: the file, vouching wherever it lists
+        try:
+            J = lst.joint(compare)
+            with open(args.compare_report, "wb") as f:
+                f.write(countops.compare_report(lst.k, lst.floor, compare.floor, J, min_a=thr + 1, min_b=1))
+        except _lib.BrxError as e:
+            raise SystemExit(f"Error: --counts-compare {args.counts_compare}: {e}")
+        del compare  # (the file's list goes back before the set is built)
     return lst.finish(thr)
 
 
@@ -459,6 +499,12 @@ def parser() -> argparse.ArgumentParser:
         c.add_argument(flag, action=CountOpAction, dest="count_ops", default=None, metavar="PATH",
                        help=what + " the count file in PATH (the same k); -i must be a count file too.  Repeatable, applied in "
                             "command-line order, merged as sorted lists without a counting table (not in the reference)")
+    c.add_argument("--counts-compare", default=None, metavar="PATH",
+                   help="with --compare-report: compare the counts in use, after every --counts-* flag, with the count file in PATH "
+                        "(the same k) by their joint spectrum; -i must be a count file too (not in the reference)")
+    c.add_argument("--compare-report", default=None, metavar="PATH",
+                   help="with --counts-compare: write shared and private k-mers, completeness, error rate, QV and the joint spectrum "
+                        "as TSV (br_amd/countops.py compare_report)")
     # (the two top-level flags are also taken behind `count`, where a command line that combines count files has its paths)
     c.add_argument("--save-counts", default=argparse.SUPPRESS, metavar="PATH", help="as in front of the sub-command")
     c.add_argument("--save-min-count", type=u8, default=argparse.SUPPRESS, metavar="N", help="as in front of the sub-command")
@@ -645,7 +691,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     abund_paths = abundance_reports(args)
     counts_path = save_counts_of(args)
     list_lookup = list_lookup_of(args)
-    if getattr(args, "count_ops", None) or (list_lookup and args.subcommand == "count"):
+    if getattr(args, "count_ops", None) or (list_lookup and args.subcommand == "count") or compare_of(args):
         kmer_set = build_set_from_lists(args, counts_path, abund_paths)
     elif getattr(args, "count_parts", None) is not None:
         kmer_set = build_set_in_parts(args, counts_path, abund_paths)

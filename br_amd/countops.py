@@ -101,6 +101,105 @@ def spectrum(k: int, counts, floor: int = 1) -> np.ndarray:
     return h
 
 
+# the joint kernel keeps the bins ca, cb < JOINT_CORNER in LDS (JOINT_CORNER of brx_setops.hip; the tests aim at its edge)
+JOINT_CORNER = 64
+
+
+def joint(a_keys, a_cnts, b_keys, b_cnts) -> np.ndarray:
+    """uint64[256][256], the joint spectrum: J[ca][cb] = keys of A u B with count byte ca in A and cb in B, 0 where the list
+    does not hold the key; J[0][0] = 0 (brx_counts_joint_device; brx_counts_compare sets J[0][0] = 2^(2k-1) - |A u B|, so
+    that the row sums are A's `spectrum` and the column sums B's).  Counts are bytes as they are: 255 is "255 or more"; a
+    key a floored list does not hold falls in row or column 0"""
+    ka, ca = _list(a_keys, a_cnts)
+    kb, cb = _list(b_keys, b_cnts)
+    keys = np.union1d(ka, kb)
+    va = np.zeros(keys.size, dtype=np.int64)
+    vb = np.zeros(keys.size, dtype=np.int64)
+    va[np.searchsorted(keys, ka)] = ca
+    vb[np.searchsorted(keys, kb)] = cb
+    return np.bincount(va * 256 + vb, minlength=65536).astype(np.uint64).reshape(256, 256)
+
+
+def _joint_of(J) -> np.ndarray:
+    J = np.ascontiguousarray(J, dtype=np.uint64)
+    if J.shape != (256, 256):
+        raise ValueError("joint spectrum: a (256, 256) array")
+    return J
+
+
+def compare_summary(J, k: int, min_a: int = 1, min_b: int = 1) -> dict:
+    """What two lists say about each other, from their joint spectrum alone (J[0][0] is never read); every integer field in
+    exact integer arithmetic.
+        a, b, both, either   distinct keys with ca >= 1, with cb >= 1, with both, with either (Pcon.compare's names)
+        jaccard              both / either, 0.0 when either == 0
+        a_solid, b_solid, both_solid   the same with ca >= min_a and cb >= min_b
+        completeness         both_solid / b_solid: the share of B's k-mers at min_b or above that A holds at min_a or above;
+                             nan when b_solid == 0
+        a_occ                sum of ca * J[ca][cb] over ca >= min_a: occurrences in A (a saturated byte counts as 255, a
+                             lower bound)
+        a_only_occ           the part of a_occ with cb < min_b: occurrences in A of k-mers B does not vouch for
+        error_rate, qv       1 - (1 - a_only_occ / a_occ) ** (1 / k) and -10 log10 of it: the k-mer survival formula Merqury
+                             uses, taken over occurrences; qv = inf when a_only_occ == 0, both nan when a_occ == 0"""
+    J = _joint_of(J)
+    min_a, min_b, k = int(min_a), int(min_b), int(k)
+    if not (1 <= min_a <= 256 and 1 <= min_b <= 256):
+        raise ValueError(f"joint spectrum: min_a={min_a}, min_b={min_b} (1..256)")
+    if k < 1:
+        raise ValueError(f"joint spectrum: k={k}")
+
+    def total(x) -> int:  # (a sum of bins may pass 2^64: the two halves of the bins apart, each sum below 2^48)
+        return (int((x >> np.uint64(32)).sum()) << 32) + int((x & np.uint64(0xFFFFFFFF)).sum())
+
+    a, b, both = total(J[1:, :]), total(J[:, 1:]), total(J[1:, 1:])
+    either = a + b - both
+    a_solid, b_solid, both_solid = total(J[min_a:, :]), total(J[:, min_b:]), total(J[min_a:, min_b:])
+    a_occ = sum(ca * total(J[ca, :]) for ca in range(min_a, 256))
+    a_only_occ = sum(ca * total(J[ca, :min_b]) for ca in range(min_a, 256))
+    if a_occ == 0:
+        error_rate = qv = float("nan")
+    elif a_only_occ == 0:
+        error_rate, qv = 0.0, float("inf")
+    else:
+        error_rate = 1.0 - (1.0 - a_only_occ / a_occ) ** (1.0 / k)
+        qv = -10.0 * float(np.log10(error_rate)) + 0.0  # (+ 0.0: an error rate of 1 gives 0.0, not -0.0)
+    return {"a": a, "b": b, "both": both, "either": either, "jaccard": both / either if either else 0.0,
+            "a_solid": a_solid, "b_solid": b_solid, "both_solid": both_solid,
+            "completeness": both_solid / b_solid if b_solid else float("nan"),
+            "a_occ": a_occ, "a_only_occ": a_only_occ, "error_rate": error_rate, "qv": qv}
+
+
+SUMMARY_INTS = ("a", "b", "both", "either", "a_solid", "b_solid", "both_solid", "a_occ", "a_only_occ")
+SUMMARY_FLOATS = (("jaccard", 6), ("completeness", 6), ("error_rate", 9), ("qv", 3))  # the decimals the report prints
+
+
+def _fixed(x: float, decimals: int) -> bytes:
+    """x to a fixed number of decimals, halves up, from the shortest text that reads back as x; nan and inf by name"""
+    from decimal import ROUND_HALF_UP, Decimal
+    if x != x:
+        return b"nan"
+    if x in (float("inf"), float("-inf")):
+        return b"inf" if x > 0 else b"-inf"
+    return format(Decimal(repr(float(x))).quantize(Decimal(1).scaleb(-decimals), rounding=ROUND_HALF_UP), "f").encode()
+
+
+def compare_report(k: int, floor_a: int, floor_b: int, J, min_a: int = 1, min_b: int = 1) -> bytes:
+    """the bytes of --compare-report: `#name<TAB>value` lines for k, both floors, min_a, min_b and every field of
+    compare_summary (floats to SUMMARY_FLOATS' decimals, halves up), then `#ca<TAB>cb<TAB>kmers` and one line per non-zero
+    bin except [0][0], rows ascending and columns ascending within a row"""
+    J = _joint_of(J)
+    s = compare_summary(J, k, min_a, min_b)
+    out = [b"#%s\t%d\n" % (name, v) for name, v in ((b"k", int(k)), (b"floor_a", int(floor_a)), (b"floor_b", int(floor_b)),
+                                                    (b"min_a", int(min_a)), (b"min_b", int(min_b)))]
+    out += [b"#%s\t%d\n" % (name.encode(), s[name]) for name in SUMMARY_INTS]
+    out += [b"#%s\t%s\n" % (name.encode(), _fixed(s[name], decimals)) for name, decimals in SUMMARY_FLOATS]
+    out.append(b"#ca\tcb\tkmers\n")
+    flat = J.ravel()
+    for x in np.flatnonzero(flat):
+        if x:
+            out.append(b"%d\t%d\t%d\n" % (x >> 8, x & 255, int(flat[x])))
+    return b"".join(out)
+
+
 def select(keys, counts, abundance: int) -> np.ndarray:
     """the keys with count > abundance (strict, as every finish of the project)"""
     keys, counts = _list(keys, counts)

@@ -28,6 +28,9 @@
 //            and counts in LDS, writes one run of each per tile and sums what it wrote: that must be the scanned total.
 //   LDS      pass 2: 2 x 2050 keys, 2048 staged keys, 2 x 2050 + 2048 count bytes: 55 KB static.
 // Timer "count_merge" for split, both passes and the scan; count_hist_kernel (a list's spectrum) under "count_hist".
+//   joint    count_joint_kernel: pass 1 without a keep rule -- the pair (ca, cb) of every key of A u B binned into u64[256][256],
+//            the bins below 64 x 64 in 16 KB of LDS per block (53 KB static with the pieces), the rest by global adds.  The
+//            table is built in scratch and copied out only when both lists passed the checks.  Timer "count_joint".
 #include "brx_internal.hpp"
 
 #include <chrono>
@@ -407,6 +410,131 @@ __global__ __launch_bounds__(256) void count_merge_write_kernel(const u64 *__res
     }
 }
 
+// ---- the joint spectrum of two lists: J[ca][cb] = keys of A u B with those two count bytes ------------------------------------
+constexpr uint32_t JOINT_CORNER = 64;               // (br_amd/countops.py JOINT_CORNER) bins ca, cb < this live in LDS
+constexpr uint32_t JOINT_NONE = 0xFFFFFFFFu;          // a position that yields no pair
+// a u32 bin takes at most MERGE_TILE per tile: 2^21 tiles could add up to exactly 2^32, one tile fewer cannot
+constexpr uint32_t JOINT_FLUSH_TILES = (1u << 21) - 1u;
+
+// Thread's MERGE_PER_THREAD positions of the tile: pair[q] = ca << 8 | cb of the key at position q, JOINT_NONE for B's key of
+// an equal pair (decided at A's key, as in tile_merge_counts) and behind the tile's end; *both = keys of A found in B.
+__device__ __forceinline__ void tile_merge_pairs(const Tile &tl, uint64_t na, uint64_t nb, const u64 *sa, const u64 *sb, const uint8_t *sca,
+                                                 const uint8_t *scb, uint32_t pair[MERGE_PER_THREAD], uint32_t *both)
+{
+    const uint32_t len = tl.la + tl.lb;
+    const uint32_t d = threadIdx.x * MERGE_PER_THREAD < len ? threadIdx.x * MERGE_PER_THREAD : len;
+    uint32_t i = merge_split<uint32_t>(sa + 1, tl.la, sb + 1, tl.lb, d), j = d - i;
+    uint32_t nboth = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < MERGE_PER_THREAD; q++) {
+        pair[q] = JOINT_NONE;
+        if (d + q >= len)
+            continue;
+        // (i + j = d + q < la + lb: at least one piece has a key left)
+        const bool take_a = i < tl.la && (j >= tl.lb || sa[1 + i] <= sb[1 + j]);
+        if (take_a) {
+            const bool in_b = tl.b0 + j < nb && sb[1 + j] == sa[1 + i]; // (j == lb: the halo behind the piece, its count beside it)
+            pair[q] = ((uint32_t)sca[1 + i] << 8) | (in_b ? (uint32_t)scb[1 + j] : 0u);
+            nboth += in_b ? 1u : 0u;
+            i++;
+        } else {
+            const bool in_a = tl.a0 + i > 0 && sa[i] == sb[1 + j]; // (i == 0: the halo before the piece)
+            if (!in_a)
+                pair[q] = (uint32_t)scb[1 + j];
+            j++;
+        }
+    }
+    *both = nboth;
+}
+
+// corner[ca * JOINT_CORNER + cb] -> joint[ca * 256 + cb], one global add per non-zero bin; the corner is left cleared
+__device__ __forceinline__ void joint_flush(uint32_t *corner, u64 *__restrict__ joint)
+{
+    __syncthreads();
+    for (uint32_t x = threadIdx.x; x < JOINT_CORNER * JOINT_CORNER; x += 256u) {
+        const uint32_t v = corner[x];
+        if (v) {
+            atomicAdd(&joint[((x / JOINT_CORNER) << 8) | (x % JOINT_CORNER)], (u64)v);
+            corner[x] = 0u;
+        }
+    }
+    __syncthreads();
+}
+
+// One pass over the tiles: pass 1's checks and |A n B| (ctl as there), and every pair binned -- the corner in LDS, flushed
+// after the block's last tile and before a u32 bin could wrap, the pairs outside it straight to the global table.
+// A thread folds the equal pairs among its own positions into (pair, n) and adds each once.  Summing equal pairs across the
+// wave first (two leader rounds per position: ballots, one lane adds) was measured and lost, 9.6 against 8.2 ms per Gbp on the
+// bench's lists and on lists of nothing but 1s alike: same-address LDS adds are not what this pass waits for.
+__global__ __launch_bounds__(256) void count_joint_kernel(const u64 *__restrict__ a, const uint8_t *__restrict__ ca, uint64_t na,
+                                                          const u64 *__restrict__ b, const uint8_t *__restrict__ cb, uint64_t nb,
+                                                          const u64 *__restrict__ split, uint64_t n_tiles, u64 *__restrict__ joint,
+                                                          u64 *__restrict__ ctl)
+{
+    __shared__ u64 sa[MERGE_TILE + 2], sb[MERGE_TILE + 2];
+    __shared__ uint8_t sca[MERGE_TILE + 2], scb[MERGE_TILE + 2];
+    __shared__ uint32_t corner[JOINT_CORNER * JOINT_CORNER];
+    __shared__ uint32_t sh[4];
+    for (uint32_t x = threadIdx.x; x < JOINT_CORNER * JOINT_CORNER; x += 256u)
+        corner[x] = 0u;
+    uint32_t unflushed = 0; // tiles binned since the last flush (block-uniform)
+    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) { // block-uniform
+        const Tile tl = tile_load(a, na, b, nb, split, t, sa, sb); // (its barrier also orders the clearing of the corner)
+        tile_load_counts(tl, ca, na, cb, nb, sca, scb);
+        uint32_t bad = tl.ok ? 0u : ERR_ORDER;
+        for (uint32_t x = threadIdx.x; x < tl.la; x += 256u) {
+            if (tl.a0 + x > 0 && sa[x] >= sa[1 + x]) // (x == 0: against the halo)
+                bad |= ERR_ORDER;
+            if (!sca[1 + x])
+                bad |= ERR_ZERO;
+        }
+        for (uint32_t x = threadIdx.x; x < tl.lb; x += 256u) {
+            if (tl.b0 + x > 0 && sb[x] >= sb[1 + x])
+                bad |= ERR_ORDER;
+            if (!scb[1 + x])
+                bad |= ERR_ZERO;
+        }
+        uint32_t pair[MERGE_PER_THREAD], n[MERGE_PER_THREAD], both = 0;
+        tile_merge_pairs(tl, na, nb, sa, sb, sca, scb, pair, &both);
+#pragma unroll
+        for (uint32_t q = 0; q < MERGE_PER_THREAD; q++)
+            n[q] = 1u;
+#pragma unroll
+        for (uint32_t q = 0; q < MERGE_PER_THREAD; q++)
+#pragma unroll
+            for (uint32_t r = q + 1; r < MERGE_PER_THREAD; r++)
+                if (pair[q] != JOINT_NONE && pair[r] == pair[q]) {
+                    n[q] += n[r]; // (n[r] is still 1: a pair folded into an earlier one is JOINT_NONE by now)
+                    pair[r] = JOINT_NONE;
+                }
+#pragma unroll
+        for (uint32_t q = 0; q < MERGE_PER_THREAD; q++)
+            if (pair[q] != JOINT_NONE) {
+                const uint32_t pa = pair[q] >> 8, pb = pair[q] & 255u;
+                if (pa < JOINT_CORNER && pb < JOINT_CORNER)
+                    atomicAdd(&corner[pa * JOINT_CORNER + pb], n[q]); // (the result is not used: an LDS add that returns nothing)
+                else
+                    atomicAdd(&joint[pair[q]], (u64)n[q]);
+            }
+        const uint32_t n_both = block_sum(both, sh);
+        const uint32_t n_order = block_sum(bad & ERR_ORDER, sh);
+        const uint32_t n_zero = block_sum(bad & ERR_ZERO, sh);
+        if (threadIdx.x == 0) {
+            if (n_both)
+                atomicAdd(&ctl[0], (u64)n_both);
+            if (n_order || n_zero)
+                atomicOr(&ctl[1], (u64)((n_order ? ERR_ORDER : 0u) | (n_zero ? ERR_ZERO : 0u)));
+        }
+        __syncthreads(); // (the pieces are written again in the next trip)
+        if (++unflushed == JOINT_FLUSH_TILES) {
+            joint_flush(corner, joint);
+            unflushed = 0;
+        }
+    }
+    if (unflushed)
+        joint_flush(corner, joint);
+}
+
 // The spectrum of a list: hist[v] += count bytes equal to v.  Bins per wave in LDS, flushed once per block.
 __global__ __launch_bounds__(256) void count_hist_kernel(const uint8_t *__restrict__ cnts, uint64_t n, u64 *__restrict__ hist)
 {
@@ -664,6 +792,67 @@ int count_merge_write(const char *me, const CountPlan &plan, uint64_t *d_kout, u
     return BRX_OK;
 }
 
+// The joint spectrum of two lists, J[0][0] = 0, accumulated in scratch and copied whole -- to d_out (device) or h_out (host),
+// whichever is given -- only when both lists passed pass 1's checks: a refusal leaves them untouched.  *both = |A n B|.
+// Returns after `s` has been synchronised.
+int count_joint(const char *me, const uint64_t *d_ka, const uint8_t *d_ca, uint64_t na, const uint64_t *d_kb, const uint8_t *d_cb,
+                uint64_t nb, hipStream_t s, uint64_t *d_out, uint64_t *h_out, uint64_t *both)
+{
+    constexpr uint64_t BINS = 65536, BYTES = BINS * sizeof(u64);
+    if (((!d_ka || !d_ca) && na) || ((!d_kb || !d_cb) && nb) || na > (1ull << 62) || nb > (1ull << 62)) {
+        set_error("%s: null keys or counts, or more than 2^62 entries", me);
+        return BRX_ERR_ARG;
+    }
+    *both = 0;
+    const uint64_t n_tiles = (na + nb + MERGE_TILE - 1) / MERGE_TILE;
+    DevScratch ws;
+    u64 *d_split = nullptr, *d_ctl = nullptr, *d_joint = nullptr; // ctl: [0] |A n B|, [1] error bits
+    BRX_TRY(ws.get(&d_split, n_tiles + 1));
+    BRX_TRY(ws.get(&d_ctl, 2));
+    BRX_TRY(ws.get(&d_joint, BINS));
+    u64 ctl[2] = {0, 0};
+    hipError_t e = hipMemsetAsync(d_ctl, 0, 16, s);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(d_joint, 0, BYTES, s);
+    if (e == hipSuccess && n_tiles) {
+        KernelTimer kt("count_joint", s);
+        const u64 *ka = (const u64 *)d_ka, *kb = (const u64 *)d_kb;
+        merge_split_kernel<<<read_grid((n_tiles + 256) / 256, 256u * 16u), 256, 0, s>>>(ka, na, kb, nb, n_tiles, d_split);
+        count_joint_kernel<<<read_grid(n_tiles, 256u * 16u), 256, 0, s>>>(ka, d_ca, na, kb, d_cb, nb, d_split, n_tiles, d_joint, d_ctl);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(ctl, d_ctl, 16, hipMemcpyDeviceToHost, s);
+    hipError_t e2 = hipStreamSynchronize(s);
+    if (e != hipSuccess || e2 != hipSuccess) {
+        set_error("%s: joint spectrum: %s", me, hipGetErrorString(e != hipSuccess ? e : e2));
+        return BRX_ERR_HIP;
+    }
+    if (ctl[1] & ERR_ORDER) {
+        set_error("%s: the keys of an input do not ascend strictly (unordered or repeated keys)", me);
+        return BRX_ERR_ARG;
+    }
+    if (ctl[1] & ERR_ZERO) {
+        set_error("%s: a count of 0 in an input (a listed k-mer was seen at least once)", me);
+        return BRX_ERR_ARG;
+    }
+    if (ctl[0] > na || ctl[0] > nb) {
+        set_error("%s: joint spectrum: |A|=%llu |B|=%llu |A n B|=%llu", me, (u64)na, (u64)nb, ctl[0]);
+        return BRX_ERR_HIP;
+    }
+    {
+        KernelTimer kt("count_joint", s);
+        e = d_out ? hipMemcpyAsync(d_out, d_joint, BYTES, hipMemcpyDeviceToDevice, s) : hipMemcpyAsync(h_out, d_joint, BYTES, hipMemcpyDeviceToHost, s);
+    }
+    e2 = hipStreamSynchronize(s); // the scratch goes back to the pool on return
+    if (e != hipSuccess || e2 != hipSuccess) {
+        set_error("%s: joint spectrum, copying out: %s", me, hipGetErrorString(e != hipSuccess ? e : e2));
+        return BRX_ERR_HIP;
+    }
+    *both = ctl[0];
+    return BRX_OK;
+}
+
 // The floor of `a op b` before min_count (include/brx.h "count lists", countops.result_floor): 0 = refused, message set
 uint32_t result_floor(const char *me, int op, uint32_t fa, uint32_t fb)
 {
@@ -796,6 +985,70 @@ int brx_counts_combine_device(const uint64_t *d_ka, const uint8_t *d_ca, uint64_
         return BRX_ERR_ARG;
     }
     return count_merge_write(me, plan, d_kout, d_cout, s);
+}
+
+int brx_counts_joint_device(const uint64_t *d_ka, const uint8_t *d_ca, uint64_t na, const uint64_t *d_kb, const uint8_t *d_cb,
+                            uint64_t nb, uint64_t *d_joint, uint64_t *sizes3, void *stream)
+{
+    const char *me = "brx_counts_joint_device";
+    if (!d_joint) {
+        set_error("%s: null d_joint", me);
+        return BRX_ERR_ARG;
+    }
+    const uint64_t bytes = 65536 * sizeof(uint64_t);
+    if (overlap_bytes(d_joint, bytes, d_ka, na * 8) || overlap_bytes(d_joint, bytes, d_kb, nb * 8) || overlap_bytes(d_joint, bytes, d_ca, na) ||
+        overlap_bytes(d_joint, bytes, d_cb, nb)) {
+        set_error("%s: d_joint overlaps an input", me);
+        return BRX_ERR_ARG;
+    }
+    uint64_t both = 0;
+    BRX_TRY(count_joint(me, d_ka, d_ca, na, d_kb, d_cb, nb, (hipStream_t)stream, d_joint, nullptr, &both));
+    if (sizes3) {
+        sizes3[0] = na;
+        sizes3[1] = nb;
+        sizes3[2] = both;
+    }
+    return BRX_OK;
+}
+
+int brx_counts_compare(const brx_counts_t *a, const brx_counts_t *b, uint64_t *joint65536, uint64_t *stats8)
+{
+    const char *me = "brx_counts_compare";
+    BRX_TRY(list_ok(me, a));
+    BRX_TRY(list_ok(me, b));
+    if (!joint65536) {
+        set_error("%s: null joint65536", me);
+        return BRX_ERR_ARG;
+    }
+    if (a->k != b->k || a->device != b->device) {
+        set_error("%s: the operands differ: a has k = %d on device %d, b has k = %d on device %d", me, a->k, a->device, b->k, b->device);
+        return BRX_ERR_ARG;
+    }
+    auto t0 = Clock::now();
+    BRX_TRY(use_device(a->device));
+    OwnStream own;
+    BRX_HIP(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
+    std::vector<uint64_t> joint(65536);
+    uint64_t both = 0;
+    BRX_TRY(count_joint(me, a->d_keys, a->d_cnts, a->n, b->d_keys, b->d_cnts, b->n, own.s, nullptr, joint.data(), &both));
+    // every key of A u B fell in exactly one bin, none in [0][0]
+    const uint64_t either = a->n + b->n - both;
+    uint64_t binned = 0;
+    for (uint64_t v : joint)
+        binned += v;
+    if (joint[0] || binned != either || either > set_nbits(a->k)) {
+        set_error("%s: the joint spectrum holds %llu keys and %llu in bin [0][0], |A|=%llu |B|=%llu |A n B|=%llu at k=%d", me, (u64)binned,
+                  (u64)joint[0], (u64)a->n, (u64)b->n, (u64)both, a->k);
+        return BRX_ERR_HIP;
+    }
+    joint[0] = set_nbits(a->k) - either;
+    memcpy(joint65536, joint.data(), 65536 * sizeof(uint64_t));
+    if (stats8) {
+        const uint64_t ns = ns_since(t0);
+        const uint64_t st8[8] = {a->n, b->n, both, either, 0, ns, 0, ns};
+        memcpy(stats8, st8, sizeof st8);
+    }
+    return BRX_OK;
 }
 
 int brx_counts_info(const brx_counts_t *l, uint64_t *info4)

@@ -86,6 +86,15 @@ def combine_counts_device(d_ka: Optional[int], d_ca: Optional[int], na: int, d_k
     return int(n.value), (int(s3[0]), int(s3[1]), int(s3[2]))
 
 
+def joint_counts_device(d_ka: Optional[int], d_ca: Optional[int], na: int, d_kb: Optional[int], d_cb: Optional[int], nb: int,
+                        d_joint: int, stream: Optional[int] = None) -> Tuple[int, int, int]:
+    """(|A|, |B|, |A n B|) of two count lists on the device, their joint spectrum -- countops.joint, J[0][0] = 0 -- written
+    to d_joint, 65536 u64 on the device, row ca and column cb (brx_counts_joint_device).  A refusal leaves d_joint untouched"""
+    s3 = (C.c_uint64 * 3)()
+    _lib.check(_lib.lib().brx_counts_joint_device(d_ka, d_ca, na, d_kb, d_cb, nb, d_joint, s3, stream))
+    return int(s3[0]), int(s3[1]), int(s3[2])
+
+
 def _trust_opts(min_quality: int, acgt_only: bool, min_len: int = 0) -> "_lib.TrustOpts":
     """brx_trust_opts_t; min_quality is handed over as it is (0..255) so that the library's own refusal of 94 and more is seen"""
     _check_u8(min_quality, "min_quality")
@@ -632,6 +641,30 @@ class CountList:
 
     def __sub__(self, other):
         return self.combine(other, "sub") if isinstance(other, CountList) else NotImplemented
+
+    def joint(self, other: "CountList") -> np.ndarray:
+        """uint64[256][256], the joint spectrum of the two lists: J[ca][cb] = k-mers counted ca times here and cb times in
+        `other` (0: not listed; countops.joint), J[0][0] = 2^(2k-1) - |self u other|, so that the row sums are
+        self.spectrum() and the column sums other.spectrum().  Same k and device; floors refuse nothing; both lists are only
+        read (brx_counts_compare)"""
+        if not isinstance(other, CountList):
+            raise TypeError("count lists compare with count lists")
+        J = np.zeros((256, 256), dtype=np.uint64)
+        st = (C.c_uint64 * 8)()
+        _lib.check(_lib.lib().brx_counts_compare(self._h, other._h, J.ctypes.data_as(C.POINTER(C.c_uint64)), st))
+        self.compare_stats = {"a": int(st[0]), "b": int(st[1]), "both": int(st[2]), "either": int(st[3]), "ns_merge": int(st[5]),
+                              "ns_wall": int(st[7])}
+        return J
+
+    def compare(self, other: "CountList", min_a: int = 1, min_b: int = 1) -> dict:
+        """countops.compare_summary of the joint spectrum -- a, b, both, either, jaccard as Pcon.compare names them, the same
+        from min_a / min_b up, completeness, occurrences, error_rate and qv -- plus "joint" (the array of joint()) and
+        "floor_a", "floor_b": a k-mer a floored list does not hold counts as 0 there: fewer than floor times, or never"""
+        from . import countops
+        J = self.joint(other)
+        res = countops.compare_summary(J, self.k, min_a, min_b)
+        res.update(joint=J, floor_a=self.floor, floor_b=other.floor)
+        return res
 
     def spectrum(self) -> np.ndarray:
         """uint64[256], Counter.spectrum() of a table counter that loaded the same file: bin 0 the k-mers not listed, the

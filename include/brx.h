@@ -541,6 +541,26 @@ int brx_counts_combine_device(const uint64_t *d_ka, const uint8_t *d_ca, uint64_
                               uint64_t nb, int op, uint8_t min_count /* 0 means 1 */, uint64_t *d_kout,
                               uint8_t *d_cout /* may be NULL */, uint64_t cap, uint64_t *n_out, uint64_t *sizes3 /* may be NULL */,
                               void *stream);
+/* The JOINT SPECTRUM of two lists: J[ca][cb] = the number of keys of A u B whose count bytes are ca in A and cb in B (0 where
+ * the list does not hold the key), u64[65536] with row ca and column cb (br_amd/countops.py joint).  Counts are bytes as they
+ * are: 255 means "255 or more".  Shared and private k-mers, completeness, a k-mer-based error rate and the copy-number plot are
+ * sums over it (countops.compare_summary).  One pass of the merge above (timer "count_joint": split, the pass, the copy out):
+ * it reads what pass 1 reads, checks what pass 1 checks and writes nothing per key.  The bins ca, cb < 64 are kept per block in
+ * LDS (16 KB of u32 beside the pieces) and added to the table once per block -- and before a u32 bin could wrap; a thread folds
+ * the equal pairs of its 8 positions and adds each distinct pair once; pairs outside the corner go straight to the table, one
+ * global add each: a list made of large counts is slow, never wrong.
+ * Measured on the bench's 1 Gbp at k = 25, two half-job lists of 366 M entries each (tools/count_compare_bench.py,
+ * profiles/count_compare_bench.json; ms per Gbp, median of 5): "count_joint" 8.15, brx_counts_compare 8.74 wall, against 5.64
+ * for split + pass 1 + scan of a size-only brx_counts_combine_device over the same lists: 1.45x, from the 16 KB of bins (three
+ * workgroups per CU where pass 1 has four), not from the adds (DESIGN.md sections 4, 10).
+ * The raw entry has brx_counts_combine_device's stream contract: the inputs are read in the order of `stream`, the call returns
+ * after `stream` has been synchronised.  Either list may be empty, A and B may be the same arrays.  On success d_joint is
+ * overwritten as a whole, J[0][0] = 0, and sizes3 (may be NULL) receives |A|, |B|, |A n B|.  Unordered or repeated keys, a 0
+ * count in an input and a d_joint that overlaps an input are BRX_ERR_ARG with the cause named, and d_joint is untouched: the
+ * table is accumulated in scratch of the device pool and copied on success.                                                  */
+int brx_counts_joint_device(const uint64_t *d_ka, const uint8_t *d_ca, uint64_t na, const uint64_t *d_kb, const uint8_t *d_cb,
+                            uint64_t nb, uint64_t *d_joint /* u64[65536], row ca, column cb */, uint64_t *sizes3 /* may be NULL */,
+                            void *stream);
 /* The object: an immutable count list on one device.  Every entry below is host-path: it works on a stream of its own and
  * returns complete; a list may be read by any number of host threads at once.
  * A list answers lookups (get_counts, abundance) once brx_counts_lookup_prepare has built its bucket directory, about n/2
@@ -577,6 +597,13 @@ int brx_counts_device(const brx_counts_t *l, void **d_keys, void **d_counts, uin
  * stats8 (may be NULL): [0] |A|, [1] |B|, [2] |A n B|, [3] |result|, [4] 0, [5] ns merging, [6] 0, [7] ns wall.               */
 int brx_counts_combine(const brx_counts_t *a, const brx_counts_t *b, int op, uint8_t min_count /* 0 means 1 */, brx_counts_t **out,
                        uint64_t *stats8);
+/* Two lists side by side: joint65536 (host, u64[65536], row ca, column cb) receives their joint spectrum (above) with
+ * J[0][0] = 2^(2k-1) - |A u B|, so that the row sums are brx_counts_spectrum of a and the column sums that of b.  Same k and
+ * device (BRX_ERR_ARG otherwise, the message names both); a == b is allowed; both are only read; lookup directories are
+ * ignored.  Floors are taken as they are and refuse nothing: a key a floored list does not hold falls in row or column 0,
+ * which for a list of floor f > 1 means "fewer than f times, or never", and the rows (columns) 1 .. f - 1 are empty.
+ * stats8 (may be NULL): [0] |A|, [1] |B|, [2] |A n B|, [3] |A u B|, [4] 0, [5] ns merging, [6] 0, [7] ns wall.               */
+int brx_counts_compare(const brx_counts_t *a, const brx_counts_t *b, uint64_t *joint65536, uint64_t *stats8 /* may be NULL */);
 /* hist256[v] = entries with count v for v >= 1 (bins below the floor are 0, as a floored counter reports them), hist256[0] =
  * 2^(2k-1) - entries: the 256 numbers brx_counter_spectrum gives a table counter that loaded the same file.                   */
 int brx_counts_spectrum(const brx_counts_t *l, uint64_t *hist256);
