@@ -5,29 +5,31 @@
 //            A and d - a(d) keys of B; a(d) is found by a binary search on the diagonal d.  A tile is MERGE_TILE consecutive
 //            positions; merge_split_kernel finds a() at every tile border, once, for both passes.  The search keeps
 //            max(0, d - nb) <= a <= min(d, na) whatever the keys hold, and every index it reads lies inside that bracket.
-//   a tile   its piece of A and its piece of B go to LDS with one key before and one key behind each (the halo).  Thread t
-//            finds a() of its own diagonal, MERGE_PER_THREAD * t positions into the tile, by the same search in LDS, and
-//            merges MERGE_PER_THREAD keys serially.
-//   members  with ties A-first, A[i] is in B iff the first unconsumed B[j] equals it (j may be the halo behind the piece),
-//            and B[j] is in A iff i > 0 and A[i - 1] equals it (i - 1 may be the halo before the piece): no thread asks
-//            another one.  An operation is a keep rule over those two bits (KEEP_A / KEEP_B below).
-//   pass 1   merge_count_kernel: kept keys per tile, |A n B| summed with one atomic per tile, and the contract checked --
-//            every neighbouring pair of either list, the halo pairs included, must ascend strictly, and the borders must not
-//            run backwards (they cannot over ascending lists); otherwise the error bit is set and nothing is written.
-//   scan     the existing exclusive scan turns the tile counts into offsets, its total is the size of the result.
-//   pass 2   merge_write_kernel: the same merge, the kept keys compacted in LDS by a block scan of the threads' counts,
-//            then stored as one contiguous run per tile, 256 neighbouring keys per step.
-// The three launches share the profile timer "set_merge".  Blocks loop over tiles; the grid cap is read_grid()'s.
-//
-// Count lists (include/brx.h "count lists", br_amd/countops.py): add / max / min / sub of two sorted (key, count byte) lists,
-// the same split, tiles and serial merge with the count pieces in LDS beside the keys.
-//   pair     with ties A-first an equal pair is (key of A, key of B): it is decided where A's key is taken -- in_b and cb come
-//            off index 1 + j of B's pieces, possibly the halo BEHIND them -- and B's key of the pair yields nothing.
-//   keep     result >= min_count: a function of the counts, so pass 1 (count_merge_count_kernel) loads them too, and no size
-//            follows from |A|, |B|, |A n B|.  Pass 1 also refuses a 0 count.  Pass 2 (count_merge_write_kernel) compacts keys
-//            and counts in LDS, writes one run of each per tile and sums what it wrote: that must be the scanned total.
-//   LDS      pass 2: 2 x 2050 keys, 2048 staged keys, 2 x 2050 + 2048 count bytes: 55 KB static.
-// Timer "count_merge" for split, both passes and the scan; count_hist_kernel (a list's spectrum) under "count_hist".
+//   a tile   its piece of A and its piece of B go to LDS with one key before and one key behind each (the halo): tile_load,
+//            and tile_load_counts for the count bytes of a count list, indexed alike.
+//   walk     tile_walk: thread t finds a() of its own diagonal, MERGE_PER_THREAD * t positions into the tile, by the same
+//            search in LDS, and decides MERGE_PER_THREAD positions serially.  With ties A-first, A[i] is in B iff the first
+//            unconsumed B[j] equals it (j may be the halo behind the piece), and B[j] is in A iff i > 0 and A[i - 1] equals
+//            it (i - 1 may be the halo before the piece): no thread asks another one.  An equal pair is (key of A, key of
+//            B) and is decided where A's key is taken.  What is done with a decided position is the caller's: the count
+//            merge and the joint spectrum.  Set algebra (tile_merge) keeps the same loop written out: through the walk its
+//            "set_merge" timer measured up to 1.6 % slower than before on three of ten operations, beyond the noise allowed.
+//   check    tile_check: every neighbouring pair of either list, the halo pairs included, must ascend strictly, the borders
+//            must not run backwards (they cannot over ascending lists), and no count of a count list is 0.
+//   report   tile_report: |A n B| summed with one atomic per tile, the error bits or-ed; a set bit means nothing is written.
+//   place    tile_place: a thread's offset among the kept entries of its tile, by a block scan of the threads' counts.
+//   pass 1   split, then one kernel that loads, checks, walks and reports every tile; the existing exclusive scan turns the
+//            kernel's tile counts into offsets, its total is the size of the result (merge_pass1 on the host).
+//   pass 2   the same walk, the kept entries compacted in LDS at their place, then stored as one contiguous run per tile,
+//            256 neighbouring entries per step.
+// Blocks loop over tiles; the grid cap is read_grid()'s.  Three consumers:
+//   set algebra   an operation is a keep rule over "the other list holds it too" (KEEP_A / KEEP_B below).  merge_count_kernel,
+//            merge_write_kernel; the size of the result follows from |A|, |B|, |A n B|.  Timer "set_merge".
+//   count lists   (include/brx.h "count lists", br_amd/countops.py) add / max / min / sub of two sorted (key, count byte) lists;
+//            keep is result >= min_count: a function of the counts, so pass 1 (count_merge_count_kernel) loads them too and
+//            no size follows from |A|, |B|, |A n B|.  Pass 2 (count_merge_write_kernel) sums what it wrote: that must be the
+//            scanned total.  Its LDS: 2 x 2050 keys, 2048 staged keys, 2 x 2050 + 2048 count bytes, 55 KB static.  Timer
+//            "count_merge"; count_hist_kernel (a list's spectrum) under "count_hist".
 //   joint    count_joint_kernel: pass 1 without a keep rule -- the pair (ca, cb) of every key of A u B binned into u64[256][256],
 //            the bins below 64 x 64 in 16 KB of LDS per block (53 KB static with the pieces), the rest by global adds.  The
 //            table is built in scratch and copied out only when both lists passed the checks.  Timer "count_joint".
@@ -44,7 +46,8 @@ typedef unsigned long long u64;
 
 constexpr uint32_t MERGE_PER_THREAD = 8;                   // (br_amd/setops.py PER_THREAD)
 constexpr uint32_t MERGE_TILE = 256u * MERGE_PER_THREAD;   // (br_amd/setops.py TILE)
-constexpr uint32_t ERR_ORDER = 1u;
+constexpr uint32_t ERR_ORDER = 1u; // the keys of an input do not ascend strictly
+constexpr uint32_t ERR_ZERO = 2u;  // a 0 count in an input
 
 // bit 0: keep a key that the other list lacks, bit 1: keep a key that the other list holds too
 constexpr uint32_t KEEP_A[4] = {3u, 2u, 1u, 1u}; // union, intersection, difference, symmetric difference
@@ -117,7 +120,44 @@ __device__ __forceinline__ Tile tile_load(const u64 *__restrict__ a, uint64_t na
     return tl;
 }
 
-// Thread's MERGE_PER_THREAD positions of the tile: key[q], keep bit q of the result; *both = keys of A found in B.
+// The thread's MERGE_PER_THREAD positions of the tile, in order: at(q, from_a, i, j, paired) for every position q before the
+// tile's end -- the key is sa[1 + i] when from_a, else sb[1 + j]; paired: the other list holds it too.  Positions behind the
+// tile's end get no call: the caller pre-sets its outputs.  Returns the keys of A found in B among the positions.
+//   bracket  the search of the thread's diagonal reads only inside 0 <= i < la, 0 <= j < lb (merge_split's bracket).
+//   a key    i + j = d + q < la + lb at every position: at least one piece has a key left, and take_a reads sa[1 + i] only
+//            for i < la, sb[1 + j] only for j < lb.
+//   halo     in_b reads sb[1 + j] at j == lb (the entry behind B's piece, its count beside it) and in_a reads sa[i] at
+//            i == 0 (the entry before A's piece) only after the global index said that the list has such an entry.
+//   pair     ties A-first: an equal pair is decided at A's key (from_a, paired, B's entry at 1 + j); B's key of the pair
+//            comes next (not from_a, paired) and yields nothing of its own.
+template <typename At>
+__device__ __forceinline__ uint32_t tile_walk(const Tile &tl, uint64_t na, uint64_t nb, const u64 *sa, const u64 *sb, At at)
+{
+    const uint32_t len = tl.la + tl.lb;
+    const uint32_t d = threadIdx.x * MERGE_PER_THREAD < len ? threadIdx.x * MERGE_PER_THREAD : len;
+    uint32_t i = merge_split<uint32_t>(sa + 1, tl.la, sb + 1, tl.lb, d), j = d - i;
+    uint32_t nboth = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < MERGE_PER_THREAD; q++) {
+        if (d + q >= len)
+            continue;
+        const bool take_a = i < tl.la && (j >= tl.lb || sa[1 + i] <= sb[1 + j]);
+        if (take_a) {
+            const bool in_b = tl.b0 + j < nb && sb[1 + j] == sa[1 + i];
+            at(q, true, i, j, in_b);
+            nboth += in_b ? 1u : 0u;
+            i++;
+        } else {
+            const bool in_a = tl.a0 + i > 0 && sa[i] == sb[1 + j];
+            at(q, false, i, j, in_a);
+            j++;
+        }
+    }
+    return nboth;
+}
+
+// Set algebra's positions: key[q], keep bit q of the result; *both = keys of A found in B.  tile_walk's loop with the keep
+// rule written into it (see the head of the file); its invariants are tile_walk's, and a fix to one is a fix to both.
 __device__ __forceinline__ uint32_t tile_merge(const Tile &tl, uint64_t na, uint64_t nb, const u64 *sa, const u64 *sb, uint32_t keep_a,
                                                uint32_t keep_b, u64 key[MERGE_PER_THREAD], uint32_t *both)
 {
@@ -130,18 +170,17 @@ __device__ __forceinline__ uint32_t tile_merge(const Tile &tl, uint64_t na, uint
         key[q] = 0;
         if (d + q >= len)
             continue;
-        // (i + j = d + q < la + lb: at least one piece has a key left)
         const bool take_a = i < tl.la && (j >= tl.lb || sa[1 + i] <= sb[1 + j]);
         if (take_a) {
             const u64 x = sa[1 + i];
-            const bool in_b = tl.b0 + j < nb && sb[1 + j] == x; // (j == lb: the halo behind the piece)
+            const bool in_b = tl.b0 + j < nb && sb[1 + j] == x;
             key[q] = x;
             keep |= ((keep_a >> (in_b ? 1u : 0u)) & 1u) << q;
             nboth += in_b ? 1u : 0u;
             i++;
         } else {
             const u64 x = sb[1 + j];
-            const bool in_a = tl.a0 + i > 0 && sa[i] == x; // (i == 0: the halo before the piece)
+            const bool in_a = tl.a0 + i > 0 && sa[i] == x;
             key[q] = x;
             keep |= ((keep_b >> (in_a ? 1u : 0u)) & 1u) << q;
             j++;
@@ -149,6 +188,28 @@ __device__ __forceinline__ uint32_t tile_merge(const Tile &tl, uint64_t na, uint
     }
     *both = nboth;
     return keep;
+}
+
+// The thread's ERR_ORDER | ERR_ZERO bits for the tile: every pair (x - 1, x) of a list belongs to the tile that holds x, and
+// so does the count of x.  COUNTS false (set algebra): the count pieces are neither loaded nor tested.
+template <bool COUNTS>
+__device__ __forceinline__ uint32_t tile_check(const Tile &tl, const u64 *sa, const u64 *sb, const uint8_t *sca, const uint8_t *scb)
+{
+    uint32_t bad = tl.ok ? 0u : ERR_ORDER;
+#pragma unroll
+    for (uint32_t p = 0; p < 2u; p++) { // A's piece, then B's
+        const u64 *sk = p ? sb : sa;
+        const uint8_t *sc = p ? scb : sca;
+        const uint64_t p0 = p ? tl.b0 : tl.a0;
+        const uint32_t lp = p ? tl.lb : tl.la;
+        for (uint32_t x = threadIdx.x; x < lp; x += 256u) {
+            if (p0 + x > 0 && sk[x] >= sk[1 + x]) // (x == 0: against the halo)
+                bad |= ERR_ORDER;
+            if (COUNTS && !sc[1 + x])
+                bad |= ERR_ZERO;
+        }
+    }
+    return bad;
 }
 
 // sum of x over the block into every thread; sh holds 4 entries
@@ -163,7 +224,43 @@ __device__ __forceinline__ uint32_t block_sum(uint32_t x, uint32_t *sh)
     return sh[0] + sh[1] + sh[2] + sh[3];
 }
 
-// ctl[0] += |A n B| of the tile, ctl[1] |= ERR_ORDER
+// ctl[0] += |A n B| of the tile (both: the thread's share), ctl[1] |= the error bits any thread holds in bad.  A thread's
+// two bits are summed over the block in one word, a count of up to 256 in each half.
+__device__ __forceinline__ void tile_report(uint32_t both, uint32_t bad, uint32_t *sh, u64 *__restrict__ ctl)
+{
+    const uint32_t n_both = block_sum(both, sh);
+    const uint32_t n_bad = block_sum((bad & ERR_ORDER) | ((bad & ERR_ZERO) << 15), sh);
+    if (threadIdx.x == 0) {
+        if (n_both)
+            atomicAdd(&ctl[0], (u64)n_both);
+        if (n_bad)
+            atomicOr(&ctl[1], (u64)(((n_bad & 0xFFFFu) ? ERR_ORDER : 0u) | ((n_bad >> 16) ? ERR_ZERO : 0u)));
+    }
+}
+
+// The thread's place among the kept entries of the tile, `mine` of them its own: a wave scan, then the waves before.
+// *total = the kept entries of the tile, <= MERGE_TILE: a bit per position.  sh holds 4 entries; the caller's barrier at the
+// end of its trip keeps the next trip's sh apart from this one's reads.
+__device__ __forceinline__ uint32_t tile_place(uint32_t mine, uint32_t *sh, uint32_t *total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t inc = mine;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(inc, o);
+        if (lane >= (uint32_t)o)
+            inc += y;
+    }
+    if (lane == 63u)
+        sh[wave] = inc;
+    __syncthreads();
+    uint32_t at = inc - mine;
+    for (uint32_t w = 0; w < wave; w++)
+        at += sh[w];
+    *total = sh[0] + sh[1] + sh[2] + sh[3];
+    return at;
+}
+
+// pass 1 of set algebra: counts[t] = kept keys of tile t
 __global__ __launch_bounds__(256) void merge_count_kernel(const u64 *__restrict__ a, uint64_t na, const u64 *__restrict__ b, uint64_t nb,
                                                           const u64 *__restrict__ split, uint64_t n_tiles, uint32_t keep_a, uint32_t keep_b,
                                                           u64 *__restrict__ counts, u64 *__restrict__ ctl)
@@ -172,26 +269,14 @@ __global__ __launch_bounds__(256) void merge_count_kernel(const u64 *__restrict_
     __shared__ uint32_t sh[4];
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) { // block-uniform
         const Tile tl = tile_load(a, na, b, nb, split, t, sa, sb);
-        uint32_t bad = tl.ok ? 0u : 1u;
-        for (uint32_t x = threadIdx.x; x < tl.la; x += 256u)
-            if (tl.a0 + x > 0 && sa[x] >= sa[1 + x]) // (x == 0: against the halo)
-                bad = 1u;
-        for (uint32_t x = threadIdx.x; x < tl.lb; x += 256u)
-            if (tl.b0 + x > 0 && sb[x] >= sb[1 + x])
-                bad = 1u;
+        const uint32_t bad = tile_check<false>(tl, sa, sb, nullptr, nullptr);
         u64 key[MERGE_PER_THREAD];
         uint32_t both = 0;
         const uint32_t keep = tile_merge(tl, na, nb, sa, sb, keep_a, keep_b, key, &both);
         const uint32_t kept = block_sum((uint32_t)__popc(keep), sh);
-        const uint32_t n_both = block_sum(both, sh);
-        const uint32_t n_bad = block_sum(bad, sh);
-        if (threadIdx.x == 0) {
+        if (threadIdx.x == 0)
             counts[t] = kept;
-            if (n_both)
-                atomicAdd(&ctl[0], (u64)n_both);
-            if (n_bad)
-                atomicOr(&ctl[1], (u64)ERR_ORDER);
-        }
+        tile_report(both, bad, sh, ctl);
         __syncthreads(); // (the pieces are written again in the next trip)
     }
 }
@@ -203,27 +288,12 @@ __global__ __launch_bounds__(256) void merge_write_kernel(const u64 *__restrict_
 {
     __shared__ u64 sa[MERGE_TILE + 2], sb[MERGE_TILE + 2], so[MERGE_TILE];
     __shared__ uint32_t sh[4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) { // block-uniform
         const Tile tl = tile_load(a, na, b, nb, split, t, sa, sb);
         u64 key[MERGE_PER_THREAD];
-        uint32_t both = 0;
+        uint32_t both = 0, total = 0;
         const uint32_t keep = tile_merge(tl, na, nb, sa, sb, keep_a, keep_b, key, &both);
-        // the thread's place among the kept keys of the tile: a wave scan, then the waves before
-        const uint32_t mine = (uint32_t)__popc(keep);
-        uint32_t inc = mine;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(inc, o);
-            if (lane >= (uint32_t)o)
-                inc += y;
-        }
-        if (lane == 63u)
-            sh[wave] = inc;
-        __syncthreads();
-        uint32_t at = inc - mine;
-        for (uint32_t w = 0; w < wave; w++)
-            at += sh[w];
-        const uint32_t total = sh[0] + sh[1] + sh[2] + sh[3]; // <= MERGE_TILE: a bit per position
+        uint32_t at = tile_place((uint32_t)__popc(keep), sh, &total);
 #pragma unroll
         for (uint32_t q = 0; q < MERGE_PER_THREAD; q++)
             if ((keep >> q) & 1u)
@@ -238,8 +308,6 @@ __global__ __launch_bounds__(256) void merge_write_kernel(const u64 *__restrict_
 }
 
 // ---- count lists: the same merge with a count byte per key -------------------------------------------------------------------
-constexpr uint32_t ERR_ZERO = 2u; // a 0 count in an input
-
 // min(255, ca + cb), max, min, ca - cb (0 where cb >= ca); a count of 0 stands for "absent"
 __device__ __forceinline__ uint32_t count_op(uint32_t op, uint32_t ca, uint32_t cb)
 {
@@ -272,48 +340,28 @@ __device__ __forceinline__ void tile_load_counts(const Tile &tl, const uint8_t *
     __syncthreads();
 }
 
-// Thread's MERGE_PER_THREAD positions of the tile: key[q], byte q of *cnt the result count, keep bit q of the result
-// (result >= min_count, min_count >= 1); *both = keys of A found in B.  The B key of an equal pair yields nothing.
+// A count list's positions: key[q], byte q of *cnt the result count, keep bit q of the result (result >= min_count,
+// min_count >= 1); *both = keys of A found in B.  The B key of an equal pair yields nothing.
 __device__ __forceinline__ uint32_t tile_merge_counts(const Tile &tl, uint64_t na, uint64_t nb, const u64 *sa, const u64 *sb, const uint8_t *sca,
                                                       const uint8_t *scb, uint32_t op, uint32_t min_count, u64 key[MERGE_PER_THREAD], u64 *cnt,
                                                       uint32_t *both)
 {
-    const uint32_t len = tl.la + tl.lb;
-    const uint32_t d = threadIdx.x * MERGE_PER_THREAD < len ? threadIdx.x * MERGE_PER_THREAD : len;
-    uint32_t i = merge_split<uint32_t>(sa + 1, tl.la, sb + 1, tl.lb, d), j = d - i;
-    uint32_t keep = 0, nboth = 0;
+    uint32_t keep = 0;
     u64 cnts = 0;
 #pragma unroll
-    for (uint32_t q = 0; q < MERGE_PER_THREAD; q++) {
+    for (uint32_t q = 0; q < MERGE_PER_THREAD; q++)
         key[q] = 0;
-        if (d + q >= len)
-            continue;
-        // (i + j = d + q < la + lb: at least one piece has a key left)
-        const bool take_a = i < tl.la && (j >= tl.lb || sa[1 + i] <= sb[1 + j]);
-        uint32_t r = 0;
-        if (take_a) {
-            const u64 x = sa[1 + i];
-            const bool in_b = tl.b0 + j < nb && sb[1 + j] == x; // (j == lb: the halo behind the piece, its count beside it)
-            key[q] = x;
-            r = count_op(op, sca[1 + i], in_b ? (uint32_t)scb[1 + j] : 0u);
-            nboth += in_b ? 1u : 0u;
-            i++;
-        } else {
-            const u64 x = sb[1 + j];
-            const bool in_a = tl.a0 + i > 0 && sa[i] == x; // (i == 0: the halo before the piece)
-            key[q] = x;
-            r = in_a ? 0u : count_op(op, 0u, scb[1 + j]); // (the pair was decided at A's key)
-            j++;
-        }
+    *both = tile_walk(tl, na, nb, sa, sb, [&](uint32_t q, bool from_a, uint32_t i, uint32_t j, bool paired) {
+        key[q] = from_a ? sa[1 + i] : sb[1 + j];
+        const uint32_t r = from_a ? count_op(op, sca[1 + i], paired ? (uint32_t)scb[1 + j] : 0u) : paired ? 0u : count_op(op, 0u, scb[1 + j]);
         keep |= (r >= min_count ? 1u : 0u) << q;
         cnts |= (u64)r << (8u * q);
-    }
+    });
     *cnt = cnts;
-    *both = nboth;
     return keep;
 }
 
-// pass 1.  ctl[0] += |A n B| of the tile, ctl[1] |= ERR_ORDER / ERR_ZERO
+// pass 1 of a count merge: counts[t] = kept entries of tile t
 __global__ __launch_bounds__(256) void count_merge_count_kernel(const u64 *__restrict__ a, const uint8_t *__restrict__ ca, uint64_t na,
                                                                 const u64 *__restrict__ b, const uint8_t *__restrict__ cb, uint64_t nb,
                                                                 const u64 *__restrict__ split, uint64_t n_tiles, uint32_t op, uint32_t min_count,
@@ -325,33 +373,14 @@ __global__ __launch_bounds__(256) void count_merge_count_kernel(const u64 *__res
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) { // block-uniform
         const Tile tl = tile_load(a, na, b, nb, split, t, sa, sb);
         tile_load_counts(tl, ca, na, cb, nb, sca, scb);
-        uint32_t bad = tl.ok ? 0u : ERR_ORDER;
-        for (uint32_t x = threadIdx.x; x < tl.la; x += 256u) {
-            if (tl.a0 + x > 0 && sa[x] >= sa[1 + x]) // (x == 0: against the halo)
-                bad |= ERR_ORDER;
-            if (!sca[1 + x])
-                bad |= ERR_ZERO;
-        }
-        for (uint32_t x = threadIdx.x; x < tl.lb; x += 256u) {
-            if (tl.b0 + x > 0 && sb[x] >= sb[1 + x])
-                bad |= ERR_ORDER;
-            if (!scb[1 + x])
-                bad |= ERR_ZERO;
-        }
+        const uint32_t bad = tile_check<true>(tl, sa, sb, sca, scb);
         u64 key[MERGE_PER_THREAD], cnt = 0;
         uint32_t both = 0;
         const uint32_t keep = tile_merge_counts(tl, na, nb, sa, sb, sca, scb, op, min_count, key, &cnt, &both);
         const uint32_t kept = block_sum((uint32_t)__popc(keep), sh);
-        const uint32_t n_both = block_sum(both, sh);
-        const uint32_t n_order = block_sum(bad & ERR_ORDER, sh);
-        const uint32_t n_zero = block_sum(bad & ERR_ZERO, sh);
-        if (threadIdx.x == 0) {
+        if (threadIdx.x == 0)
             counts[t] = kept;
-            if (n_both)
-                atomicAdd(&ctl[0], (u64)n_both);
-            if (n_order || n_zero)
-                atomicOr(&ctl[1], (u64)((n_order ? ERR_ORDER : 0u) | (n_zero ? ERR_ZERO : 0u)));
-        }
+        tile_report(both, bad, sh, ctl);
         __syncthreads(); // (the pieces are written again in the next trip)
     }
 }
@@ -367,28 +396,13 @@ __global__ __launch_bounds__(256) void count_merge_write_kernel(const u64 *__res
     __shared__ u64 sa[MERGE_TILE + 2], sb[MERGE_TILE + 2], so[MERGE_TILE];
     __shared__ uint8_t sca[MERGE_TILE + 2], scb[MERGE_TILE + 2], sco[MERGE_TILE];
     __shared__ uint32_t sh[4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) { // block-uniform
         const Tile tl = tile_load(a, na, b, nb, split, t, sa, sb);
         tile_load_counts(tl, ca, na, cb, nb, sca, scb);
         u64 key[MERGE_PER_THREAD], cnt = 0;
-        uint32_t both = 0;
+        uint32_t both = 0, total = 0;
         const uint32_t keep = tile_merge_counts(tl, na, nb, sa, sb, sca, scb, op, min_count, key, &cnt, &both);
-        // the thread's place among the kept entries of the tile: a wave scan, then the waves before
-        const uint32_t mine = (uint32_t)__popc(keep);
-        uint32_t inc = mine;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(inc, o);
-            if (lane >= (uint32_t)o)
-                inc += y;
-        }
-        if (lane == 63u)
-            sh[wave] = inc;
-        __syncthreads();
-        uint32_t at = inc - mine;
-        for (uint32_t w = 0; w < wave; w++)
-            at += sh[w];
-        const uint32_t total = sh[0] + sh[1] + sh[2] + sh[3]; // <= MERGE_TILE: a bit per position
+        uint32_t at = tile_place((uint32_t)__popc(keep), sh, &total);
 #pragma unroll
         for (uint32_t q = 0; q < MERGE_PER_THREAD; q++)
             if ((keep >> q) & 1u) {
@@ -416,35 +430,20 @@ constexpr uint32_t JOINT_NONE = 0xFFFFFFFFu;          // a position that yields 
 // a u32 bin takes at most MERGE_TILE per tile: 2^21 tiles could add up to exactly 2^32, one tile fewer cannot
 constexpr uint32_t JOINT_FLUSH_TILES = (1u << 21) - 1u;
 
-// Thread's MERGE_PER_THREAD positions of the tile: pair[q] = ca << 8 | cb of the key at position q, JOINT_NONE for B's key of
-// an equal pair (decided at A's key, as in tile_merge_counts) and behind the tile's end; *both = keys of A found in B.
+// The joint's positions: pair[q] = ca << 8 | cb of the key at position q, JOINT_NONE for B's key of an equal pair (decided
+// at A's key) and behind the tile's end; *both = keys of A found in B.
 __device__ __forceinline__ void tile_merge_pairs(const Tile &tl, uint64_t na, uint64_t nb, const u64 *sa, const u64 *sb, const uint8_t *sca,
                                                  const uint8_t *scb, uint32_t pair[MERGE_PER_THREAD], uint32_t *both)
 {
-    const uint32_t len = tl.la + tl.lb;
-    const uint32_t d = threadIdx.x * MERGE_PER_THREAD < len ? threadIdx.x * MERGE_PER_THREAD : len;
-    uint32_t i = merge_split<uint32_t>(sa + 1, tl.la, sb + 1, tl.lb, d), j = d - i;
-    uint32_t nboth = 0;
 #pragma unroll
-    for (uint32_t q = 0; q < MERGE_PER_THREAD; q++) {
+    for (uint32_t q = 0; q < MERGE_PER_THREAD; q++)
         pair[q] = JOINT_NONE;
-        if (d + q >= len)
-            continue;
-        // (i + j = d + q < la + lb: at least one piece has a key left)
-        const bool take_a = i < tl.la && (j >= tl.lb || sa[1 + i] <= sb[1 + j]);
-        if (take_a) {
-            const bool in_b = tl.b0 + j < nb && sb[1 + j] == sa[1 + i]; // (j == lb: the halo behind the piece, its count beside it)
-            pair[q] = ((uint32_t)sca[1 + i] << 8) | (in_b ? (uint32_t)scb[1 + j] : 0u);
-            nboth += in_b ? 1u : 0u;
-            i++;
-        } else {
-            const bool in_a = tl.a0 + i > 0 && sa[i] == sb[1 + j]; // (i == 0: the halo before the piece)
-            if (!in_a)
-                pair[q] = (uint32_t)scb[1 + j];
-            j++;
-        }
-    }
-    *both = nboth;
+    *both = tile_walk(tl, na, nb, sa, sb, [&](uint32_t q, bool from_a, uint32_t i, uint32_t j, bool paired) {
+        if (from_a)
+            pair[q] = ((uint32_t)sca[1 + i] << 8) | (paired ? (uint32_t)scb[1 + j] : 0u);
+        else if (!paired)
+            pair[q] = (uint32_t)scb[1 + j];
+    });
 }
 
 // corner[ca * JOINT_CORNER + cb] -> joint[ca * 256 + cb], one global add per non-zero bin; the corner is left cleared
@@ -481,19 +480,7 @@ __global__ __launch_bounds__(256) void count_joint_kernel(const u64 *__restrict_
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) { // block-uniform
         const Tile tl = tile_load(a, na, b, nb, split, t, sa, sb); // (its barrier also orders the clearing of the corner)
         tile_load_counts(tl, ca, na, cb, nb, sca, scb);
-        uint32_t bad = tl.ok ? 0u : ERR_ORDER;
-        for (uint32_t x = threadIdx.x; x < tl.la; x += 256u) {
-            if (tl.a0 + x > 0 && sa[x] >= sa[1 + x]) // (x == 0: against the halo)
-                bad |= ERR_ORDER;
-            if (!sca[1 + x])
-                bad |= ERR_ZERO;
-        }
-        for (uint32_t x = threadIdx.x; x < tl.lb; x += 256u) {
-            if (tl.b0 + x > 0 && sb[x] >= sb[1 + x])
-                bad |= ERR_ORDER;
-            if (!scb[1 + x])
-                bad |= ERR_ZERO;
-        }
+        const uint32_t bad = tile_check<true>(tl, sa, sb, sca, scb);
         uint32_t pair[MERGE_PER_THREAD], n[MERGE_PER_THREAD], both = 0;
         tile_merge_pairs(tl, na, nb, sa, sb, sca, scb, pair, &both);
 #pragma unroll
@@ -516,15 +503,7 @@ __global__ __launch_bounds__(256) void count_joint_kernel(const u64 *__restrict_
                 else
                     atomicAdd(&joint[pair[q]], (u64)n[q]);
             }
-        const uint32_t n_both = block_sum(both, sh);
-        const uint32_t n_order = block_sum(bad & ERR_ORDER, sh);
-        const uint32_t n_zero = block_sum(bad & ERR_ZERO, sh);
-        if (threadIdx.x == 0) {
-            if (n_both)
-                atomicAdd(&ctl[0], (u64)n_both);
-            if (n_order || n_zero)
-                atomicOr(&ctl[1], (u64)((n_order ? ERR_ORDER : 0u) | (n_zero ? ERR_ZERO : 0u)));
-        }
+        tile_report(both, bad, sh, ctl);
         __syncthreads(); // (the pieces are written again in the next trip)
         if (++unflushed == JOINT_FLUSH_TILES) {
             joint_flush(corner, joint);
@@ -566,69 +545,102 @@ __global__ __launch_bounds__(256) void count_hist_kernel(const uint8_t *__restri
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-// Pass 1 and the scan of one combine; the scratch lives until the plan goes.
+// The two lists of one merge and what pass 1 found; the scratch lives until the plan goes.
 struct MergePlan {
+    MergePlan(const uint64_t *ka, const uint8_t *ca, uint64_t na_, const uint64_t *kb, const uint8_t *cb, uint64_t nb_)
+        : d_a((const u64 *)ka), d_b((const u64 *)kb), d_ca(ca), d_cb(cb), na(na_), nb(nb_)
+    {
+    }
     DevScratch ws;
-    const u64 *d_a = nullptr, *d_b = nullptr;
-    uint64_t na = 0, nb = 0, n_tiles = 0, total = 0, both = 0;
-    int op = 0;
-    u64 *d_split = nullptr, *d_counts = nullptr;
+    const u64 *d_a, *d_b;
+    const uint8_t *d_ca, *d_cb; // the count bytes of count lists; null for set algebra
+    uint64_t na, nb, n_tiles = 0, total = 0, both = 0;
+    uint32_t op = 0, min_count = 1;
+    u64 *d_split = nullptr, *d_counts = nullptr, *d_ctl = nullptr; // ctl: [0] |A n B|, [1] error bits, [2] entries pass 2 wrote
+    uint32_t grid() const { return read_grid(n_tiles, 256u * 16u); }
 };
 
-// *plan: the size of the result and |A n B|; BRX_ERR_ARG when a list does not ascend strictly.  Returns after `s` has been
-// synchronised.
-int merge_count(const char *me, const uint64_t *d_a, uint64_t na, const uint64_t *d_b, uint64_t nb, int op, hipStream_t s, MergePlan *plan)
+// the refusal of lists that are not there or too long; `counted`: count lists, the count bytes must be there too
+int lists_given(const char *me, const MergePlan &plan, bool counted)
 {
-    if (op < 0 || op > 3) {
-        set_error("%s: op=%d (BRX_SETOP_UNION 0, INTERSECT 1, DIFFERENCE 2, SYMDIFF 3)", me, op);
+    const uint64_t na = plan.na, nb = plan.nb;
+    if ((!plan.d_a && na) || (!plan.d_b && nb) || (counted && ((!plan.d_ca && na) || (!plan.d_cb && nb))) || na > (1ull << 62) ||
+        nb > (1ull << 62)) {
+        set_error("%s: %s", me, counted ? "null keys or counts, or more than 2^62 entries" : "null keys, or more than 2^62 of them");
         return BRX_ERR_ARG;
     }
-    if ((!d_a && na) || (!d_b && nb) || na > (1ull << 62) || nb > (1ull << 62)) {
-        set_error("%s: null keys, or more than 2^62 of them", me);
-        return BRX_ERR_ARG;
-    }
-    plan->d_a = (const u64 *)d_a;
-    plan->d_b = (const u64 *)d_b;
-    plan->na = na;
-    plan->nb = nb;
-    plan->op = op;
+    return BRX_OK;
+}
+
+// Pass 1 over the plan's lists, `counted` telling whether they are count lists: the split and launch(), the caller's
+// kernel that checks every tile and reports into plan->d_ctl (and, with `scan`, leaves its tile counts in plan->d_counts,
+// which the scan turns into offsets), under the timer `timer`.  *plan: n_tiles, |A n B| and, with `scan`, the size of the
+// result.  BRX_ERR_ARG when a list does not ascend strictly or holds a 0 count; `what` names the pass in a HIP failure.
+// Returns after `s` has been synchronised, or at once where both lists are empty.
+template <typename Launch>
+int merge_pass1(const char *me, const char *what, const char *timer, bool counted, bool scan, hipStream_t s, MergePlan *plan, Launch launch)
+{
+    BRX_TRY(lists_given(me, *plan, counted));
+    const uint64_t na = plan->na, nb = plan->nb;
     const uint64_t n_tiles = (na + nb + MERGE_TILE - 1) / MERGE_TILE;
     plan->n_tiles = n_tiles;
     if (!n_tiles)
         return BRX_OK;
-    const uint64_t n_sums = keys_scan_sums(n_tiles);
-    u64 *d_sums = nullptr, *d_ctl = nullptr; // ctl: [0] |A n B|, [1] error bits
+    const uint64_t n_sums = scan ? keys_scan_sums(n_tiles) : 0;
+    u64 *d_sums = nullptr;
     BRX_TRY(plan->ws.get(&plan->d_split, n_tiles + 1));
-    BRX_TRY(plan->ws.get(&plan->d_counts, n_tiles));
-    BRX_TRY(plan->ws.get(&d_sums, n_sums + 1));
-    BRX_TRY(plan->ws.get(&d_ctl, 2));
-    BRX_HIP(hipMemsetAsync(d_ctl, 0, 16, s));
+    if (scan) {
+        BRX_TRY(plan->ws.get(&plan->d_counts, n_tiles));
+        BRX_TRY(plan->ws.get(&d_sums, n_sums + 1));
+    }
+    BRX_TRY(plan->ws.get(&plan->d_ctl, 3));
+    BRX_HIP(hipMemsetAsync(plan->d_ctl, 0, 24, s));
     u64 ctl[2] = {0, 0}, total = 0;
     int st = BRX_OK;
     hipError_t e = hipSuccess;
     {
-        KernelTimer kt("set_merge", s);
+        KernelTimer kt(timer, s);
         merge_split_kernel<<<read_grid((n_tiles + 256) / 256, 256u * 16u), 256, 0, s>>>(plan->d_a, na, plan->d_b, nb, n_tiles, plan->d_split);
-        merge_count_kernel<<<read_grid(n_tiles, 256u * 16u), 256, 0, s>>>(plan->d_a, na, plan->d_b, nb, plan->d_split, n_tiles, KEEP_A[op],
-                                                                         KEEP_B[op], plan->d_counts, d_ctl);
-        if ((e = hipGetLastError()) == hipSuccess)
+        launch();
+        if ((e = hipGetLastError()) == hipSuccess && scan)
             st = keys_scan_exclusive(plan->d_counts, n_tiles, d_sums, s);
     }
-    if (st == BRX_OK && e == hipSuccess && (e = hipMemcpyAsync(ctl, d_ctl, 16, hipMemcpyDeviceToHost, s)) == hipSuccess)
+    if (st == BRX_OK && e == hipSuccess && (e = hipMemcpyAsync(ctl, plan->d_ctl, 16, hipMemcpyDeviceToHost, s)) == hipSuccess && scan)
         e = hipMemcpyAsync(&total, d_sums + n_sums, 8, hipMemcpyDeviceToHost, s);
     const hipError_t e2 = hipStreamSynchronize(s); // the scratch may go back to the pool when the caller drops the plan
     if (st != BRX_OK)
         return st;
     if (e != hipSuccess || e2 != hipSuccess) {
-        set_error("%s: merge, pass 1: %s", me, hipGetErrorString(e != hipSuccess ? e : e2));
+        set_error("%s: %s: %s", me, what, hipGetErrorString(e != hipSuccess ? e : e2));
         return BRX_ERR_HIP;
     }
-    if (ctl[1]) {
+    if (ctl[1] & ERR_ORDER) {
         set_error("%s: the keys of an input do not ascend strictly (unordered or repeated keys)", me);
         return BRX_ERR_ARG;
     }
+    if (ctl[1] & ERR_ZERO) {
+        set_error("%s: a count of 0 in an input (a listed k-mer was seen at least once)", me);
+        return BRX_ERR_ARG;
+    }
+    plan->total = total;
+    plan->both = ctl[0];
+    return BRX_OK;
+}
+
+// Pass 1 of set algebra.  *plan: the size of the result and |A n B|.
+int merge_count(const char *me, int op, hipStream_t s, MergePlan *plan)
+{
+    if (op < 0 || op > 3) {
+        set_error("%s: op=%d (BRX_SETOP_UNION 0, INTERSECT 1, DIFFERENCE 2, SYMDIFF 3)", me, op);
+        return BRX_ERR_ARG;
+    }
+    plan->op = (uint32_t)op;
+    BRX_TRY(merge_pass1(me, "merge, pass 1", "set_merge", false, true, s, plan, [&] {
+        merge_count_kernel<<<plan->grid(), 256, 0, s>>>(plan->d_a, plan->na, plan->d_b, plan->nb, plan->d_split, plan->n_tiles, KEEP_A[op],
+                                                       KEEP_B[op], plan->d_counts, plan->d_ctl);
+    }));
     // the four sizes follow from |A|, |B| and |A n B|: what the scan found must agree
-    const uint64_t both = ctl[0];
+    const uint64_t na = plan->na, nb = plan->nb, both = plan->both;
     uint64_t want = both; // intersection
     if (op == BRX_SETOP_UNION)
         want = na + nb - both;
@@ -636,12 +648,10 @@ int merge_count(const char *me, const uint64_t *d_a, uint64_t na, const uint64_t
         want = na - both;
     else if (op == BRX_SETOP_SYMDIFF)
         want = na + nb - 2 * both;
-    if (both > na || both > nb || total != want) {
-        set_error("%s: merge, pass 1: %llu keys kept, |A|=%llu |B|=%llu |A n B|=%llu", me, total, (u64)na, (u64)nb, (u64)both);
+    if (both > na || both > nb || plan->total != want) {
+        set_error("%s: merge, pass 1: %llu keys kept, |A|=%llu |B|=%llu |A n B|=%llu", me, (u64)plan->total, (u64)na, (u64)nb, (u64)both);
         return BRX_ERR_HIP;
     }
-    plan->total = total;
-    plan->both = both;
     return BRX_OK;
 }
 
@@ -652,9 +662,8 @@ int merge_write(const char *me, const MergePlan &plan, uint64_t *d_out, hipStrea
         return BRX_OK;
     {
         KernelTimer kt("set_merge", s);
-        merge_write_kernel<<<read_grid(plan.n_tiles, 256u * 16u), 256, 0, s>>>(plan.d_a, plan.na, plan.d_b, plan.nb, plan.d_split, plan.n_tiles,
-                                                                              KEEP_A[plan.op], KEEP_B[plan.op], plan.d_counts, (u64 *)d_out,
-                                                                              plan.total);
+        merge_write_kernel<<<plan.grid(), 256, 0, s>>>(plan.d_a, plan.na, plan.d_b, plan.nb, plan.d_split, plan.n_tiles, KEEP_A[plan.op],
+                                                      KEEP_B[plan.op], plan.d_counts, (u64 *)d_out, plan.total);
     }
     const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(s);
     if (e1 != hipSuccess || e2 != hipSuccess) {
@@ -662,12 +671,6 @@ int merge_write(const char *me, const MergePlan &plan, uint64_t *d_out, hipStrea
         return BRX_ERR_HIP;
     }
     return BRX_OK;
-}
-
-bool overlap(const void *p, uint64_t pn, const void *q, uint64_t qn)
-{
-    const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
-    return p && q && pn && qn && p0 < q0 + qn * 8 && q0 < p0 + pn * 8;
 }
 
 bool overlap_bytes(const void *p, uint64_t pbytes, const void *q, uint64_t qbytes)
@@ -679,92 +682,35 @@ bool overlap_bytes(const void *p, uint64_t pbytes, const void *q, uint64_t qbyte
 // ---- count lists ------------------------------------------------------------------------------------------------------------
 const char *const COUNTOP_NAMES = "BRX_COUNTOP_ADD 0, MAX 1, MIN 2, SUB 3";
 
-// Pass 1 and the scan of one count merge; the scratch lives until the plan goes.
-struct CountPlan {
-    DevScratch ws;
-    const u64 *d_ka = nullptr, *d_kb = nullptr;
-    const uint8_t *d_ca = nullptr, *d_cb = nullptr;
-    uint64_t na = 0, nb = 0, n_tiles = 0, total = 0, both = 0;
-    uint32_t op = 0, min_count = 1;
-    u64 *d_split = nullptr, *d_counts = nullptr, *d_ctl = nullptr; // ctl: [0] |A n B|, [1] error bits, [2] entries pass 2 wrote
-};
-
-// *plan: the size of the result and |A n B|; BRX_ERR_ARG when a list does not ascend strictly or holds a 0 count.  min_count
-// 1 .. 256.  Returns after `s` has been synchronised.
-int count_merge_count(const char *me, const uint64_t *d_ka, const uint8_t *d_ca, uint64_t na, const uint64_t *d_kb, const uint8_t *d_cb,
-                      uint64_t nb, int op, uint32_t min_count, hipStream_t s, CountPlan *plan)
+// Pass 1 of a count merge, min_count 1 .. 256.  *plan: the size of the result and |A n B|.
+int count_merge_count(const char *me, int op, uint32_t min_count, hipStream_t s, MergePlan *plan)
 {
     if (op < 0 || op > 3) {
         set_error("%s: op=%d (%s)", me, op, COUNTOP_NAMES);
         return BRX_ERR_ARG;
     }
-    if (((!d_ka || !d_ca) && na) || ((!d_kb || !d_cb) && nb) || na > (1ull << 62) || nb > (1ull << 62)) {
-        set_error("%s: null keys or counts, or more than 2^62 entries", me);
-        return BRX_ERR_ARG;
-    }
+    BRX_TRY(lists_given(me, *plan, true)); // (pass 1 would say it too: here so that it is said before min_count's range)
     if (min_count < 1u || min_count > 256u) {
         set_error("%s: min_count=%u (1 to 256)", me, min_count);
         return BRX_ERR_ARG;
     }
-    plan->d_ka = (const u64 *)d_ka;
-    plan->d_ca = d_ca;
-    plan->d_kb = (const u64 *)d_kb;
-    plan->d_cb = d_cb;
-    plan->na = na;
-    plan->nb = nb;
     plan->op = (uint32_t)op;
     plan->min_count = min_count;
-    const uint64_t n_tiles = (na + nb + MERGE_TILE - 1) / MERGE_TILE;
-    plan->n_tiles = n_tiles;
-    if (!n_tiles)
-        return BRX_OK;
-    const uint64_t n_sums = keys_scan_sums(n_tiles);
-    u64 *d_sums = nullptr;
-    BRX_TRY(plan->ws.get(&plan->d_split, n_tiles + 1));
-    BRX_TRY(plan->ws.get(&plan->d_counts, n_tiles));
-    BRX_TRY(plan->ws.get(&d_sums, n_sums + 1));
-    BRX_TRY(plan->ws.get(&plan->d_ctl, 3));
-    BRX_HIP(hipMemsetAsync(plan->d_ctl, 0, 24, s));
-    u64 ctl[2] = {0, 0}, total = 0;
-    int st = BRX_OK;
-    hipError_t e = hipSuccess;
-    {
-        KernelTimer kt("count_merge", s);
-        merge_split_kernel<<<read_grid((n_tiles + 256) / 256, 256u * 16u), 256, 0, s>>>(plan->d_ka, na, plan->d_kb, nb, n_tiles, plan->d_split);
-        count_merge_count_kernel<<<read_grid(n_tiles, 256u * 16u), 256, 0, s>>>(plan->d_ka, d_ca, na, plan->d_kb, d_cb, nb, plan->d_split, n_tiles,
-                                                                               plan->op, min_count, plan->d_counts, plan->d_ctl);
-        if ((e = hipGetLastError()) == hipSuccess)
-            st = keys_scan_exclusive(plan->d_counts, n_tiles, d_sums, s);
-    }
-    if (st == BRX_OK && e == hipSuccess && (e = hipMemcpyAsync(ctl, plan->d_ctl, 16, hipMemcpyDeviceToHost, s)) == hipSuccess)
-        e = hipMemcpyAsync(&total, d_sums + n_sums, 8, hipMemcpyDeviceToHost, s);
-    const hipError_t e2 = hipStreamSynchronize(s); // the scratch may go back to the pool when the caller drops the plan
-    if (st != BRX_OK)
-        return st;
-    if (e != hipSuccess || e2 != hipSuccess) {
-        set_error("%s: count merge, pass 1: %s", me, hipGetErrorString(e != hipSuccess ? e : e2));
-        return BRX_ERR_HIP;
-    }
-    if (ctl[1] & ERR_ORDER) {
-        set_error("%s: the keys of an input do not ascend strictly (unordered or repeated keys)", me);
-        return BRX_ERR_ARG;
-    }
-    if (ctl[1] & ERR_ZERO) {
-        set_error("%s: a count of 0 in an input (a listed k-mer was seen at least once)", me);
-        return BRX_ERR_ARG;
-    }
+    BRX_TRY(merge_pass1(me, "count merge, pass 1", "count_merge", true, true, s, plan, [&] {
+        count_merge_count_kernel<<<plan->grid(), 256, 0, s>>>(plan->d_a, plan->d_ca, plan->na, plan->d_b, plan->d_cb, plan->nb, plan->d_split,
+                                                             plan->n_tiles, plan->op, min_count, plan->d_counts, plan->d_ctl);
+    }));
     // (what is kept depends on the counts: no size follows from |A|, |B| and |A n B| but the bounds)
-    if (ctl[0] > na || ctl[0] > nb || total > na + nb - ctl[0]) {
-        set_error("%s: count merge, pass 1: %llu entries kept, |A|=%llu |B|=%llu |A n B|=%llu", me, total, (u64)na, (u64)nb, ctl[0]);
+    if (plan->both > plan->na || plan->both > plan->nb || plan->total > plan->na + plan->nb - plan->both) {
+        set_error("%s: count merge, pass 1: %llu entries kept, |A|=%llu |B|=%llu |A n B|=%llu", me, (u64)plan->total, (u64)plan->na,
+                  (u64)plan->nb, (u64)plan->both);
         return BRX_ERR_HIP;
     }
-    plan->total = total;
-    plan->both = ctl[0];
     return BRX_OK;
 }
 
 // pass 2 into d_kout and d_cout (may be null), plan->total entries each; returns after `s` has been synchronised
-int count_merge_write(const char *me, const CountPlan &plan, uint64_t *d_kout, uint8_t *d_cout, hipStream_t s)
+int count_merge_write(const char *me, const MergePlan &plan, uint64_t *d_kout, uint8_t *d_cout, hipStream_t s)
 {
     if (!plan.total)
         return BRX_OK;
@@ -772,10 +718,9 @@ int count_merge_write(const char *me, const CountPlan &plan, uint64_t *d_kout, u
     hipError_t e1 = hipSuccess;
     {
         KernelTimer kt("count_merge", s);
-        count_merge_write_kernel<<<read_grid(plan.n_tiles, 256u * 16u), 256, 0, s>>>(plan.d_ka, plan.d_ca, plan.na, plan.d_kb, plan.d_cb, plan.nb,
-                                                                                    plan.d_split, plan.n_tiles, plan.op, plan.min_count,
-                                                                                    plan.d_counts, (u64 *)d_kout, d_cout, plan.total,
-                                                                                    plan.d_ctl + 2);
+        count_merge_write_kernel<<<plan.grid(), 256, 0, s>>>(plan.d_a, plan.d_ca, plan.na, plan.d_b, plan.d_cb, plan.nb, plan.d_split,
+                                                            plan.n_tiles, plan.op, plan.min_count, plan.d_counts, (u64 *)d_kout, d_cout,
+                                                            plan.total, plan.d_ctl + 2);
         e1 = hipGetLastError();
     }
     if (e1 == hipSuccess)
@@ -799,57 +744,30 @@ int count_joint(const char *me, const uint64_t *d_ka, const uint8_t *d_ca, uint6
                 uint64_t nb, hipStream_t s, uint64_t *d_out, uint64_t *h_out, uint64_t *both)
 {
     constexpr uint64_t BINS = 65536, BYTES = BINS * sizeof(u64);
-    if (((!d_ka || !d_ca) && na) || ((!d_kb || !d_cb) && nb) || na > (1ull << 62) || nb > (1ull << 62)) {
-        set_error("%s: null keys or counts, or more than 2^62 entries", me);
-        return BRX_ERR_ARG;
-    }
+    MergePlan plan(d_ka, d_ca, na, d_kb, d_cb, nb);
+    BRX_TRY(lists_given(me, plan, true)); // (before the table is got and cleared: a refusal queues nothing)
     *both = 0;
-    const uint64_t n_tiles = (na + nb + MERGE_TILE - 1) / MERGE_TILE;
-    DevScratch ws;
-    u64 *d_split = nullptr, *d_ctl = nullptr, *d_joint = nullptr; // ctl: [0] |A n B|, [1] error bits
-    BRX_TRY(ws.get(&d_split, n_tiles + 1));
-    BRX_TRY(ws.get(&d_ctl, 2));
-    BRX_TRY(ws.get(&d_joint, BINS));
-    u64 ctl[2] = {0, 0};
-    hipError_t e = hipMemsetAsync(d_ctl, 0, 16, s);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(d_joint, 0, BYTES, s);
-    if (e == hipSuccess && n_tiles) {
-        KernelTimer kt("count_joint", s);
-        const u64 *ka = (const u64 *)d_ka, *kb = (const u64 *)d_kb;
-        merge_split_kernel<<<read_grid((n_tiles + 256) / 256, 256u * 16u), 256, 0, s>>>(ka, na, kb, nb, n_tiles, d_split);
-        count_joint_kernel<<<read_grid(n_tiles, 256u * 16u), 256, 0, s>>>(ka, d_ca, na, kb, d_cb, nb, d_split, n_tiles, d_joint, d_ctl);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(ctl, d_ctl, 16, hipMemcpyDeviceToHost, s);
-    hipError_t e2 = hipStreamSynchronize(s);
-    if (e != hipSuccess || e2 != hipSuccess) {
-        set_error("%s: joint spectrum: %s", me, hipGetErrorString(e != hipSuccess ? e : e2));
+    u64 *d_joint = nullptr;
+    BRX_TRY(plan.ws.get(&d_joint, BINS));
+    BRX_HIP(hipMemsetAsync(d_joint, 0, BYTES, s));
+    BRX_TRY(merge_pass1(me, "joint spectrum", "count_joint", true, false, s, &plan, [&] {
+        count_joint_kernel<<<plan.grid(), 256, 0, s>>>(plan.d_a, d_ca, na, plan.d_b, d_cb, nb, plan.d_split, plan.n_tiles, d_joint, plan.d_ctl);
+    }));
+    if (plan.both > na || plan.both > nb) {
+        set_error("%s: joint spectrum: |A|=%llu |B|=%llu |A n B|=%llu", me, (u64)na, (u64)nb, (u64)plan.both);
         return BRX_ERR_HIP;
     }
-    if (ctl[1] & ERR_ORDER) {
-        set_error("%s: the keys of an input do not ascend strictly (unordered or repeated keys)", me);
-        return BRX_ERR_ARG;
-    }
-    if (ctl[1] & ERR_ZERO) {
-        set_error("%s: a count of 0 in an input (a listed k-mer was seen at least once)", me);
-        return BRX_ERR_ARG;
-    }
-    if (ctl[0] > na || ctl[0] > nb) {
-        set_error("%s: joint spectrum: |A|=%llu |B|=%llu |A n B|=%llu", me, (u64)na, (u64)nb, ctl[0]);
-        return BRX_ERR_HIP;
-    }
+    hipError_t e = hipSuccess;
     {
         KernelTimer kt("count_joint", s);
         e = d_out ? hipMemcpyAsync(d_out, d_joint, BYTES, hipMemcpyDeviceToDevice, s) : hipMemcpyAsync(h_out, d_joint, BYTES, hipMemcpyDeviceToHost, s);
     }
-    e2 = hipStreamSynchronize(s); // the scratch goes back to the pool on return
+    const hipError_t e2 = hipStreamSynchronize(s); // the scratch goes back to the pool on return
     if (e != hipSuccess || e2 != hipSuccess) {
         set_error("%s: joint spectrum, copying out: %s", me, hipGetErrorString(e != hipSuccess ? e : e2));
         return BRX_ERR_HIP;
     }
-    *both = ctl[0];
+    *both = plan.both;
     return BRX_OK;
 }
 
@@ -920,6 +838,40 @@ int operands_list(const brx_set *a, const brx_set *b, hipStream_t s, Operands *o
     return BRX_OK;
 }
 
+// two count lists of one k on one device
+int lists_ok(const char *me, const brx_counts *a, const brx_counts *b)
+{
+    BRX_TRY(list_ok(me, a));
+    BRX_TRY(list_ok(me, b));
+    if (a->k != b->k || a->device != b->device) {
+        set_error("%s: the operands differ: a has k = %d on device %d, b has k = %d on device %d", me, a->k, a->device, b->k, b->device);
+        return BRX_ERR_ARG;
+    }
+    return BRX_OK;
+}
+
+// *out: a new set of this k on this device, the closed set of the n sorted keys of d_keys (set_build_from_keys takes them
+// over); on failure nothing is left behind.  Returns after `s` has been synchronised.
+int set_from_keys(const char *me, int k, int device, DevBuf<uint64_t> &d_keys, uint64_t n, hipStream_t s, brx_set **out)
+{
+    brx_set *set = nullptr;
+    int st = set_alloc_unwritten(k, device, &set);
+    if (st == BRX_OK)
+        st = set_build_from_keys(set, d_keys, n, s, me);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (st == BRX_OK && e != hipSuccess) {
+        set_error("%s: building the set: %s", me, hipGetErrorString(e));
+        st = BRX_ERR_HIP;
+    }
+    if (st != BRX_OK) {
+        if (set)
+            brx_set_free(set);
+        return st;
+    }
+    *out = set;
+    return BRX_OK;
+}
+
 } // namespace
 
 namespace brx {
@@ -931,8 +883,8 @@ int counts_merge(const char *me, const uint64_t *d_ka, const uint8_t *d_ca, uint
     d_kout.reset();
     d_cout.reset();
     *n_out = 0;
-    CountPlan plan;
-    BRX_TRY(count_merge_count(me, d_ka, d_ca, na, d_kb, d_cb, nb, op, min_count, s, &plan));
+    MergePlan plan(d_ka, d_ca, na, d_kb, d_cb, nb);
+    BRX_TRY(count_merge_count(me, op, min_count, s, &plan));
     if (both)
         *both = plan.both;
     if (!plan.total)
@@ -970,8 +922,8 @@ int brx_counts_combine_device(const uint64_t *d_ka, const uint8_t *d_ca, uint64_
         return BRX_ERR_ARG;
     }
     hipStream_t s = (hipStream_t)stream;
-    CountPlan plan;
-    BRX_TRY(count_merge_count(me, d_ka, d_ca, na, d_kb, d_cb, nb, op, min_count ? min_count : 1u, s, &plan));
+    MergePlan plan(d_ka, d_ca, na, d_kb, d_cb, nb);
+    BRX_TRY(count_merge_count(me, op, min_count ? min_count : 1u, s, &plan));
     *n_out = plan.total;
     if (sizes3) {
         sizes3[0] = na;
@@ -1014,14 +966,9 @@ int brx_counts_joint_device(const uint64_t *d_ka, const uint8_t *d_ca, uint64_t 
 int brx_counts_compare(const brx_counts_t *a, const brx_counts_t *b, uint64_t *joint65536, uint64_t *stats8)
 {
     const char *me = "brx_counts_compare";
-    BRX_TRY(list_ok(me, a));
-    BRX_TRY(list_ok(me, b));
+    BRX_TRY(lists_ok(me, a, b));
     if (!joint65536) {
         set_error("%s: null joint65536", me);
-        return BRX_ERR_ARG;
-    }
-    if (a->k != b->k || a->device != b->device) {
-        set_error("%s: the operands differ: a has k = %d on device %d, b has k = %d on device %d", me, a->k, a->device, b->k, b->device);
         return BRX_ERR_ARG;
     }
     auto t0 = Clock::now();
@@ -1090,12 +1037,7 @@ int brx_counts_combine(const brx_counts_t *a, const brx_counts_t *b, int op, uin
         return BRX_ERR_ARG;
     }
     *out = nullptr;
-    BRX_TRY(list_ok(me, a));
-    BRX_TRY(list_ok(me, b));
-    if (a->k != b->k || a->device != b->device) {
-        set_error("%s: the operands differ: a has k = %d on device %d, b has k = %d on device %d", me, a->k, a->device, b->k, b->device);
-        return BRX_ERR_ARG;
-    }
+    BRX_TRY(lists_ok(me, a, b));
     if (op < 0 || op > 3) {
         set_error("%s: op=%d (%s)", me, op, COUNTOP_NAMES);
         return BRX_ERR_ARG;
@@ -1201,23 +1143,9 @@ int brx_counts_finish(const brx_counts_t *l, uint8_t abundance, brx_set_t **out,
     st8[1] = kept;
     st8[4] = ns_since(t0);
     auto t1 = Clock::now();
-    brx_set *set = nullptr;
-    int st = set_alloc_unwritten(l->k, l->device, &set);
-    if (st == BRX_OK)
-        st = set_build_from_keys(set, d_keys, kept, s, me);
-    const hipError_t e = hipStreamSynchronize(s);
-    if (st == BRX_OK && e != hipSuccess) {
-        set_error("%s: building the set: %s", me, hipGetErrorString(e));
-        st = BRX_ERR_HIP;
-    }
-    if (st != BRX_OK) {
-        if (set)
-            brx_set_free(set);
-        return st;
-    }
+    BRX_TRY(set_from_keys(me, l->k, l->device, d_keys, kept, s, out));
     st8[6] = ns_since(t1);
     st8[7] = ns_since(t0);
-    *out = set;
     if (stats8)
         memcpy(stats8, st8, sizeof st8);
     return BRX_OK;
@@ -1232,13 +1160,13 @@ int brx_keys_combine_device(const uint64_t *d_a, uint64_t na, const uint64_t *d_
         return BRX_ERR_ARG;
     }
     *n_out = 0;
-    if (overlap(d_out, cap, d_a, na) || overlap(d_out, cap, d_b, nb)) {
+    if (overlap_bytes(d_out, cap * 8, d_a, na * 8) || overlap_bytes(d_out, cap * 8, d_b, nb * 8)) {
         set_error("%s: the output array overlaps an input", me);
         return BRX_ERR_ARG;
     }
     hipStream_t s = (hipStream_t)stream;
-    MergePlan plan;
-    BRX_TRY(merge_count(me, d_a, na, d_b, nb, op, s, &plan));
+    MergePlan plan(d_a, nullptr, na, d_b, nullptr, nb);
+    BRX_TRY(merge_count(me, op, s, &plan));
     *n_out = plan.total;
     if (sizes3) {
         sizes3[0] = na;
@@ -1279,8 +1207,8 @@ int brx_set_combine(const brx_set_t *a, const brx_set_t *b, int op, brx_set_t **
     auto t1 = Clock::now();
     DevBuf<uint64_t> d_res;
     {
-        MergePlan plan;
-        BRX_TRY(merge_count(me, o.d_a, o.na, o.d_b, o.nb, op, s, &plan));
+        MergePlan plan(o.d_a, nullptr, o.na, o.d_b, nullptr, o.nb);
+        BRX_TRY(merge_count(me, op, s, &plan));
         if (plan.total > set_nbits(a->k)) {
             set_error("%s: %llu keys in the result, only %llu exist at k=%d", me, (u64)plan.total, (u64)set_nbits(a->k), a->k);
             return BRX_ERR_HIP;
@@ -1297,23 +1225,9 @@ int brx_set_combine(const brx_set_t *a, const brx_set_t *b, int op, brx_set_t **
     o.keys_b.reset();
     st8[5] = ns_since(t1);
     auto t2 = Clock::now();
-    brx_set *set = nullptr;
-    int st = set_alloc_unwritten(a->k, a->device, &set);
-    if (st == BRX_OK)
-        st = set_build_from_keys(set, d_res, st8[3], s, me);
-    const hipError_t e = hipStreamSynchronize(s);
-    if (st == BRX_OK && e != hipSuccess) {
-        set_error("%s: building the set: %s", me, hipGetErrorString(e));
-        st = BRX_ERR_HIP;
-    }
-    if (st != BRX_OK) {
-        if (set)
-            brx_set_free(set);
-        return st;
-    }
+    BRX_TRY(set_from_keys(me, a->k, a->device, d_res, st8[3], s, out));
     st8[6] = ns_since(t2);
     st8[7] = ns_since(t0);
-    *out = set;
     if (stats8)
         memcpy(stats8, st8, sizeof st8);
     return BRX_OK;
@@ -1332,8 +1246,8 @@ int brx_set_compare(const brx_set_t *a, const brx_set_t *b, uint64_t *sizes3)
     BRX_HIP(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
     Operands o;
     BRX_TRY(operands_list(a, b, own.s, &o));
-    MergePlan plan;
-    BRX_TRY(merge_count(me, o.d_a, o.na, o.d_b, o.nb, BRX_SETOP_INTERSECT, own.s, &plan));
+    MergePlan plan(o.d_a, nullptr, o.na, o.d_b, nullptr, o.nb);
+    BRX_TRY(merge_count(me, BRX_SETOP_INTERSECT, own.s, &plan));
     sizes3[0] = o.na;
     sizes3[1] = o.nb;
     sizes3[2] = plan.both;
