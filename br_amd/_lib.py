@@ -150,6 +150,11 @@ SIGNATURES = {
     "brx_counts_abundance_batch_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint8, _vp, _vp, _vp, _vp]),
     "brx_counts_abundance_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint8, _vp, _vp, _vp]),
     "brx_counts_get_counts": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
+    "brx_kmertext_format_device": (C.c_int, [C.c_int, _vp, _vp, C.c_uint64, C.c_int, _vp, C.c_uint64, _u64p, _vp]),
+    "brx_kmertext_parse_device": (C.c_int, [_vp, C.c_uint64, C.c_int, _vp, _vp, C.c_uint64, _u64p, _u64p, _vp]),
+    "brx_counts_dump_text_fd": (C.c_int, [_vp, C.c_uint8, C.c_int, C.c_int, _u64p]),
+    "brx_counts_import_text_fd": (C.c_int, [C.c_int, C.c_int, C.c_uint8, C.c_int, _pp, _u64p]),
+    "brx_counts_from_arrays": (C.c_int, [C.c_int, _vp, _vp, C.c_uint64, C.c_uint8, C.c_int, _pp]),
     "brx_comm_unique_id":(C.c_int, [_vp]),
     "brx_comm_init": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _pp]),
     "brx_comm_init_all": (C.c_int, [C.c_int, C.POINTER(C.c_int), _pp]),

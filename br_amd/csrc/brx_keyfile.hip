@@ -25,6 +25,7 @@
 // by the fd while the other is copied.
 #include "brx_internal.hpp"
 #include "brx_index.hpp"
+#include "brx_keyio.hpp"
 
 #include <errno.h>
 #include <string.h>
@@ -48,33 +49,7 @@ const char KF_MAGIC[9] = "BRXKMERS";
 
 uint32_t grid_of(uint64_t items, uint32_t per_block) { return read_grid((items + per_block - 1) / per_block + (items ? 0 : 1), 256u * 16u); }
 
-// ---- scan -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 wave_incl_scan(u64 x, uint32_t lane)
-{
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 y = __shfl_up(x, o);
-        if (lane >= (uint32_t)o)
-            x += y;
-    }
-    return x;
-}
-
-// exclusive prefix of x over the 256 threads of the block, *total = their sum; sh holds 4 entries
-__device__ __forceinline__ u64 block_excl_scan(u64 x, u64 *sh, u64 *total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const u64 inc = wave_incl_scan(x, lane);
-    __syncthreads(); // (sh may still be read from the trip before)
-    if (lane == 63u)
-        sh[wave] = inc;
-    __syncthreads();
-    u64 off = 0;
-    for (uint32_t w = 0; w < wave; w++)
-        off += sh[w];
-    *total = sh[0] + sh[1] + sh[2] + sh[3];
-    return off + inc - x;
-}
-
+// ---- scan (wave_incl_scan, block_excl_scan: brx_keyio.hpp) ------------------------------------------------------------------
 // sums[c] = sum of chunk c of data
 __global__ __launch_bounds__(256) void scan_reduce_kernel(const u64 *__restrict__ data, uint64_t n, uint64_t n_chunks, u64 *__restrict__ sums)
 {
@@ -663,9 +638,10 @@ __global__ __launch_bounds__(256) void order_check_kernel(const uint64_t *__rest
             atomicOr(err, ERR_ORDER);
 }
 
-// ---- host side ------------------------------------------------------------------------------------------------------------
-typedef std::chrono::steady_clock Clock;
-uint64_t ns_since(Clock::time_point t0) { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - t0).count(); }
+// ---- host side (the pieces: brx_keyio.hpp) -----------------------------------------------------------------------------------
+} // namespace
+
+namespace brx {
 
 size_t slice_bytes()
 {
@@ -709,39 +685,9 @@ int read_upto(int fd, uint8_t *p, size_t want, size_t *got)
     return BRX_OK;
 }
 
-struct PinnedPair {
-    uint8_t *p[2] = {nullptr, nullptr};
-    ~PinnedPair()
-    {
-        host_buf_release(p[0]);
-        host_buf_release(p[1]);
-    }
-    int get(size_t bytes)
-    {
-        for (int i = 0; i < 2; i++)
-            if (!(p[i] = (uint8_t *)host_buf_acquire(bytes))) {
-                set_error("key file: no host memory for a piece of %llu bytes", (u64)bytes);
-                return BRX_ERR_NOMEM;
-            }
-        return BRX_OK;
-    }
-};
+} // namespace brx
 
-struct EventPair {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~EventPair()
-    {
-        for (int i = 0; i < 2; i++)
-            if (e[i])
-                (void)hipEventDestroy(e[i]);
-    }
-    int make()
-    {
-        for (int i = 0; i < 2; i++)
-            BRX_HIP(hipEventCreateWithFlags(&e[i], hipEventDisableTiming));
-        return BRX_OK;
-    }
-};
+namespace {
 
 void put_header(uint8_t *h, int k, bool with_counts, uint8_t floor, uint64_t n, uint64_t key_sum)
 {

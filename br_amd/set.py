@@ -95,6 +95,39 @@ def joint_counts_device(d_ka: Optional[int], d_ca: Optional[int], na: int, d_kb:
     return int(s3[0]), int(s3[1]), int(s3[2])
 
 
+def format_kmertext_device(k: int, d_keys: Optional[int], d_counts: Optional[int], n: int, d_text: Optional[int], cap: int,
+                           strand="lex", stream: Optional[int] = None) -> int:
+    """bytes of the k-mer text (kmertext.format_lines) of n entries on the device -- u64 keys, u8 counts, in the order given
+    -- written to d_text, which holds `cap` bytes (brx_kmertext_format_device).  A BrxError carries `needed` where the
+    library said how many bytes the text takes; d_text is untouched then"""
+    from . import kmertext
+    n_bytes = C.c_uint64(0)
+    st = _lib.lib().brx_kmertext_format_device(k, d_keys, d_counts, n, kmertext.strand_id(strand) if isinstance(strand, str) else int(strand),
+                                               d_text, cap, C.byref(n_bytes), stream)
+    try:
+        _lib.check(st)
+    except _lib.BrxError as e:
+        e.needed = int(n_bytes.value)
+        raise
+    return int(n_bytes.value)
+
+
+def parse_kmertext_device(d_text: Optional[int], n_bytes: int, k: int, d_keys: Optional[int], d_counts: Optional[int], cap: int,
+                          stream: Optional[int] = None) -> int:
+    """the number of non-empty lines of a k-mer text on the device, their (canonical key, min(255, value)) pairs written to
+    d_keys / d_counts in line order, neither sorted nor summed: kmertext.parse_lines (brx_kmertext_parse_device).  A
+    BrxError carries `needed` (a cap too small) and `err3` = (cause, line from 0, column) of the first malformed line"""
+    n, err3 = C.c_uint64(0), (C.c_uint64 * 3)()
+    st = _lib.lib().brx_kmertext_parse_device(d_text, n_bytes, k, d_keys, d_counts, cap, C.byref(n), err3, stream)
+    try:
+        _lib.check(st)
+    except _lib.BrxError as e:
+        e.needed = int(n.value)
+        e.err3 = (int(err3[0]), int(err3[1]), int(err3[2]))
+        raise
+    return int(n.value)
+
+
 def _trust_opts(min_quality: int, acgt_only: bool, min_len: int = 0) -> "_lib.TrustOpts":
     """brx_trust_opts_t; min_quality is handed over as it is (0..255) so that the library's own refusal of 94 and more is seen"""
     _check_u8(min_quality, "min_quality")
@@ -568,6 +601,49 @@ class CountList:
         h = C.c_void_p()
         _lib.check(_lib.lib().brx_counts_from_counter(counter._h, min_count, C.byref(h), None))
         return cls(h.value, counter.device)
+
+    @classmethod
+    def from_arrays(cls, k: int, keys, counts, floor: int = 1, device: int = 0) -> "CountList":
+        """the list of plain arrays: keys (canonical k-mer >> 1) strictly ascending and below 2^(2k-1), one count >= floor
+        each; checked on the device, a refusal names the first offending index (brx_counts_from_arrays)"""
+        _check_u8(floor, "floor")
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        counts = np.ascontiguousarray(counts, dtype=np.uint8)
+        if keys.ndim != 1 or counts.shape != keys.shape:
+            raise ValueError("one count per key, both one-dimensional")
+        h = C.c_void_p()
+        _lib.check(_lib.lib().brx_counts_from_arrays(k, keys.ctypes.data if keys.size else None, counts.ctypes.data if keys.size else None,
+                                                     keys.size, floor, device, C.byref(h)))
+        return cls(h.value, device)
+
+    @classmethod
+    def from_text(cls, f, k: Optional[int] = None, floor: int = 1, device: int = 0) -> "CountList":
+        """the list a k-mer text states -- KMER<TAB>COUNT lines as jellyfish dump -c -t and kmc_tools dump write them, in any
+        order, either strand, equal k-mers added up to 255: kmertext.parse -- read from the binary file object `f`
+        sequentially (pipes and gzip objects work); k None: from the first line; `floor`: the smallest count the text kept,
+        the list's floor (brx_counts_import_text_fd).  A malformed line is a BrxError that names its line"""
+        from . import hostio
+        _check_u8(floor, "floor")
+        h = C.c_void_p()
+        st = (C.c_uint64 * 8)()
+        with hostio.input_fd(f) as fd:
+            _lib.check(_lib.lib().brx_counts_import_text_fd(fd, int(k or 0), floor, device, C.byref(h), st))
+        l = cls(h.value, device)
+        l.text_stats = {"entries": int(st[0]), "bytes": int(st[1]), "lines": int(st[2]), "sorted": bool(st[3]), "ns_sort_sum": int(st[4]),
+                        "ns_parse": int(st[5]), "ns_fd": int(st[6]), "ns_wall": int(st[7])}
+        return l
+
+    def dump_text(self, f, min_count: int = 1, strand="lex") -> dict:
+        """write the list as k-mer text (kmertext.format_lines: ascending key order, not alphabetical) to the binary file
+        object `f`, the entries below min_count dropped; strand "lex" prints the alphabetically smaller strand, as Jellyfish
+        -C and KMC do, "canonical" the list's own (brx_counts_dump_text_fd)"""
+        from . import hostio, kmertext
+        _check_u8(min_count, "min_count")
+        st = (C.c_uint64 * 8)()
+        with hostio.output_fd(f) as fd:
+            _lib.check(_lib.lib().brx_counts_dump_text_fd(self._h, min_count, kmertext.strand_id(strand), fd, st))
+        return {"entries": int(st[0]), "bytes": int(st[1]), "slices": int(st[2]), "ns_compact": int(st[4]), "ns_format": int(st[5]),
+                "ns_fd": int(st[6]), "ns_wall": int(st[7])}
 
     def save(self, f, min_count: int = 1) -> dict:
         """write the list as a count file to the binary file object `f`, the entries below min_count dropped and the floor

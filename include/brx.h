@@ -652,6 +652,56 @@ int brx_counts_abundance_batch(const brx_counts_t *l, const uint8_t *bases, cons
                                uint8_t abundance, uint8_t *profile, uint32_t *hist, brx_abund_stats_t *stats);
 int brx_counts_get_counts(const brx_counts_t *l, const uint64_t *forward_kmers, uint32_t n, uint8_t *out);
 
+/* ---- k-mer text: count lists to and from KMER<TAB>COUNT lines.  No counterpart in the reference ---------------------------
+ * The form `jellyfish dump -c -t` and `kmc_tools transform ... dump` write, stated in numpy by br_amd/kmertext.py: per entry
+ * the k-mer as k upper-case letters, one TAB, the count in decimal, '\n'; a line takes k + 3 + (count >= 10) + (count >= 100)
+ * bytes.  Lines stand in ascending KEY order -- the list's order, not alphabetical.  The k-mer printed for key x, with c =
+ * (x << 1) | (popcount(x) & 1) the canonical k-mer: BRX_TEXT_CANONICAL c itself, BRX_TEXT_LEX the alphabetically smaller
+ * (A < C < G < T) of c and its reverse complement, the member Jellyfish -C and KMC print.  A count byte of 255 prints as 255.
+ * Reading: lines end with '\n', one '\r' before it is dropped, the bytes behind the last '\n' are a line too, empty lines are
+ * skipped.  A line is exactly k bytes of ACGTacgt, one or more of TAB / space, one or more decimal digits, nothing else;
+ * the digits' value saturates at 255 and must not be 0; either strand may be listed, the key is canonical(k-mer) >> 1.
+ * Kernels: br_amd/csrc/brx_kmertext.hip (profile timers "text_format", "text_parse", "text_runsum").                          */
+#define BRX_TEXT_LEX 0
+#define BRX_TEXT_CANONICAL 1
+/* The raw entries, with brx_counts_combine_device's stream contract: the inputs are read in the order of `stream`, the call
+ * returns after `stream` has been synchronised.  Scratch comes from the device pool.
+ * format: the lines of entries (d_keys, d_counts)[0 .. n) in the order given into d_text, *bytes_out of them.  A cap smaller
+ * than the text (or a NULL d_text) is BRX_ERR_ARG with *bytes_out set to what is needed and d_text untouched.  Keys are taken
+ * modulo 2^(2k-1), counts as they are.
+ * parse: ONE pair per non-empty line of d_text[0 .. bytes), in line order: (canonical key, min(255, value)).  It does NOT
+ * sort and does NOT sum equal keys.  The text must end at a line end, or its end is the end of its last line.  A cap smaller
+ * than the non-empty lines is BRX_ERR_ARG with *n_out set to their number.  On the first malformed line in text order:
+ * BRX_ERR_FORMAT, *n_out = 0, err3 = { cause, line within this text from 0 (empty lines counted), column }, the cause worded
+ * in brx_last_error; the outputs may have been written.  Causes: 1 a byte of the k-mer that is no base (column from 1), 2 /
+ * 3 a k-mer shorter / longer than k (column: its bases), 4 no count, 5 a byte that is no digit (column from 1), 6 a count
+ * of 0.  err3[0] == 0 otherwise.                                                                                              */
+int brx_kmertext_format_device(int k, const uint64_t *d_keys, const uint8_t *d_counts, uint64_t n, int strand, uint8_t *d_text, uint64_t cap,
+                               uint64_t *bytes_out, void *stream);
+int brx_kmertext_parse_device(const uint8_t *d_text, uint64_t bytes, int k, uint64_t *d_keys, uint8_t *d_counts, uint64_t cap, uint64_t *n_out,
+                              uint64_t *err3, void *stream);
+/* The host-path entries: a stream of their own, complete on return; the descriptor is written / read sequentially, never
+ * sought, through the two page-locked pieces of BRX_KEYFILE_SLICE_KB KiB of the key files.
+ * dump: the entries counted at least min_count times (as brx_counts_save_fd drops the others), slice by slice of
+ * piece / (k + 6) entries: a slice is formatted while the one before it is written.  stats8 (may be NULL): [0] entries,
+ * [1] text bytes, [2] slices, [4] ns compacting, [5] ns waiting for the device (formatting and copies not hidden behind the
+ * fd), [6] ns fd, [7] ns wall.
+ * import: the list a text states.  The host cuts every piece at its last '\n' and carries the rest in front of the next one;
+ * a line longer than a piece is BRX_ERR_FORMAT.  k == 0 takes k from the first non-empty line: its bytes before the first
+ * TAB / space (odd, 5..31; an empty text tells none: BRX_ERR_FORMAT).  The pairs are sorted (brx_sort_keys_device; skipped
+ * when they never descend), equal keys -- a k-mer twice, or both strands listed apart -- ADD saturating at 255, then a sum
+ * below `floor` is BRX_ERR_FORMAT, and `floor` becomes the list's floor.  A malformed line is BRX_ERR_FORMAT, the message
+ * "k-mer text: line N: cause" with N counted from 1 over the whole stream, empty lines included.  On any error *out is NULL.
+ * stats8 (may be NULL): [0] entries, [1] text bytes, [2] non-empty lines, [3] 1 if the sort ran, [4] ns sorting + summing,
+ * [5] ns parsing, [6] ns fd, [7] ns wall.
+ * from_arrays: the list of n host (key, count) pairs, checked on the device: keys strictly ascending and below 2^(2k-1),
+ * counts >= floor; BRX_ERR_ARG names the first offending index.  n == 0 is the valid empty list.                             */
+int brx_counts_dump_text_fd(const brx_counts_t *l, uint8_t min_count /* 0 means 1 */, int strand, int out_fd, uint64_t *stats8);
+int brx_counts_import_text_fd(int in_fd, int k /* 0: from the first line */, uint8_t floor /* 0 means 1 */, int device,
+                              brx_counts_t **out, uint64_t *stats8);
+int brx_counts_from_arrays(int k, const uint64_t *keys, const uint8_t *counts, uint64_t n, uint8_t floor /* 0 means 1 */,
+                           int device, brx_counts_t **out);
+
 /* ---- multi-GPU: reads shard over the GPUs, the set is exchanged ONCE -----------------------------
  * The reference is one process with rayon threads over shared memory (src/main.rs:30-33, src/lib.rs:72-139); on N
  * GPUs every rank counts and later corrects its own block of the reads, and the single exchange step is the k-mer
