@@ -1,5 +1,6 @@
-// Shared by the correction kernels (brx_correct.hip: groups of lanes per read; brx_onelane.hip: one lane per chunk of a
-// read): the pass description, the staging-slot layout, the control block and the wave-level k-mer scans.
+// Shared by the correction kernels (brx_group.hip, brx_one.hip, brx_revscan.hip: groups of lanes per read; brx_onelane.hip:
+// one lane per chunk of a read) and their host side (brx_correct.hip): the pass description, the staging-slot layout, the
+// control block, the wave-level k-mer scans and the launches the units call across files.
 #pragma once
 #include "brx_internal.hpp"
 #include "brx_index.hpp"
@@ -17,7 +18,7 @@ enum { CTL_WORK = 0, CTL_OVERFLOW = 1, CTL_ROUNDS = 2, CTL_PROBES = 3, CTL_TRIGG
        // (not reset per pass: summed over the attempt) unit records the replay kernel found UNWRITTEN -- every unit is
        // taken by exactly one lane and leaves a record, so this stays 0; the records are filled with ones before the
        // automaton runs so that a unit nobody scanned could not pass for a result (its read goes to the group kernel)
-       // the lean reverse pass (rev_scan_kernel, brx_correct.hip): reads handed back to the group kernel, this pass / summed
+       // the lean reverse pass (rev_scan_kernel, brx_revscan.hip): reads handed back to the group kernel, this pass / summed
        CTL_REV_HANDBACK = 13, CTL_REV_HANDBACK_SUM = 14,
        CTL_LANE_UNWRITTEN = 15,
        // ... and the triggers it left to the verify pass (this pass / summed)
@@ -76,12 +77,28 @@ struct PassParams {
     int rev_batch = 0;
 };
 
+// states of a group's machine; one_kernel (brx_one.hip) runs the first six of correct_kernel's (brx_group.hip)
+enum { ST_INIT = 0, ST_SCAN, ST_ERRLEN, ST_ALTS, ST_SCEN, ST_MORE, ST_WALK, ST_T1, ST_TSCORE, ST_TMORE, ST_GFOLLOW, ST_GVALID };
+
 __host__ __device__ __forceinline__ uint64_t slot_of(uint64_t o, uint64_t r, uint32_t slack)
 {
     return o + (o >> 2) * (uint64_t)slack + 64ull * r;
 }
 
 #if defined(__HIPCC__)
+// look-ahead k-mers per scenario probed in the SCEN round that starts at look-ahead index `sub`
+// (the lanes are dealt to the scenarios still alive, so once the wrong ones have died the survivor's
+// remaining look-aheads fit one round even in an 8-lane group)
+__device__ __forceinline__ uint32_t scen_width(uint32_t sub, uint32_t c, int G, uint32_t flags, uint32_t failmask)
+{
+    const uint32_t left = c - sub;
+    const uint32_t alive = 3u - (uint32_t)__popc(failmask & 7u);
+    // G / alive without a division (a variable u32 division is ~25 VALU instructions, paid by the whole wave)
+    const uint32_t share = alive <= 1u ? (uint32_t)G : (alive == 2u ? (uint32_t)G / 2u : (uint32_t)G / 3u);
+    const uint32_t cap = (sub == 0u && !(flags & 4u)) ? (share < 2u ? share : 2u) : share;
+    return left < cap ? left : cap;
+}
+
 template <int D>
 __device__ __forceinline__ uint32_t dpp_row_shr(uint32_t v)
 {
@@ -302,7 +319,12 @@ struct LanePassInfo {
 // A pass of One, Graph or GapSize with one lane per chunk of a read (brx_onelane.hip), as planned: plan.form is PASS_LANE.
 int lane_pass(brx_chain *ch, const PassParams &p, const PassPlan &plan, const LanePassInfo &info, hipStream_t s);
 void lane_ws_free(brx_chain *ch);
-// the group kernel over a list of reads (p.only / p.only_n), brx_correct.hip
+// the group kernel over a list of reads (p.only / p.only_n): brx_one.hip, brx_group.hip
 int launch_one_list(const PassParams &p, hipStream_t s);
 int launch_walk_list(const PassParams &p, int method, uint64_t path_lists, hipStream_t s);
+// one_kernel over the whole batch at the planned width (brx_one.hip)
+void launch_one(const PassParams &p, int width, uint32_t blocks, hipStream_t s);
+// a pass of the group kernels as planned (brx_group.hip); a reverse pass in lean form, plan.form PASS_REV_LEAN (brx_revscan.hip)
+int launch_group(PassParams p, const PassPlan &pl, const brx_method_t &md, uint32_t blocks, const char *timer, hipStream_t s);
+int launch_rev_lean(brx_chain *ch, PassParams p, const PassPlan &pl, const brx_method_t &md, uint64_t path_lists, hipStream_t s);
 } // namespace brx

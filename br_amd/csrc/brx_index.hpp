@@ -268,7 +268,7 @@ __device__ __forceinline__ bool probe(const uint32_t *__restrict__ bits, uint64_
 //                    bits live in the L2, i.e. at most 2^26 lines (4 MiB at 2^25).  Past that every lookup is a request
 //                    of its own on top of the line's (BASELINE configs[4]'s share, 2^28 lines: lane_mask_kernel 40.1 ms
 //                    with the bits, 35.1 without);
-//   LINE_BITS_KEPT   the group kernels' scans and walks (brx_correct.hip): always;
+//   LINE_BITS_KEPT   the group kernels' scans and walks (brx_group.hip, brx_one.hip, brx_revscan.hip): always;
 //   LINE_BITS_NEVER  single probes (lane_sync_kernel, succ_build_kernel, index_get_kernel).
 // (LB and TELL are template parameters so that each caller compiles to the code it had when it wrote this out itself.)
 enum LineBitsUse { LINE_BITS_NEVER, LINE_BITS_KEPT, LINE_BITS_IN_L2 };

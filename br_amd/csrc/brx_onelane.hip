@@ -3,7 +3,7 @@
 // Reference: Corrector::correct (src/correct/mod.rs:53-107), Exist<ScenarioOne>::correct_error
 // (src/correct/exist/mod.rs:112-150, get_score :21-47, one_more :49-70), ScenarioOne (src/correct/exist/one.rs:33-74).
 //
-// Why.  The group kernel (brx_correct.hip: one_kernel, 8 lanes per read) is instruction-issue-bound: ~440 vector
+// Why.  The group kernel (brx_one.hip: one_kernel, 8 lanes per read) is instruction-issue-bound: ~440 vector
 // instructions per wave-round with 29 of 64 lanes live, because the eight groups of a wave sit in different states and
 // every wave runs the union of the states' code every round (profiles/r2h_sq_summary.json).  Here every lane is its own
 // scalar state machine over its own stretch of a read, written as ONE straight-line round -- build the k-mer this state

@@ -6,7 +6,8 @@
 //                          environment).  A chain reads BRX_MAXPATH through it when it is created.
 //   plan_pass()            pure: tuning + facts of the set + the pass -> the form the pass takes (lane per chunk, group
 //                          kernel, lean reverse scan), how wide, through the index or the bit vector, in block form or not.
-//                          brx_correct.hip and brx_onelane.hip only execute what it returns.
+//                          brx_correct.hip's chain loop, the launches of the group kernels (brx_group.hip, brx_revscan.hip) and
+//                          brx_onelane.hip only execute what it returns.
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>

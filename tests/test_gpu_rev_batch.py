@@ -1,4 +1,4 @@
-"""The 64-lane reverse scans (one_kernel<64>, correct_kernel<64>, rev_scan_kernel in br_amd/csrc/brx_correct.hip) take
+"""The 64-lane reverse scans (one_kernel<64>, correct_kernel<64>, rev_scan_kernel in br_amd/csrc/brx_one.hip, brx_group.hip, brx_revscan.hip) take
 their trigger-free rounds REV_BLOCK = 4 at a time (rev_block_rounds, brx_correct.hpp): every round filters its 64
 positions through the index's occupancy bits, the survivors wait in a queue and are probed together, and the trigger
 test runs over the block's answer words.  These inputs aim at that loop: reverse passes that correct for their living

@@ -262,7 +262,7 @@ def test_every_switch_of_the_issue_is_in_the_record():
         plan = f.read()
     for n in names:
         assert f'("{n}"' in plan, n
-    for src in ("brx_correct.hip", "brx_onelane.hip", "brx_pipeline.hip"):
+    for src in ("brx_correct.hip", "brx_group.hip", "brx_one.hip", "brx_revscan.hip", "brx_onelane.hip", "brx_pipeline.hip"):
         with open(os.path.join(csrc, src)) as f:
             text = f.read()
         for n in names:

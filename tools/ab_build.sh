@@ -9,7 +9,7 @@ cd "$(dirname "$0")/../br_amd/csrc"
 name=$1; shift
 bdir=build_ab_$name
 mkdir -p $bdir ../lib/ab
-# every source of br_amd/csrc/Makefile (a library that lacks one links, and then fails to load)
+# every source of br_amd/csrc/Makefile (and --no-undefined, as there: a library that lacks one does not link)
 srcs=$(sed -n 's/^SRCS *= *//p' Makefile | sed 's/\.hip//g')
 pids=()
 for f in $srcs; do
@@ -18,6 +18,6 @@ for f in $srcs; do
 done
 for p in "${pids[@]}"; do wait $p; done
 objs=""; for f in $srcs; do objs="$objs $bdir/$f.o"; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../lib/ab/libbrx_$name.so $objs -lpthread -ldl -Wl,-rpath,/opt/rocm/lib
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../lib/ab/libbrx_$name.so $objs -lpthread -ldl -Wl,-rpath,/opt/rocm/lib -Wl,--no-undefined
 rm -rf $bdir
 echo "br_amd/lib/ab/libbrx_$name.so"
